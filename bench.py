@@ -21,11 +21,16 @@ the timed blocks use the fastest (--in-flight N fixes it).  Every step's work is
 clock stops).  The one-at-a-time figure is printed beside `value` (value_one_forward / ms_one_forward), and the per-kernel roofline block is
 measured with ONE forward in flight, so that a launch's duration is the kernel's own.
 
-Timing: W warm-up steps (at least 0.2 s of them, so the clocks have ramped), then BLOCKS
-of exactly K steps, each bracketed by barrier + torch.cuda.synchronize() on both sides and by a pair of HIP events
-on the launch stream, repeated until at least --min-seconds (0.5 s) of timed work has run (never fewer than 5
-blocks).  `value` / `ms_per_step` come from the MEDIAN block (max over ranks); min and the HIP-event median are
-reported beside it.  Prints ONE JSON line on rank 0 (contract: see the task statement).
+Timing: W warm-up steps (at least 0.2 s of them, so the clocks have ramped) and the choice of the
+number in flight, then ONE block of exactly K timed steps, bracketed by barrier + torch.cuda.synchronize() on both sides
+and by a pair of HIP events on the launch stream.  `value` / `ms_per_step` come from that block (max over ranks).  Prints
+ONE JSON line on rank 0 (contract: see the task statement).  `--dump-outputs DIR` writes what the last timed step returned
+(the gathered log-probs) as DIR/log_probs.npy; inputs and weights are seeded, so equal arguments give equal inputs.
+
+A plain run does only that.  `--full` adds everything else, after the headline: the same K-step blocks repeated until
+--min-seconds (0.5 s) of timed work (never fewer than 5 blocks; median / min / HIP-event median in timing.repeated_blocks),
+the delivered-bits check, one forward at a time, the per-kernel HIP-event roofline, the other gather mode (N > 1), the
+secondary legs (other precisions, shapes and BASELINE configs), the CPU baseline and the GPU clocks.
 """
 from __future__ import annotations
 
@@ -394,8 +399,9 @@ class Runner:
         self.sp.set_in_flight(best)
         self.tuning = {str(k): round(v, 4) for k, v in res.items()}
 
-    def timed_blocks(self, steps, warmup, min_seconds, max_blocks=400):
-        """-> (per-block wall seconds [max over ranks], per-block HIP-event seconds on this rank)"""
+    def timed_blocks(self, steps, warmup, min_seconds, max_blocks=400, min_blocks=5):
+        """-> (per-block wall seconds [max over ranks], per-block HIP-event seconds on this rank); min_blocks=1 with
+        min_seconds=0 times exactly one block of `steps` steps"""
         vdist, clock = self.vdist, self.clock
         t0 = time.perf_counter()
         n = 0
@@ -414,7 +420,7 @@ class Runner:
             clock.sync()
         walls, evs = [], []
         total = 0.0
-        while len(walls) < 5 or (total < min_seconds and len(walls) < max_blocks):
+        while len(walls) < min_blocks or (total < min_seconds and len(walls) < max_blocks):
             ev = clock.pair()
             vdist.barrier()
             clock.sync()
@@ -926,9 +932,10 @@ def bench_summary(line, flags):
         return {"ms": ms, "frac": frac}
 
     rl = line.get("roofline", {})
-    out = {"headline": pair(line.get("ms_per_step"), rl.get("forward_frac")),
-           "headline_one_forward": pair(line.get("ms_one_forward"), rl.get("forward_frac_one_forward")),
-           "headline_dominant_kernel": pair(rl.get("ms_per_launch"), rl.get("frac"))}
+    out = {"headline": pair(line.get("ms_per_step"), rl.get("forward_frac"))}
+    if "ms_one_forward" in line:   # (--full)
+        out["headline_one_forward"] = pair(line.get("ms_one_forward"), rl.get("forward_frac_one_forward"))
+        out["headline_dominant_kernel"] = pair(rl.get("ms_per_launch"), rl.get("frac"))
     if "fp32_equivalent_tflops" in rl:
         out["headline_fp32_equivalent_tflops"] = {"forward": rl.get("forward_fp32_equivalent_tflops"), "one_forward": rl.get("forward_fp32_equivalent_tflops_one_forward"),
                                                   "dominant_kernel": rl.get("fp32_equivalent_tflops")}
@@ -978,6 +985,26 @@ def summarize(walls, evs, steps, frames_per_step):
             "value": round(frames_per_step * steps / med, 1)}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, logp):
+    """--dump-outputs: the log-probs [world, B, T, 2] the last timed step returned, as out_dir/log_probs.npy (float32).  Over
+    DUMP_BYTES, a fixed seeded sample of whole sequences is written instead, with their flat indices over world x B in
+    log_probs_rows.npy (float64)."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    y = logp.detach().float().cpu().numpy()
+    rows = y.reshape(-1, *y.shape[2:])
+    per_row = rows[0].nbytes if len(rows) else 1
+    if y.nbytes > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(len(rows), size=max(1, DUMP_BYTES // per_row), replace=False))
+        np.save(out / "log_probs.npy", np.ascontiguousarray(rows[keep]))
+        np.save(out / "log_probs_rows.npy", keep.astype(np.float64))
+    else:
+        np.save(out / "log_probs.npy", y)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -992,12 +1019,19 @@ def main():
                          "fp32 accumulate: the same 1e-4 parity bar as fp32); fp32 = the same config on the exact-fp32 MFMA; bf16 = configs[2]: "
                          "bf16 MFMA operands, bf16 features")
     ap.add_argument("--plant-false-flag", action="store_true", help=argparse.SUPPRESS)  # tests: a planted failing self-check must fail the run
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="timed work per measurement, in K-step blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: repeated K-step blocks, the delivered-bits check, one "
+                         "forward at a time, the per-kernel roofline, the other gather mode, the secondary legs, the CPU baseline, the clocks "
+                         "(off by default: a plain run times exactly --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the log-probs the last timed step returned as DIR/log_probs.npy (float32; a seeded sample of "
+                         "sequences above 64 MB)")
+    ap.add_argument("--min-seconds", type=float, default=0.5, help="--full: timed work per measurement, in K-step blocks")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-events", action="store_true", help="skip the per-kernel HIP-event pass (no roofline per kernel)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the configs[2] / T=7 / configs[0] / configs[3] / configs[4] legs")
-    ap.add_argument("--legs", default="all", help="comma-separated secondary legs to run (default: all)")
+    ap.add_argument("--legs", default="all", help="comma-separated secondary legs to run under --full (default: all)")
     ap.add_argument("--in-flight", type=int, default=0,
                     help="independent forwards kept in flight (own HIP stream / library handle / workspace each): 0 = pick the fastest "
                          "of 1, 2, 3 for the shape during warm-up (default), N = exactly N")
@@ -1019,14 +1053,17 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-            # `python bench.py --gpus N` on its own: become the launcher (one rank per GPU under torch.distributed.run, this file again)
+            # `python bench.py --gpus N` on its own: launch the ranks (one per GPU under torch.distributed.run, this file again) as a
+            # child process and exit with its status
             import socket
+            import subprocess
 
             with socket.socket() as sock:
                 sock.bind(("127.0.0.1", 0))
                 port = sock.getsockname()[1]
-            os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                      "--master-addr", "127.0.0.1", "--master-port", str(port), str(Path(__file__).resolve()), *sys.argv[1:]])
+            rc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                                 "--master-addr", "127.0.0.1", "--master-port", str(port), str(Path(__file__).resolve()), *sys.argv[1:]]).returncode
+            sys.exit(rc if rc >= 0 else 128 - rc)
         args.gpus = world
     stub = args.stub_forward
     if args.backend == "gloo" and not stub:
@@ -1058,13 +1095,21 @@ def main():
     main_run = Runner(state, B, T, args.precision, dev, rank, world, args.gather, K, args.row_mode, args.splits, args.in_flight, stub)
     frames_per_step = world * B * T
 
-    # ---- the headline measurement
-    clocks0 = None if stub else gpu_state()
-    walls, evs = main_run.timed_blocks(K, args.warmup, args.min_seconds)
+    # ---- the headline measurement: exactly K timed steps
+    full = args.full
+    clocks0 = None if (stub or not full) else gpu_state()
+    walls, evs = main_run.timed_blocks(K, args.warmup, 0.0, min_blocks=1)
     head = summarize(walls, evs, K, frames_per_step)
-    ok = main_run.delivered()
+    ok = main_run.last is not None and bool(torch.isfinite(main_run.last).all().item())
+    if rank == 0 and args.dump_outputs and main_run.last is not None:
+        dump_outputs(args.dump_outputs, main_run.last)
+    repeated = None
+    if full:   # the same K-step blocks until --min-seconds of timed work: median / min / HIP-event median over the blocks
+        wr, er = main_run.timed_blocks(K, 2, args.min_seconds)
+        repeated = summarize(wr, er, K, frames_per_step)
+        ok = ok and main_run.delivered()
     gather_modes = None
-    if use_dist:  # the OTHER gather mode, for comparison
+    if use_dist and full:  # the OTHER gather mode, for comparison
         other = "final" if args.gather == "step" else "step"
         main_run.set_gather(other)
         w2, e2 = main_run.timed_blocks(K, 2, args.min_seconds / 2)
@@ -1078,7 +1123,7 @@ def main():
         main_run.set_gather(args.gather)
     # the same K-step blocks with ONE forward in flight (wall time of one forward; the kernels' own durations are measured this way)
     one = None
-    if main_run.sp.in_flight > 1:
+    if full and main_run.sp.in_flight > 1:
         tuned = main_run.sp.in_flight
         main_run.drain()
         main_run.sp.set_in_flight(1)
@@ -1086,9 +1131,10 @@ def main():
         one = summarize(w1, e1, K, frames_per_step)
         main_run.drain()
         main_run.sp.set_in_flight(tuned)
-    ktimes = [] if (args.no_events or stub) else main_run.kernel_profile(min(K, 20), (one or head)["ms_per_step"])
-    ktimes_in_flight = None if (args.no_events or stub) else main_run.kernel_profile_in_flight(min(K, 20), head["ms_per_step"])
-    clocks1 = None if stub else gpu_state()
+    no_events = args.no_events or stub or not full
+    ktimes = [] if no_events else main_run.kernel_profile(min(K, 20), (one or head)["ms_per_step"])
+    ktimes_in_flight = None if no_events else main_run.kernel_profile_in_flight(min(K, 20), head["ms_per_step"])
+    clocks1 = None if (stub or not full) else gpu_state()
 
     # ---- secondary legs, measured in the same run so that they are driver-witnessed
     secondary = {}
@@ -1151,7 +1197,7 @@ def main():
             return s
         return run
 
-    if not args.no_secondary:
+    if full and not args.no_secondary:
         if world == 1 and not use_dist and not stub:
             if (args.precision, B, T) != ("fp32", 32, 800):
                 leg("configs1_exact_fp32_b32_t800", shape_leg("fp32", 32, 800, None))   # the same config on the exact-fp32 MFMA (rounds 1-5's headline)
@@ -1187,20 +1233,23 @@ def main():
     all_ok = True
     if rank == 0:
         one_fwd = one or head
-        line = {
-            "metric": "audio frames/sec (whole node)", "value": head["value"],
-            # SURVEY section 8d's own definition (wall time of ONE forward at a time) right beside the throughput figure `value`
-            "value_one_forward": one_fwd["value"], "ms_one_forward": one_fwd["ms_per_step"], "unit": "frames/s",
+        line = {"metric": "audio frames/sec (whole node)", "value": head["value"]}
+        if full:   # SURVEY section 8d's own definition (wall time of ONE forward at a time) right beside the throughput figure `value`
+            line.update({"value_one_forward": one_fwd["value"], "ms_one_forward": one_fwd["ms_per_step"]})
+        line.update({
+            "unit": "frames/s",
             "n_gpus": world, "steps": K, "warmup": args.warmup, "ms_per_step": head["ms_per_step"],
-            "ms_per_step_min": head["ms_per_step_min"], "ms_per_step_hip_events_median": head["ms_per_step_hip_events_median"],
-            "timing": {"statistic": "median over blocks of exactly K steps (barrier + synchronize on both sides of every block; max over ranks)",
+            "ms_per_step_hip_events": head["ms_per_step_hip_events_median"],
+            "timing": {"statistic": "one block of exactly K timed steps (barrier + synchronize on both sides; max over ranks)",
                        "blocks": head["blocks"], "timed_seconds": head["timed_seconds"],
-                       "value_is": f"throughput with `in_flight` independent batches in flight; value_one_forward / ms_one_forward = one forward at a time"},
+                       "value_is": "throughput with `in_flight` independent batches in flight"
+                                   + ("; value_one_forward / ms_one_forward = one forward at a time" if full else "")},
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": DTYPE_LABEL[args.precision],
             "data": "synthetic (seeded U(-13.8,4.2) mel frames, seeded random-init weights)",
-            "config": {"workload": workload_label(args.precision, B, T) + "; `value` = throughput with `in_flight` independent batches in flight, "
-                                   "`value_one_forward` / `ms_one_forward` = SURVEY.md section 8d's own definition (wall time of ONE forward at a time)",
+            "config": {"workload": workload_label(args.precision, B, T) + "; `value` = throughput with `in_flight` independent batches in flight"
+                                   + (", `value_one_forward` / `ms_one_forward` = SURVEY.md section 8d's own definition (wall time of ONE forward at a time)"
+                                      if full else ""),
                        "global_batch": world * B, "frames_per_sequence": T,
                        "parallelism": f"batch-shard x{world}" + ((" + 1 RCCL all_gather of the [B,T,2] log-probs per forward" if args.gather == "step"
                                                                    else " + 1 RCCL all_gather of all K batches' log-probs per block") if use_dist else "")},
@@ -1208,14 +1257,24 @@ def main():
             "in_flight": main_run.sp.in_flight,
             "in_flight_note": "consecutive batches are independent: `in_flight` forwards are kept in flight, each on its own HIP stream with its own "
                               "library handle and workspace (voice_activity_detection_amd.PipelinedVAD; same bits as one at a time); picked during "
-                              "warm-up from the ms per step in in_flight_tuning; roofline.per_kernel, roofline.frac and roofline.forward_frac_one_forward "
-                              "are measured with ONE in flight, roofline.forward_frac with `in_flight`",
+                              "warm-up from the ms per step in in_flight_tuning"
+                              + ("; roofline.per_kernel, roofline.frac and roofline.forward_frac_one_forward are measured with ONE in flight, "
+                                 "roofline.forward_frac with `in_flight`" if full else ""),
             "in_flight_tuning_ms": main_run.tuning,
-            "ms_per_step_one_in_flight": one_fwd["ms_per_step"], "value_one_in_flight": one_fwd["value"],
-            "roofline": roofline_block(ktimes, args.precision, B, T, head["ms_per_step"], profiled_shape=True, ms_one_forward=one_fwd["ms_per_step"]),
-            "clocks": {"start": clocks0, "end": clocks1},
-            "collective_counts": all_counts,
-        }
+        })
+        if full:
+            line["timing"]["repeated_blocks"] = {
+                "statistic": "median over blocks of exactly K steps, repeated until --min-seconds of timed work (never fewer than 5 blocks)",
+                **{k: repeated[k] for k in ("ms_per_step", "ms_per_step_min", "ms_per_step_hip_events_median", "blocks", "timed_seconds", "value")}}
+            line.update({
+                "ms_per_step_one_in_flight": one_fwd["ms_per_step"], "value_one_in_flight": one_fwd["value"],
+                "roofline": roofline_block(ktimes, args.precision, B, T, head["ms_per_step"], profiled_shape=True, ms_one_forward=one_fwd["ms_per_step"]),
+                "clocks": {"start": clocks0, "end": clocks1},
+            })
+        else:   # the whole forward against the binding roof, from ms_per_step alone
+            line["roofline"] = roofline_block([], args.precision, B, T, head["ms_per_step"])
+            line["roofline"].pop("forward_frac_one_forward", None)
+        line["collective_counts"] = all_counts
         if ktimes_in_flight:   # the launches' durations in the mode `value` is quoted in (stretched by the overlap; sum / in_flight ~ ms_per_step)
             line["roofline"]["kernels_ms_in_flight"] = ktimes_in_flight
             line["roofline"]["kernels_ms_in_flight_note"] = (f"mean launch durations with {main_run.sp.in_flight} forwards in flight, HIP events on each "
@@ -1233,7 +1292,7 @@ def main():
         rest = {k: v for k, v in secondary.items() if k not in ("config3", "config4")}
         if rest:
             line["secondary"] = rest
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if full and world == 1 and not args.no_cpu_baseline and not stub:
             line["cpu_baseline"] = cpu_baseline(state, B, T, args.cpu_seconds)
             line["speedup_vs_cpu_baseline"] = round(line["value"] / line["cpu_baseline"]["value"], 1)
         # ---- every leg's self-checks folded into the top-level flag, and a compact summary as the LAST key of the line (the tail of the

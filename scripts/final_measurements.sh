@@ -27,8 +27,8 @@ prof ${R}_t7_bf16_big --precision bf16 --batch 65536 --frames 7 --no-secondary -
 timeout 150 bash scripts/profile_logmel.sh ${R}_logmel > $OUT/prof_${R}_logmel.log 2>&1; grep "rc=" $OUT/prof_${R}_logmel.log | tr '\n' ' '
 for t in "${R}_bf16 ${R}_bf16_b256" ${R} ${R}_fp32s ${R}_t7 ${R}_t7_fp32s ${R}_t7_fp32s_big ${R}_t7_bf16 ${R}_t7_bf16_big ${R}_logmel; do bash scripts/collect_profiles.sh $t > /dev/null 2>&1 || echo "collect $t failed"; done
 timeout 200 bash scripts/profile_overlap.sh ${R} > $OUT/overlap.log 2>&1; cp gpurun_out/overlap_${R}.txt profiles/${R}_inflight_overlap.txt 2>/dev/null
-( timeout 300 python bench.py 2>$OUT/bench.err | grep "^{" ) > $OUT/bench.json; wc -c $OUT/bench.json
-( SAVAD_BENCH_FORCE_DIST=1 timeout 150 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29641 bench.py --gpus 1 --no-cpu-baseline 2>/dev/null | grep "^{" ) > $OUT/bench_dist1.json; wc -c $OUT/bench_dist1.json
+( timeout 300 python bench.py --full 2>$OUT/bench.err | grep "^{" ) > $OUT/bench.json; wc -c $OUT/bench.json
+( SAVAD_BENCH_FORCE_DIST=1 timeout 150 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29641 bench.py --gpus 1 --full --no-cpu-baseline 2>/dev/null | grep "^{" ) > $OUT/bench_dist1.json; wc -c $OUT/bench_dist1.json
 find gpurun_out -name "*.csv" -size +1M -delete
 echo "measurements done after $(( $(date +%s) - T0 )) s"
 n=0

@@ -4,7 +4,8 @@ from oracle import oracle
 sys.path.insert(0,'tests')
 from test_trained_weights import recording
 from voice_activity_detection_amd import SelfAttentiveVAD
-z=np.load('tests/golden/trained.npz'); state={k[6:]:z[k] for k in z.files if k.startswith('state/')}
+from tests.golden.data_files import load_trained
+z=load_trained(); state={k[6:]:v for k,v in z.items() if k.startswith('state/')}
 m=SelfAttentiveVAD(80,3,128,0.5); m.load_state_dict({k:torch.from_numpy(v) for k,v in state.items()}); m=m.cuda().eval()
 _,feat,_=recording(0)
 x=np.ascontiguousarray(feat[:6400].reshape(8,800,80))

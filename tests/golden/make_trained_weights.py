@@ -11,7 +11,7 @@ on the labelled recordings of the reference's test data (tests/data/JamakeSpeech
 only, the reference model ranks the clip's frames upside down, AUC 0.28; all kept as fixtures under tests/golden/data/), in the shape the reference trains and predicts in: windows of 7 frames at offsets -19 .. 19 step 9
 (vad/predictor.py:180-224), every frame of a window scored against its own label (the boosted model's per-frame NLL), log-mel
 features from oracle/logmel.py (the restated librosa defaults: librosa itself is absent), labels from VoiceActivity.to_labels(100).
-Stored (tests/golden/trained.npz): ONLY the resulting state_dict (fp32) and, for the HELD-OUT clip (WhenTheWeatherIsFine, never
+Stored (tests/golden/trained.npz + trained_layer<i>.npz, data_files.save_trained): ONLY the resulting state_dict (fp32) and, for the HELD-OUT clip (WhenTheWeatherIsFine, never
 trained on), the reference model's own outputs -- log-probs of its first 1000 windows and the predictor-level boosted
 probabilities computed the reference's way -- plus the AUC the reference arithmetic reaches on each of the three files."""
 from __future__ import annotations
@@ -31,8 +31,9 @@ from oracle import logmel, oracle  # noqa: E402
 from voice_activity_detection_amd.data_models import VoiceActivity  # noqa: E402
 from voice_activity_detection_amd.features import load_wav_mono16k  # noqa: E402
 from voice_activity_detection_amd.metrics import roc_auc  # noqa: E402
+from tests.golden.data_files import data_root, save_trained  # noqa: E402
 
-DATA = Path(__file__).resolve().parent / "data"
+DATA = data_root()
 OUT = Path(__file__).resolve().parent / "trained.npz"
 OFFSETS = oracle.window_offsets(19, 9)  # [-19, -10, -1, 0, 1, 10, 19]
 HALF = 19
@@ -110,8 +111,8 @@ def main():
             aucs.append(tail)
     out["auc_ref"] = np.array(aucs)   # sample_93, sample_95, the whole clip, the clip's untrained tail
     assert aucs[2] > 0.8, "the clip must be well separated for the AUC-parity tests to mean something"
-    np.savez_compressed(OUT, **out)
-    print("wrote", OUT, OUT.stat().st_size, "bytes")
+    for f in save_trained(out, OUT.parent):   # one archive per encoder layer + one for the rest: each under 1 MiB
+        print("wrote", f, f.stat().st_size, "bytes")
 
 
 if __name__ == "__main__":

@@ -230,7 +230,7 @@ def test_bench_runs_with_two_gloo_ranks(tmp_path):
     repo = Path(__file__).resolve().parent.parent
     for attempt in range(3):   # the driver's own command line (a fixed --master-port): a port picked here can be gone by the time it is bound
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-               "--master-port", str(_free_port()), str(repo / "bench.py"), "--gpus", "2", "--backend", "gloo", "--stub-forward",
+               "--master-port", str(_free_port()), str(repo / "bench.py"), "--gpus", "2", "--full", "--backend", "gloo", "--stub-forward",
                "--steps", "3", "--warmup", "1", "--min-seconds", "0.01", "--batch", "2", "--frames", "40", "--config3-shape", "3,24"]
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
         if res.returncode == 0 or "EADDRINUSE" not in res.stderr and "address already in use" not in res.stderr.lower():
@@ -259,7 +259,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
 
     repo = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, str(repo / "bench.py"), "--gpus", "2", "--backend", "gloo", "--stub-forward", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, str(repo / "bench.py"), "--gpus", "2", "--full", "--backend", "gloo", "--stub-forward", "--steps", "3", "--warmup", "1",
            "--min-seconds", "0.01", "--batch", "2", "--frames", "40", "--config3-shape", "3,24"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path), env=env)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -327,7 +327,7 @@ def test_bench_self_checks_fail_the_run(tmp_path):
 
     repo = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, str(repo / "bench.py"), "--gpus", "1", "--backend", "gloo", "--stub-forward", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, str(repo / "bench.py"), "--gpus", "1", "--full", "--backend", "gloo", "--stub-forward", "--steps", "3", "--warmup", "1",
            "--min-seconds", "0.01", "--batch", "2", "--frames", "40"]
     ok = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path), env=env)
     assert ok.returncode == 0, ok.stderr[-2000:]
@@ -342,6 +342,31 @@ def test_bench_self_checks_fail_the_run(tmp_path):
     assert d["finite"] is False and d["summary"]["all_flags_true"] is False and d["summary"]["false_flags"] == ["secondary.planted.finite"]
 
 
+def test_bench_plain_run_times_exactly_k_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times ONE block of exactly --steps steps, measures nothing else, and --dump-outputs writes what the
+    last timed step returned: the same bits from run to run (seeded inputs), equal to the stand-in forward of the seeded input."""
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    repo = Path(__file__).resolve().parent.parent
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for i in range(2):
+        cmd = [sys.executable, str(repo / "bench.py"), "--gpus", "1", "--backend", "gloo", "--stub-forward", "--steps", "7", "--warmup", "2",
+               "--batch", "3", "--frames", "40", "--dump-outputs", str(tmp_path / f"out{i}")]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path), env=env)
+        assert res.returncode == 0, res.stderr[-2000:]
+        d = _bench_line(res)
+        assert d["steps"] == 7 and d["timing"]["blocks"] == 1 and d["finite"] is True and list(d)[-1] == "summary"
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d) and d["ms_per_step"] > 0
+        assert not {"secondary", "cpu_baseline", "value_one_forward", "clocks", "repeated_blocks"} & (set(d) | set(d["timing"]))
+        dumps.append(np.load(tmp_path / f"out{i}" / "log_probs.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (1, 3, 40, 2) and np.array_equal(dumps[0], dumps[1])
+    x = torch.from_numpy(np.random.default_rng(0).uniform(-13.8, 4.2, (3, 40, 80)).astype(np.float32))
+    assert np.array_equal(dumps[0][0], torch.log_softmax(x[..., :2], dim=-1).numpy())
+
+
 def test_bench_dry_run_at_the_real_rank_count(tmp_path):
     """`python bench.py --gpus 8 --backend gloo --stub-forward`, plain (the file launches its own eight ranks): the control flow of the
     driver's 8-GPU scaling run at the rank count it will use -- tuning agreed by eight ranks, both gather modes, the config3 leg with a
@@ -353,7 +378,7 @@ def test_bench_dry_run_at_the_real_rank_count(tmp_path):
     repo = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
-    cmd = [sys.executable, str(repo / "bench.py"), "--gpus", "8", "--backend", "gloo", "--stub-forward", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, str(repo / "bench.py"), "--gpus", "8", "--full", "--backend", "gloo", "--stub-forward", "--steps", "2", "--warmup", "1",
            "--min-seconds", "0.01", "--batch", "2", "--frames", "24", "--config3-shape", "3,16"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(tmp_path), env=env)
     assert res.returncode == 0, res.stderr[-3000:]

@@ -1566,7 +1566,9 @@ def test_auc_parity_on_the_reference_labelled_files(torch_cuda, model, state1234
     from voice_activity_detection_amd.features import load_wav_mono16k, log_mel
     from voice_activity_detection_amd.metrics import roc_auc
 
-    root = Path(__file__).resolve().parent / "golden" / "data"
+    from tests.golden.data_files import data_root
+
+    root = data_root()
     write_reference_checkpoint(tmp_path / "model.checkpoint", state1234)
     jam = root / "JamakeSpeechSample"
     out = evaluate_vad_from_scratch(jam / "vad-train-sample.jsonl", tmp_path / "model.checkpoint", tmp_path / "eval.jsonl", echo=lambda s: None)

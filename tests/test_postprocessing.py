@@ -57,10 +57,10 @@ def test_timecode_format_and_json_roundtrip(tmp_path):
     assert list(data) == ["version", "duration", "activities", "probs_sample_rate", "probs"] and data["version"] == "v0.3"
     assert data["duration"] == "00:00:10.213" and data["activities"] == [{"start": "00:00:00.525", "end": "00:00:01.225"}]
     assert VoiceActivity.load(tmp_path / "va.json") == va
-    # the reference's own sample file parses (format example of JSON v0.3: tests/data/WhenTheWeatherIsFine/voice_activity.json)
-    ref_file = Path("/root/reference/tests/data/WhenTheWeatherIsFine/voice_activity.json")
-    if ref_file.exists():
-        assert len(VoiceActivity.load(ref_file).activities) == 5
+    # the reference's own sample file parses (format example of JSON v0.3: its tests/data/WhenTheWeatherIsFine/voice_activity.json,
+    # a byte-identical copy under tests/golden/data)
+    ref_file = Path(__file__).resolve().parent / "golden" / "data" / "WhenTheWeatherIsFine" / "voice_activity.json"
+    assert len(VoiceActivity.load(ref_file).activities) == 5
 
 
 def _audio(case, seconds):

@@ -10,8 +10,9 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from tests.golden.data_files import data_root, load_trained
+
 HERE = Path(__file__).resolve().parent
-DATA = HERE / "golden" / "data"
 OFFSETS = np.array([-19, -10, -1, 0, 1, 10, 19])
 FILES = [("JamakeSpeechSample/data/sample_93/audio_93.wav", "JamakeSpeechSample/data/sample_93/voice_activity_93.json"),
          ("JamakeSpeechSample/data/sample_95/audio_95.wav", "JamakeSpeechSample/data/sample_95/voice_activity_95.json"),
@@ -20,9 +21,9 @@ FILES = [("JamakeSpeechSample/data/sample_93/audio_93.wav", "JamakeSpeechSample/
 
 @pytest.fixture(scope="module")
 def trained():
-    with np.load(HERE / "golden" / "trained.npz") as z:
-        state = {k[len("state/"):]: z[k] for k in z.files if k.startswith("state/")}
-        return state, z["clip_logp"], z["clip_probs"], z["auc_ref"]
+    z = load_trained()
+    state = {k[len("state/"):]: v for k, v in z.items() if k.startswith("state/")}
+    return state, z["clip_logp"], z["clip_probs"], z["auc_ref"]
 
 
 def recording(i):
@@ -30,8 +31,8 @@ def recording(i):
     from voice_activity_detection_amd.data_models import VoiceActivity
     from voice_activity_detection_amd.features import load_wav_mono16k
 
-    audio = load_wav_mono16k(DATA / FILES[i][0])
-    labels = VoiceActivity.load(DATA / FILES[i][1]).to_labels(100)
+    audio = load_wav_mono16k(data_root() / FILES[i][0])
+    labels = VoiceActivity.load(data_root() / FILES[i][1]).to_labels(100)
     feat = logmel.log_mel(audio)
     n = min(len(labels), len(feat))
     return audio, feat[:n].astype(np.float32), labels[:n]
