@@ -245,6 +245,42 @@ int savad_logmel_set_algorithm(int algorithm);
 int savad_logmel_table_floats(int which);
 int savad_logmel_tables_host(float* t1, float* t3, float* tm);
 
+/* Feature front-end for every transform a reference config can name (vad/acoustics/transforms/transform_factory.py:13-59)
+ * and the temporal differences of vad/acoustics/feature_extractor.py:135-145 (stack_differences false), at 16 kHz.
+ * hop / win in samples (int(hop_ms / 1000 * 16000), int(window_ms / 1000 * 16000)); output [n_frames][n_features] fp32:
+ *   SAVAD_FE_LOGMEL / _MEL : librosa 0.8 melspectrogram (stft center=True, reflect padding, periodic Hann(win) centred in
+ *                            n_fft, power 2, Slaney filterbank fmin 0 fmax 8 kHz) -> log(x + 1e-6) / as it is; n_mels features
+ *   SAVAD_FE_MFCC          : power_to_db(mel, ref 1, amin 1e-10, top_db 80 -- the maximum over the whole call) -> DCT-II ortho,
+ *                            first n_mfcc rows; n_frames = 1 + (n_samples + 2 (n_fft / 2) - n_fft) / hop for these
+ *                            three (1 + n_samples / hop for an even n_fft)
+ *   SAVAD_FE_SPECTROGRAM   : |torch.stft(center=False, periodic Hamming(win) centred in n_fft, onesided)|; n_fft / 2 + 1
+ *                            features, n_frames = 1 + (n_samples - n_fft) / hop
+ *   deltas = 1             : [x, delta(x, 9, order 1), delta(x, 9, order 2)] along the features (3x), at least 9 frames.
+ * Limits: win <= n_fft <= 2048, 1 <= n_mels <= 256, 1 <= n_mfcc <= n_mels, n_samples >= n_fft / 2 + 1 (centred) or n_fft
+ * (spectrogram).  The tables of a config are built on the host and uploaded to the current device on first use, which
+ * synchronises: call savad_frontend_prepare before a graph capture; savad_frontend itself then only launches kernels.
+ * savad_frontend_tables_host (which = 0 DFT [rows][kr], 1 mel [n_mels][n_fft/2+1], 2 DCT [n_mfcc][n_mels], 3 Savitzky-Golay
+ * [order 2][position 9][tap 9]; savad_frontend_table_floats floats each) copies them to HOST memory for the CPU tests.
+ * The DFT table's columns are frame samples k0 .. k0 + kr - 1, k0 = ((n_fft - win) / 2) rounded down to a multiple of 4,
+ * kr = that window's end - k0 rounded up to 8; its rows: re(bin 0), re(bin n_fft/2) (zero for an odd n_fft), then re / im of
+ * bins 1 .. ceil(n_fft/2) - 1, padded with zero rows to a multiple of 128.  audio: device, any alignment; workspace
+ * (savad_frontend_workspace_bytes) and features: device, 16-byte aligned. */
+#define SAVAD_FE_SPECTROGRAM 0
+#define SAVAD_FE_MEL 1
+#define SAVAD_FE_LOGMEL 2
+#define SAVAD_FE_MFCC 3
+typedef struct {
+    int transform; /* SAVAD_FE_* */
+    int n_fft, hop, win, n_mels, n_mfcc, deltas;
+} savad_frontend_config;
+int savad_frontend_shape(const savad_frontend_config* config, long n_samples, int* n_frames, int* n_features);
+int savad_frontend_workspace_bytes(const savad_frontend_config* config, long n_samples, size_t* bytes);
+int savad_frontend_prepare(const savad_frontend_config* config);
+int savad_frontend(const savad_frontend_config* config, const float* audio, long n_samples, float* workspace, float* features,
+                   void* stream);
+int savad_frontend_table_floats(const savad_frontend_config* config, int which);
+int savad_frontend_tables_host(const savad_frontend_config* config, int which, float* out);
+
 /* Post-processing of the predict path (next-row 3 of the scope table); HOST pointers.
  * savad_trim_voice_activity  : vad/postprocessing/trim.py:4-66 (valley fill, hill flatten, hang before/over; the
  *                              hang pass only runs when hang_before > 0, as in the reference)

@@ -37,6 +37,9 @@ def main(argv=None) -> int:
     p.add_argument("--graph", action="store_true",
                    help="replay clip-sized chunks (<= 120 s) as a captured HIP graph: pays when many chunks have the same length "
                         "(--split-max-seconds), same results.")
+    p.add_argument("--extended-front-end", action="store_true",
+                   help="build any feature_extractor config of the checkpoint (spectrogram, mel, log-mel, mfcc at any geometry within "
+                        "the limits, temporal differences); without it only the shipped log-mel is accepted")
     e = sub.add_parser("evaluate", help="frame metrics over a labelled data list (vad/evaluate.py:20-29)")
     e.add_argument("eval_path", type=Path)
     e.add_argument("checkpoint_path", type=Path)
@@ -47,18 +50,21 @@ def main(argv=None) -> int:
     e.add_argument("--limit", type=int, default=None)
     e.add_argument("--random-seed", type=int, default=0)
     e.add_argument("--device", default="cuda")
+    e.add_argument("--extended-front-end", action="store_true",
+                   help="build any feature_extractor config of the checkpoint (spectrogram, mel, log-mel, mfcc at any geometry within "
+                        "the limits, temporal differences); without it only the shipped log-mel is accepted")
     args = ap.parse_args(argv)
 
     if args.command == "evaluate":
         from .evaluate import evaluate_vad_from_scratch
 
         evaluate_vad_from_scratch(args.eval_path, args.checkpoint_path, args.output_path, args.data_dir, args.threshold,
-                                  args.shuffle, args.limit, args.random_seed, args.device)
+                                  args.shuffle, args.limit, args.random_seed, args.device, extended_front_end=args.extended_front_end)
         return 0
 
     from .predictor import VADFromScratchPredictor, VADPredictParameters
 
-    predictor = VADFromScratchPredictor.from_checkpoint(args.checkpoint_path, args.device)
+    predictor = VADFromScratchPredictor.from_checkpoint(args.checkpoint_path, args.device, extended_front_end=args.extended_front_end)
     predictor.model.precision, predictor.model.batch_invariant, predictor.graph = args.precision, args.batch_invariant, args.graph
     voice_activity = predictor.predict_from_path(
         args.audio_path,

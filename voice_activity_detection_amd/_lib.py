@@ -20,6 +20,11 @@ class savad_config(ctypes.Structure):
     _fields_ = [("feature_size", c_int32), ("num_layers", c_int32), ("d_model", c_int32)]
 
 
+class savad_frontend_config(ctypes.Structure):
+    _fields_ = [("transform", c_int32), ("n_fft", c_int32), ("hop", c_int32), ("win", c_int32), ("n_mels", c_int32),
+                ("n_mfcc", c_int32), ("deltas", c_int32)]
+
+
 # every symbol include/savad.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "savad_create": (c_int, [POINTER(savad_config), POINTER(c_void_p)]),
@@ -59,6 +64,12 @@ SYMBOLS = {
     "savad_logmel_set_algorithm": (c_int, [c_int]),
     "savad_logmel_table_floats": (c_int, [c_int]),
     "savad_logmel_tables_host": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "savad_frontend_shape": (c_int, [POINTER(savad_frontend_config), c_long, POINTER(c_int), POINTER(c_int)]),
+    "savad_frontend_workspace_bytes": (c_int, [POINTER(savad_frontend_config), c_long, POINTER(c_size_t)]),
+    "savad_frontend_prepare": (c_int, [POINTER(savad_frontend_config)]),
+    "savad_frontend": (c_int, [POINTER(savad_frontend_config), c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
+    "savad_frontend_table_floats": (c_int, [POINTER(savad_frontend_config), c_int]),
+    "savad_frontend_tables_host": (c_int, [POINTER(savad_frontend_config), c_int, c_void_p]),
     "savad_trim_voice_activity": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "savad_frames_to_samples": (c_long, [c_void_p, c_int, c_int, c_double, c_double, c_void_p]),
     "savad_samples_to_segments": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int]),

@@ -9,6 +9,7 @@
 #include "savad_generic.h"
 #include <type_traits>
 #include "savad_logmel.h"
+#include "savad_frontend.h"
 #include "savad_post.h"
 
 #include <math.h>
@@ -1542,8 +1543,7 @@ SAVAD_EXPORT int savad_window_offsets(int half, int jump, int32_t* offsets) {
 SAVAD_EXPORT int savad_gather_windows(const float* feature, int N, int F, int half, int jump, int first, int count,
                                       float* windows, int64_t* positions, void* stream) {
     if (count == 0) return SAVAD_OK;
-    if (!feature || !windows || N <= 0 || F <= 0 || F % 4 || first < 0 || count < 0)
-        return fail(SAVAD_E_INVALID, "bad argument (F must be a multiple of 4)");
+    if (!feature || !windows || N <= 0 || F <= 0 || first < 0 || count < 0) return fail(SAVAD_E_INVALID, "bad argument");
     WindowOffsets wo;
     int32_t off[256];
     if (savad_window_offsets(half, jump, nullptr) > 64) return fail(SAVAD_E_UNSUPPORTED, "window longer than 64 frames");
@@ -1551,10 +1551,14 @@ SAVAD_EXPORT int savad_gather_windows(const float* feature, int N, int F, int ha
     for (int i = 0; i < wo.w; ++i) wo.off[i] = off[i];
     if ((long)half + first + count - 1 + off[wo.w - 1] >= N || half + first + off[0] < 0)
         return fail(SAVAD_E_INVALID, "window [%d,%d) reaches outside the %d feature frames", first, first + count, N);
-    const size_t total = (size_t)count * wo.w * (F / 4);
+    const size_t total = (size_t)count * wo.w * (F % 4 ? F : F / 4);
     const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(gather_windows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feature, F, half, first,
-                       count, wo, windows, positions);
+    if (F % 4)
+        hipLaunchKernelGGL(gather_windows_scalar_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feature, F, half, first,
+                           count, wo, windows, positions);
+    else
+        hipLaunchKernelGGL(gather_windows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feature, F, half, first,
+                           count, wo, windows, positions);
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }
@@ -1647,8 +1651,7 @@ SAVAD_EXPORT int savad_predict_probabilities(savad_handle m, const float* featur
     if (rc) return rc;
     if (workspace_bytes < p.total) return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
     hipStream_t st = (hipStream_t)stream;
-    const int F = m->cfg.feature_size, W = p.W;
-    if (F % 4) return fail(SAVAD_E_INVALID, "F must be a multiple of 4");
+    const int F = m->cfg.feature_size, W = p.W;  // (F % 4 != 0: never windowed -- m->FP != F -- the windows go through savad_gather_windows)
     WindowOffsets wo;
     int32_t off[64];
     wo.w = savad_window_offsets(half, jump, off);
@@ -2064,6 +2067,213 @@ SAVAD_EXPORT int savad_logmel(const float* audio, int n_samples, float* workspac
     const int tiles = (n_frames + 31) / 32;
     hipLaunchKernelGGL(mel::logmel_kernel<4>, dim3(tiles), dim3(256), 0, st, workspace, n_frames, g_mel.d_dft, g_mel.d_mel,
                        features);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+// ---- feature front-end for any transform config (savad_frontend.h) ----------------------------------------------
+namespace {
+
+struct FeTables {
+    float* d_dft = nullptr;  // stft_kernel's A fragments
+    float* d_mel = nullptr;  // [n_mels][nb]
+    float* d_dct = nullptr;  // [n_mfcc][n_mels]
+    float* d_sg = nullptr;   // [2][9][9]
+};
+std::mutex g_fe_mutex;
+std::map<std::vector<int>, FeTables> g_fe_tables;  // (device, transform, n_fft, win, n_mels, n_mfcc) -> tables; process lifetime
+
+int fe_check(const savad_frontend_config* c) {
+    if (!c) return fail(SAVAD_E_INVALID, "null config");
+    if (c->transform < SAVAD_FE_SPECTROGRAM || c->transform > SAVAD_FE_MFCC) return fail(SAVAD_E_UNSUPPORTED, "unsupported transform %d", c->transform);
+    if (c->win < 1 || c->hop < 1) return fail(SAVAD_E_INVALID, "window %d and hop %d must be >= 1", c->win, c->hop);
+    if (c->n_fft < c->win || c->n_fft < 2 || c->n_fft > 2048) return fail(SAVAD_E_INVALID, "n_fft %d outside the limit win (%d) <= n_fft <= 2048", c->n_fft, c->win);
+    if (c->transform != SAVAD_FE_SPECTROGRAM && (c->n_mels < 1 || c->n_mels > 256))
+        return fail(SAVAD_E_INVALID, "n_mels %d outside the limit 1 <= n_mels <= 256", c->n_mels);
+    if (c->transform == SAVAD_FE_MFCC && (c->n_mfcc < 1 || c->n_mfcc > c->n_mels))
+        return fail(SAVAD_E_INVALID, "n_mfcc %d outside the limit 1 <= n_mfcc <= n_mels (%d)", c->n_mfcc, c->n_mels);
+    if (c->deltas != 0 && c->deltas != 1) return fail(SAVAD_E_INVALID, "deltas must be 0 or 1");
+    return SAVAD_OK;
+}
+
+// frames and features of a call; errors name the limit that was not met
+int fe_shape(const savad_frontend_config* c, long n, int* frames, int* feats) {
+    int rc;
+    if ((rc = fe_check(c))) return rc;
+    const bool centred = c->transform != SAVAD_FE_SPECTROGRAM;
+    const long need = centred ? c->n_fft / 2 + 1 : c->n_fft;
+    if (n < need || n > 2000000000L)
+        return fail(SAVAD_E_INVALID, "%ld samples: the limit is n_samples >= %ld (%s)", n, need, centred ? "n_fft / 2 + 1, reflect padding" : "n_fft, center=False");
+    // frames of the n_fft-sample window over the signal (padded by n_fft / 2 per side when centred): 1 + n / hop for an even n_fft
+    const long N = 1 + (n + (centred ? 2 * (c->n_fft / 2) : 0) - c->n_fft) / c->hop;
+    if (c->deltas && N < savad::fe::DELTA_W)
+        return fail(SAVAD_E_INVALID, "%ld frames: temporal differences need at least %d (librosa.feature.delta, width 9)", N, savad::fe::DELTA_W);
+    const int F = c->transform == SAVAD_FE_SPECTROGRAM ? c->n_fft / 2 + 1 : c->transform == SAVAD_FE_MFCC ? c->n_mfcc : c->n_mels;
+    *frames = (int)N;
+    *feats = c->deltas ? 3 * F : F;
+    return SAVAD_OK;
+}
+
+// workspace (floats, each piece 256-byte aligned): MFCC maximum | padded / copied signal | power [N][nbs] | dB mel [N][n_mels]
+struct FeWs {
+    size_t sig, spec, db, total;
+};
+FeWs fe_workspace(const savad_frontend_config* c, long n, int N) {
+    const savad::fe::Geo g = savad::fe::geometry(c->n_fft, c->hop, c->win);
+    auto up = [](size_t v) { return (v + 63) / 64 * 64; };
+    FeWs w;
+    w.sig = 64;
+    w.spec = w.sig + up((size_t)n + c->n_fft + savad::fe::SLACK);
+    w.db = w.spec + (c->transform == SAVAD_FE_SPECTROGRAM ? 0 : up((size_t)N * g.nbs));
+    w.total = w.db + (c->transform == SAVAD_FE_MFCC ? up((size_t)N * c->n_mels) : 0);
+    return w;
+}
+
+std::vector<float> fe_host_table(const savad_frontend_config* c, int which) {
+    namespace fe = savad::fe;
+    const fe::Geo g = fe::geometry(c->n_fft, c->hop, c->win);
+    if (which == 0) return fe::dft_plain(g, c->transform == SAVAD_FE_SPECTROGRAM);
+    if (which == 1) return c->transform == SAVAD_FE_SPECTROGRAM ? std::vector<float>() : fe::mel_filterbank(c->n_fft, c->n_mels);
+    if (which == 2) return c->transform == SAVAD_FE_MFCC ? fe::dct_ortho(c->n_mels, c->n_mfcc) : std::vector<float>();
+    return fe::savgol_rows();
+}
+
+// tables of this config on the current device, built (host, float64) and uploaded on first use: synchronous, so never
+// inside a graph capture -- savad_frontend_prepare is the explicit step before one
+int fe_tables(const savad_frontend_config* c, FeTables* out) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const bool sp = c->transform == SAVAD_FE_SPECTROGRAM, mf = c->transform == SAVAD_FE_MFCC;
+    const std::vector<int> key{dev, sp ? 0 : 1, c->n_fft, c->win, sp ? 0 : c->n_mels, mf ? c->n_mfcc : 0};
+    std::lock_guard<std::mutex> lock(g_fe_mutex);
+    auto it = g_fe_tables.find(key);
+    if (it != g_fe_tables.end()) {
+        *out = it->second;
+        return SAVAD_OK;
+    }
+    const savad::fe::Geo g = savad::fe::geometry(c->n_fft, c->hop, c->win);
+    const std::vector<float> dft = savad::fe::dft_fragments(g, fe_host_table(c, 0)), mel = fe_host_table(c, 1), dct = fe_host_table(c, 2),
+                             sg = fe_host_table(c, 3);
+    auto up = [](size_t v) { return (v + 63) / 64 * 64; };
+    float* base = nullptr;
+    HIP_TRY(hipMalloc(&base, (up(dft.size()) + up(mel.size()) + up(dct.size()) + up(sg.size())) * sizeof(float)));
+    size_t off = 0;
+    FeTables t;
+    auto put = [&](const std::vector<float>& v, float** d) -> hipError_t {
+        *d = base + off;
+        off += up(v.size());
+        return v.empty() ? hipSuccess : hipMemcpy(*d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice);
+    };
+    HIP_TRY(put(dft, &t.d_dft));
+    HIP_TRY(put(mel, &t.d_mel));
+    HIP_TRY(put(dct, &t.d_dct));
+    HIP_TRY(put(sg, &t.d_sg));
+    g_fe_tables[key] = t;
+    *out = t;
+    return SAVAD_OK;
+}
+
+int grid_for(long work) { return (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096); }
+
+}  // namespace
+
+SAVAD_EXPORT int savad_frontend_shape(const savad_frontend_config* config, long n_samples, int* n_frames, int* n_features) {
+    if (!n_frames || !n_features) return fail(SAVAD_E_INVALID, "null argument");
+    return fe_shape(config, n_samples, n_frames, n_features);
+}
+SAVAD_EXPORT int savad_frontend_workspace_bytes(const savad_frontend_config* config, long n_samples, size_t* bytes) {
+    int N, F, rc;
+    if (!bytes) return fail(SAVAD_E_INVALID, "null argument");
+    if ((rc = fe_shape(config, n_samples, &N, &F))) return rc;
+    *bytes = fe_workspace(config, n_samples, N).total * sizeof(float);
+    return SAVAD_OK;
+}
+SAVAD_EXPORT int savad_frontend_prepare(const savad_frontend_config* config) {
+    int rc;
+    FeTables t;
+    if ((rc = fe_check(config))) return rc;
+    return fe_tables(config, &t);
+}
+SAVAD_EXPORT int savad_frontend_table_floats(const savad_frontend_config* config, int which) {
+    int rc;
+    if ((rc = fe_check(config))) return rc;
+    if (which < 0 || which > 3) return fail(SAVAD_E_INVALID, "table %d (0 = DFT, 1 = mel, 2 = DCT, 3 = Savitzky-Golay)", which);
+    return (int)fe_host_table(config, which).size();
+}
+SAVAD_EXPORT int savad_frontend_tables_host(const savad_frontend_config* config, int which, float* out) {
+    int rc;
+    if ((rc = fe_check(config))) return rc;
+    if (!out || which < 0 || which > 3) return fail(SAVAD_E_INVALID, "table %d / null output", which);
+    const std::vector<float> t = fe_host_table(config, which);
+    if (!t.empty()) memcpy(out, t.data(), t.size() * sizeof(float));
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_frontend(const savad_frontend_config* config, const float* audio, long n_samples, float* workspace, float* features,
+                                void* stream) {
+    using namespace savad::fe;
+    int N, Fo, rc;
+    if ((rc = fe_shape(config, n_samples, &N, &Fo))) return rc;
+    if (!audio || !workspace || !features) return fail(SAVAD_E_INVALID, "null argument");
+    if (((uintptr_t)workspace | (uintptr_t)features) & 15) return fail(SAVAD_E_INVALID, "workspace and features must be 16-byte aligned");
+    FeTables tb;
+    if ((rc = fe_tables(config, &tb))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const savad_frontend_config& c = *config;
+    const Geo g = geometry(c.n_fft, c.hop, c.win);
+    const FeWs w = fe_workspace(config, n_samples, N);
+    const bool sp = c.transform == SAVAD_FE_SPECTROGRAM;
+    const int F = c.deltas ? Fo / 3 : Fo;
+    int* gmax = reinterpret_cast<int*>(workspace);
+    float* sig = workspace + w.sig;
+    const float* src;
+    if (!sp) {  // centred: the reflect-padded signal, always materialised (aligned whatever the audio pointer)
+        const long total = n_samples + c.n_fft + SLACK;
+        hipLaunchKernelGGL(fe_reflect_pad_kernel, dim3(grid_for(total)), dim3(256), 0, st, audio, n_samples, c.n_fft / 2, total, sig);
+        src = sig;
+    } else {  // straight from the audio when every 16-byte read lands inside it; otherwise from an aligned copy (same values)
+        const bool aligned = ((uintptr_t)audio & 15) == 0 || (g.hop & 3);
+        if (aligned && (long)g.hop * (N - 1) + g.k0 + g.kr <= n_samples) {
+            src = audio;
+        } else {
+            const long total = n_samples + SLACK;
+            hipLaunchKernelGGL(fe_copy_kernel, dim3(grid_for(total)), dim3(256), 0, st, audio, n_samples, total, sig);
+            src = sig;
+        }
+    }
+    StftArgs a;
+    a.src = src + g.k0;
+    a.tab = tb.d_dft;
+    a.out = sp ? features : workspace + w.spec;
+    a.gmax = c.transform == SAVAD_FE_MFCC ? gmax : nullptr;
+    a.n_frames = N;
+    a.hop = g.hop;
+    a.kg = g.kg;
+    a.rblocks = g.rblocks;
+    a.nb = g.nb;
+    a.n_fft = g.n_fft;
+    a.ld = sp ? Fo : g.nbs;
+    a.magnitude = sp;
+    const int wgs = (N + 32 * FT - 1) / (32 * FT);
+    if (g.hop % 4 == 0)
+        hipLaunchKernelGGL(stft_kernel<true>, dim3(wgs), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(stft_kernel<false>, dim3(wgs), dim3(256), 0, st, a);
+    if (!sp) {
+        const bool mf = c.transform == SAVAD_FE_MFCC;
+        FeGemm m{workspace + w.spec, (long)g.nbs, tb.d_mel, mf ? workspace + w.db : features, mf ? (long)c.n_mels : (long)Fo, N, c.n_mels, g.nb, gmax};
+        const dim3 gm((c.n_mels + GT - 1) / GT, (N + GT - 1) / GT);
+        if (c.transform == SAVAD_FE_MEL)
+            hipLaunchKernelGGL((fe_gemm_kernel<EPI_NONE, false>), gm, dim3(256), 0, st, m);
+        else if (c.transform == SAVAD_FE_LOGMEL)
+            hipLaunchKernelGGL((fe_gemm_kernel<EPI_LOG, false>), gm, dim3(256), 0, st, m);
+        else {
+            hipLaunchKernelGGL((fe_gemm_kernel<EPI_DB, false>), gm, dim3(256), 0, st, m);
+            FeGemm d{workspace + w.db, (long)c.n_mels, tb.d_dct, features, (long)Fo, N, c.n_mfcc, c.n_mels, gmax};
+            hipLaunchKernelGGL((fe_gemm_kernel<EPI_NONE, true>), dim3((c.n_mfcc + GT - 1) / GT, (N + GT - 1) / GT), dim3(256), 0, st, d);
+        }
+    }
+    if (c.deltas) hipLaunchKernelGGL(delta_kernel, dim3(grid_for((long)N * F)), dim3(256), 0, st, features, N, F, (long)Fo, tb.d_sg);
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }

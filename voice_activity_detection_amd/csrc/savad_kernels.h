@@ -1627,6 +1627,21 @@ __global__ void gather_windows_kernel(const float* __restrict__ feature, int F, 
     }
 }
 
+// the same for a feature size that is not a multiple of 4 (the MFCC / spectrogram front-ends: 13, 39, 161 ...): one float per thread
+__global__ void gather_windows_scalar_kernel(const float* __restrict__ feature, int F, int half, int first, int count,
+                                             WindowOffsets wo, float* __restrict__ windows, int64_t* __restrict__ positions) {
+    const size_t total = (size_t)count * wo.w * F;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % F);
+        const size_t iw = i / F;
+        const int wi = (int)(iw % wo.w);
+        const size_t item = iw / wo.w;
+        const size_t pos = (size_t)half + first + item + wo.off[wi];
+        windows[i] = feature[pos * F + c];
+        if (c == 0 && positions) positions[iw] = (int64_t)pos;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // a14: boosted prediction (vad/predictor.py:238-258, :95): scatter, then softmax[...,1] and mean.
 // ---------------------------------------------------------------------------------------------

@@ -68,18 +68,20 @@ def _report(title: str, m: dict) -> str:
 def evaluate_vad_from_scratch(eval_path: Path, checkpoint_path: Optional[Path] = None, output_path: Optional[Path] = None,
                               data_dir: Optional[Path] = None, threshold: float = 0.5, shuffle: bool = False,
                               limit: Optional[int] = None, random_seed: int = 0, device: str = "cuda",
-                              probabilities_fn: Optional[Callable[[Path], np.ndarray]] = None, echo=print) -> dict:
+                              probabilities_fn: Optional[Callable[[Path], np.ndarray]] = None, echo=print,
+                              extended_front_end: bool = False) -> dict:
     """Arguments as vad/evaluate.py:20-29.  `probabilities_fn(audio_path) -> [N, W]` replaces checkpoint + GPU
-    predictor (host-logic tests); otherwise the audio goes WAV -> log-mel -> predict_probabilities on `device`."""
+    predictor (host-logic tests); otherwise the audio goes WAV -> the checkpoint's front-end -> predict_probabilities on
+    `device` (`extended_front_end`: VADFromScratchPredictor.from_checkpoint)."""
     eval_path = Path(eval_path)
     if probabilities_fn is None:
-        from .features import load_wav_mono16k, log_mel
+        from .features import load_wav_mono16k
         from .predictor import VADFromScratchPredictor
 
-        predictor = VADFromScratchPredictor.from_checkpoint(checkpoint_path, device)
+        predictor = VADFromScratchPredictor.from_checkpoint(checkpoint_path, device, extended_front_end=extended_front_end)
 
         def probabilities_fn(path):
-            return predictor.predict_probabilities(log_mel(load_wav_mono16k(path), predictor.device))
+            return predictor.predict_probabilities(predictor.features(load_wav_mono16k(path)))
 
     data_dir = eval_path.parent if data_dir is None else Path(data_dir)
     pairs = load_data_list(eval_path)

@@ -1,10 +1,13 @@
-"""Log-mel front-end on the GPU: mirror of the reference's ``FeatureExtractor.extract_with_postprocessing``
-for its only shipped transform (log-mel, n_fft 512, hop 10 ms, window 25 ms, 80 mels @16 kHz:
-``vad/acoustics/feature_extractor.py:71-80``, ``vad/acoustics/transforms/log_mel_spectrogram.py:19-32``)."""
+"""Feature front-end on the GPU: mirror of the reference's ``FeatureExtractor.extract_with_postprocessing``
+(``vad/acoustics/feature_extractor.py:71-80``): ``log_mel`` for its shipped transform (log-mel, n_fft 512, hop 10 ms, window
+25 ms, 80 mels @16 kHz: ``vad/acoustics/transforms/log_mel_spectrogram.py:19-32``), ``FrontEnd`` for every other transform
+configuration a checkpoint can name."""
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 from pathlib import Path
+from typing import Optional
 
 import numpy as np
 import torch
@@ -234,3 +237,133 @@ def span_samples(n_samples: int, frame_first: int, frame_count: int):
     first, count = ctypes.c_long(), ctypes.c_long()
     _lib.check(lib.savad_logmel_span_samples(int(n_samples), int(frame_first), int(frame_count), ctypes.byref(first), ctypes.byref(count)))
     return first.value, count.value
+
+
+_FE_TRANSFORMS = {"spectrogram": 0, "mel": 1, "log-mel": 2, "mfcc": 3}   # include/savad.h: SAVAD_FE_*
+
+
+@dataclass(frozen=True)
+class FrontEnd:
+    """A checkpoint's ``feature_extractor`` (vad/acoustics/transforms/transform_factory.py:13-59,
+    vad/acoustics/feature_extractor.py:122-147): one of the four transforms at any geometry, optionally followed by the temporal
+    differences [x, delta, delta-delta] along the features.  ``extract`` runs savad_frontend (include/savad.h: semantics and
+    limits); the shipped configuration (log-mel, n_fft 512, hop 10 ms, window 25 ms, 80 mels, no differences) runs ``log_mel``,
+    so its features keep their bits."""
+    transform: str = "log-mel"
+    n_fft: int = 512
+    hop_ms: float = 10
+    window_ms: float = 25
+    n_mels: Optional[int] = 80
+    n_mfcc: Optional[int] = None
+    deltas: bool = False
+
+    def __post_init__(self):
+        if self.transform not in _FE_TRANSFORMS:
+            raise NotImplementedError(f"unsupported transform {self.transform!r} (known: {', '.join(_FE_TRANSFORMS)})")
+        if self.transform != "spectrogram" and self.n_mels is None:
+            raise NotImplementedError(f"unsupported transform {self.transform!r} without n_mels")
+        if self.transform == "mfcc" and self.n_mfcc is None:
+            raise NotImplementedError("unsupported transform 'mfcc' without n_mfcc")
+        hop, win = self.hop, self.win
+        if hop < 1 or win < 1 or not (win <= self.n_fft <= 2048):
+            raise ValueError(f"front-end geometry outside the limits: hop {hop} >= 1, window {win} <= n_fft {self.n_fft} <= 2048")
+        if self.transform != "spectrogram" and not 1 <= self.n_mels <= 256:
+            raise ValueError(f"n_mels {self.n_mels} outside the limit 1 <= n_mels <= 256")
+        if self.transform == "mfcc" and not 1 <= self.n_mfcc <= self.n_mels:
+            raise ValueError(f"n_mfcc {self.n_mfcc} outside the limit 1 <= n_mfcc <= n_mels ({self.n_mels})")
+
+    @classmethod
+    def from_config(cls, fe) -> "FrontEnd":
+        """A checkpoint config's ``feature_extractor`` node (dict or attribute object).  Refuses, with "unsupported" in the
+        message, what the device path does not build: stacked differences (a [T, F, 3] tensor the self-attention model's
+        nn.Linear(feature_size, d_model) cannot take: vad/models/model_factory.py:42-48) and a silence remover."""
+        def get(c, name, default=None):
+            if isinstance(c, dict):
+                return c.get(name, default)
+            return getattr(c, name, default)
+
+        tr = get(fe, "transform")
+        if tr is None:
+            raise NotImplementedError("unsupported feature_extractor: no transform")
+        if get(fe, "silence_remover"):
+            raise NotImplementedError("unsupported feature_extractor: silence_remover (vad/acoustics/feature_extractor.py:115-116) is not built")
+        deltas = bool(get(fe, "temporal_differences", False))
+        if deltas and get(fe, "stack_differences", False):
+            raise NotImplementedError("unsupported feature_extractor: stack_differences yields [T, F, 3], which the self-attention "
+                                      "model cannot consume (vad/models/model_factory.py:42-48)")
+        name = get(tr, "name")
+        n_mels = get(tr, "n_mels")
+        n_mfcc = get(tr, "n_mfcc")
+        return cls(str(name), int(get(tr, "n_fft")), get(tr, "hop_ms"), get(tr, "window_ms"),
+                   None if n_mels is None else int(n_mels), None if n_mfcc is None else int(n_mfcc), deltas)
+
+    @property
+    def hop(self) -> int:
+        return int(self.hop_ms / 1000 * SAMPLE_RATE)
+
+    @property
+    def win(self) -> int:
+        return int(self.window_ms / 1000 * SAMPLE_RATE)
+
+    @property
+    def is_shipped(self) -> bool:
+        """the reference's shipped configuration: the tuned savad_logmel path"""
+        return (self.transform, self.n_fft, self.hop, self.win, self.n_mels, self.deltas) == ("log-mel", 512, _HOP, 400, 80, False)
+
+    @property
+    def base_size(self) -> int:
+        return {"spectrogram": self.n_fft // 2 + 1, "mfcc": self.n_mfcc}.get(self.transform, self.n_mels)
+
+    @property
+    def feature_size(self) -> int:
+        return 3 * self.base_size if self.deltas else self.base_size
+
+    def config(self):
+        return _lib.savad_frontend_config(_FE_TRANSFORMS[self.transform], self.n_fft, self.hop, self.win, self.n_mels or 0,
+                                          self.n_mfcc or 0, int(self.deltas))
+
+    def frames(self, n_samples: int) -> int:
+        """rows of extract() for n_samples samples (raises outside the limits)"""
+        N, F = ctypes.c_int(), ctypes.c_int()
+        cfg = self.config()
+        _lib.check(_lib.load().savad_frontend_shape(ctypes.byref(cfg), int(n_samples), ctypes.byref(N), ctypes.byref(F)))
+        return N.value
+
+    def prepare(self, device) -> None:
+        """build and upload this config's tables on `device` (synchronises: the step before a graph capture)"""
+        dev = torch.device(device)
+        with torch.cuda.device(dev):
+            cfg = self.config()
+            _lib.check(_lib.load().savad_frontend_prepare(ctypes.byref(cfg)))
+
+    def extract(self, audio, device="cuda", generic: bool = False) -> torch.Tensor:
+        """audio: 1-D float32 samples @16 kHz (numpy or tensor; int16 PCM is uploaded as it is and converted on the device) ->
+        device tensor [frames(n), feature_size] float32.  `generic=True` runs the shipped configuration through savad_frontend as
+        well (the cross-check against savad_logmel)."""
+        if self.is_shipped and not generic:
+            return log_mel(audio, device)
+        lib = _lib.load()
+        dev = device if isinstance(device, torch.device) else torch.device(device)
+        if getattr(audio, "dtype", None) in (torch.int16, np.dtype("int16")):
+            audio = pcm16_to_f32(torch.as_tensor(audio).to(dev).contiguous())
+        y = audio if (isinstance(audio, torch.Tensor) and audio.dtype == torch.float32 and audio.device == dev and audio.dim() == 1
+                      and audio.is_contiguous()) else torch.as_tensor(audio, dtype=torch.float32).to(dev).contiguous()
+        if y.dim() != 1 or y.numel() < 1:
+            raise ValueError("audio must be a non-empty 1-D array")
+        if y.device.type != "cuda":
+            raise _lib.SavadError("the feature front-end runs only on a HIP device (no CPU fallback)")
+        with torch.cuda.device(y.device):
+            cfg = self.config()
+            n = y.numel()
+            N, F, ws = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+            _lib.check(lib.savad_frontend_shape(ctypes.byref(cfg), n, ctypes.byref(N), ctypes.byref(F)))
+            _lib.check(lib.savad_frontend_workspace_bytes(ctypes.byref(cfg), n, ctypes.byref(ws)))
+            buf = torch.empty(ws.value // 4, dtype=torch.float32, device=y.device)
+            out = torch.empty((N.value, F.value), dtype=torch.float32, device=y.device)
+            _lib.check(lib.savad_frontend(ctypes.byref(cfg), ctypes.c_void_p(y.data_ptr()), n, ctypes.c_void_p(buf.data_ptr()),
+                                          ctypes.c_void_p(out.data_ptr()),
+                                          ctypes.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)))
+        return out
+
+
+SHIPPED_FRONT_END = FrontEnd()

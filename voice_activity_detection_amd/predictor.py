@@ -67,12 +67,18 @@ class VADFromScratchPredictor:
     hop_ms, window_ms = 10, 25  # the reference's only transform config (tests/configs/vad/train_config.yaml:21-22)
 
     def __init__(self, model: SelfAttentiveVAD, device: torch.device, context: ContextResolution = ContextResolution(),
-                 chunk_size: int = 16384, graph: bool = False, graph_max_seconds: float = 120.0, graph_cache: int = 8):
+                 chunk_size: int = 16384, graph: bool = False, graph_max_seconds: float = 120.0, graph_cache: int = 8,
+                 front_end=None):
         """`graph=True` (not in the reference's signature): clip-sized inputs -- up to `graph_max_seconds` of audio -- run as a
         replayed HIP graph of the whole chain log-mel -> window gather -> forward -> boost, captured on first use per (length, model
         knobs) and re-captured when the weights change; at most `graph_cache` graphs are kept (least recently used goes).  For a 10 s
         clip the four launches take less time than the Python and the library calls around them: the replay halves the time per clip,
-        same bits (predict_audio_device)."""
+        same bits (predict_audio_device).
+        `front_end` (features.FrontEnd; None = the shipped log-mel): the transform predict / predict_audio_device / evaluate run
+        on the audio.  Only the shipped one has the host-upload path (predict_audio_host)."""
+        from .features import SHIPPED_FRONT_END
+
+        self.front_end = SHIPPED_FRONT_END if front_end is None else front_end
         self.graph, self.graph_max_seconds, self.graph_cache = bool(graph), float(graph_max_seconds), int(graph_cache)
         self._graphs: "OrderedDict[tuple, dict]" = OrderedDict()
         self.graph_stats = {"captures": 0, "replays": 0, "eager": 0}
@@ -134,12 +140,16 @@ class VADFromScratchPredictor:
         return full_unpickle()
 
     @classmethod
-    def from_checkpoint(cls, checkpoint_path, device, trust_checkpoint: bool = False):
+    def from_checkpoint(cls, checkpoint_path, device, trust_checkpoint: bool = False, extended_front_end: bool = False):
         """vad/predictor.py:264-280: a training checkpoint holds {"config": ..., "state_dict": ...} plus what
         ModelCheckpointer adds (epoch, global_step, monitor_metric, a `metrics` dict of numpy scalars, optimizer /
         scheduler / grad-scaler state: vad/training/checkpointers/model_checkpointer.py:97-110); the model size, the
         feature transform and the window geometry come from the config, the weights load strictly.  Unlike the
-        reference's plain torch.load, the file is first read with weights_only=True (see _load_checkpoint)."""
+        reference's plain torch.load, the file is first read with weights_only=True (see _load_checkpoint).
+        `extended_front_end=True` builds every feature_extractor config features.FrontEnd takes (the four transforms at any
+        geometry within its limits, temporal differences); the default refuses all but the shipped one.  The shipped
+        features are pinned by goldens and trained-weights AUC, the others by a restatement of librosa 0.8.0: opting in
+        acknowledges that."""
         ckpt = cls._load_checkpoint(checkpoint_path, trust_checkpoint)
         cfg = ckpt["config"]
 
@@ -162,6 +172,17 @@ class VADFromScratchPredictor:
         # (tests/configs/vad/train_config.yaml:18-28).  Anything else would load cleanly and then produce wrong features
         # or timings, so it is refused here rather than failing late with a shape error.
         fe = get(cfg, "feature_extractor")
+        if extended_front_end:
+            from .features import FrontEnd
+
+            front = FrontEnd.from_config(fe)
+            model = SelfAttentiveVAD(front.feature_size, get(sa, "num_layers"), get(sa, "d_model"), get(sa, "dropout"))
+            model.load_state_dict(ckpt["state_dict"])
+            ctx = ContextResolution(get(cfg, "context_resolution", "context_window_half_frames"),
+                                    get(cfg, "context_resolution", "context_window_jump_frames"))
+            predictor = cls(model.to(device).eval(), device, ctx, front_end=front)
+            predictor.hop_ms, predictor.window_ms = front.hop_ms, front.window_ms  # vad/predictor.py:103-104
+            return predictor
         tr = get(fe, "transform")
         want = {"name": "log-mel", "n_fft": 512, "hop_ms": 10, "window_ms": 25, "n_mels": 80}
         got = {k: get(tr, k) for k in want}
@@ -189,8 +210,8 @@ class VADFromScratchPredictor:
 
     def predict(self, audio: np.ndarray, parameters: VADPredictParameters, features_fn=None) -> VoiceActivity:
         """vad/predictor.py:77-157.  audio: float32 mono @16 kHz.  features_fn(chunk_audio) -> [N, F] overrides
-        the GPU log-mel front-end (used by the parity tests to feed the reference's feature matrix)."""
-        from .features import SAMPLE_RATE, log_mel
+        the GPU front-end (used by the parity tests to feed the reference's feature matrix)."""
+        from .features import SAMPLE_RATE
 
         audio = np.asarray(audio, dtype=np.float32)
         duration_s = len(audio) / SAMPLE_RATE
@@ -252,6 +273,20 @@ class VADFromScratchPredictor:
         self.model.eval()
         return self.model.predict_windows(feat, self.context_window_half_frames, self.context_window_jump_frames, self.chunk_size)
 
+    def features(self, audio) -> torch.Tensor:
+        """audio -> the [N, F] feature matrix of self.front_end on the predictor's device"""
+        from .features import log_mel
+
+        if self.front_end.is_shipped:
+            return log_mel(audio, self.device)
+        return self.front_end.extract(audio, self.device)
+
+    def _require_shipped_front_end(self, what: str):
+        if not self.front_end.is_shipped:
+            raise NotImplementedError(f"{what} runs the shipped log-mel front-end only (its spans follow the 160-sample hop, and "
+                                      f"MFCC's clamp and the temporal differences are not local): {self.front_end} is not; use "
+                                      "predict_audio_device")
+
     @torch.no_grad()
     def predict_audio_device(self, audio):
         """audio: 1-D float32 mono @16 kHz (numpy or tensor) -> (probs [N, W], mean [N]) on the device, N = 1 + len // 160: the GPU
@@ -259,19 +294,20 @@ class VADFromScratchPredictor:
         (vad/predictor.py:159-262) -- what `predict` runs per chunk.  With `graph=True` a clip-sized input replays a captured HIP
         graph (same kernels, same bits); the returned tensors then belong to the graph and are overwritten by the next call with
         the same length and knobs: copy them if they must outlive it."""
-        from .features import SAMPLE_RATE, log_mel
+        from .features import SAMPLE_RATE
 
         if self.device.type != "cuda":
             raise _lib.SavadError("the MI355X predictor needs a HIP device (no CPU fallback)")
         n = int(audio.shape[0]) if hasattr(audio, "shape") and len(audio.shape) == 1 else -1
         if not self.graph or n < 1 or n > self.graph_max_seconds * SAMPLE_RATE or self.model.training:
             self.graph_stats["eager"] += 1
-            return self.predict_probabilities_device(log_mel(audio, self.device))
+            return self.predict_probabilities_device(self.features(audio))
         model = self.model
         dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
         with torch.cuda.device(dev):
             model._prepare_call(dev)   # weights pushed, knobs set: the walk over the parameters' versions costs ~8 us
-            key = (n, dev.index, model._pushed_knobs, self.context_window_half_frames, self.context_window_jump_frames, self.chunk_size)
+            key = (n, dev.index, model._pushed_knobs, self.context_window_half_frames, self.context_window_jump_frames, self.chunk_size,
+                   self.front_end)
             entry = self._graphs.get(key)
             if entry is not None and entry["weights"] is not model._synced_versions:
                 # the weights were pushed again since the capture: the library re-folds / re-packs them inside its NEXT call, which a
@@ -320,6 +356,7 @@ class VADFromScratchPredictor:
 
         if self.device.type != "cuda":
             raise _lib.SavadError("the MI355X predictor needs a HIP device (no CPU fallback)")
+        self._require_shipped_front_end("predict_audio_host")
         src = StreamingPredictor._host_source(audio)
         n = int(src.shape[0])
         N = 1 + n // 160
@@ -369,10 +406,13 @@ class VADFromScratchPredictor:
         from .features import log_mel
 
         static_audio = torch.zeros(n, dtype=torch.float32, device=dev)
+        front = self.front_end
+        if not front.is_shipped:
+            front.prepare(dev)   # its tables reach the device before the capture (the capture may only launch kernels)
 
         def chain():
-            return self.model.predict_windows(log_mel(static_audio, dev), self.context_window_half_frames,
-                                              self.context_window_jump_frames, self.chunk_size)
+            feat = log_mel(static_audio, dev) if front.is_shipped else front.extract(static_audio, dev)
+            return self.model.predict_windows(feat, self.context_window_half_frames, self.context_window_jump_frames, self.chunk_size)
 
         # eager runs first, on a side stream like the capture itself: positional-encoding table, packed weights and the cached
         # workspace reach their final sizes, so that the captured call launches nothing but its own kernels
@@ -433,7 +473,14 @@ class StreamingPredictor:
     With torch.distributed initialised, windows are sharded contiguously over the ranks and the
     log-probs are exchanged with ONE all_gather (voice_activity_detection_amd.distributed)."""
 
-    def __init__(self, model: SelfAttentiveVAD, device, T: int = 800, hop: int = 400, max_batch: int = 256, in_flight: int = 2):
+    def __init__(self, model: SelfAttentiveVAD, device, T: int = 800, hop: int = 400, max_batch: int = 256, in_flight: int = 2,
+                 front_end=None):
+        # front_end (features.FrontEnd): the audio paths (audio_span_logp, predict_audio_device, predict_audio_host) cut the signal
+        # at the shipped log-mel's 160-sample hop and compute features per span: they refuse any other front-end; predict_device
+        # takes features of any front-end
+        from .features import SHIPPED_FRONT_END
+
+        self.front_end = SHIPPED_FRONT_END if front_end is None else front_end
         self.model, self.device, self.T, self.hop, self.max_batch = model, torch.device(device), int(T), int(hop), int(max_batch)
         # the window batches are independent: `in_flight` of them run concurrently (PipelinedVAD: own stream / handle / workspace
         # each, same bits); 1 = one after the other on the caller's stream.
@@ -525,6 +572,7 @@ class StreamingPredictor:
         slice of the samples is uploaded (when `audio` is a host array), only its frames' log-mel is computed"""
         from .features import log_mel_span
 
+        self._require_shipped_front_end("audio_span_logp")
         n = int(audio.shape[0])
         W, lo, hi, f0, f1, first, count = self.audio_shard_plan(n, self.T, self.hop, rank, world)
         if hi <= lo:
@@ -557,6 +605,7 @@ class StreamingPredictor:
 
         from .distributed import all_gather_rows
 
+        self._require_shipped_front_end("predict_audio_device")
         lib = _lib.load()
         n = int(audio.shape[0])
         N = 1 + n // 160
@@ -594,6 +643,7 @@ class StreamingPredictor:
         probabilities [N] on the device."""
         from .features import log_mel_span, pcm16_to_f32, span_samples
 
+        self._require_shipped_front_end("predict_audio_host")
         lib = _lib.load()
         src = self._host_source(audio)
         n = int(src.shape[0])
@@ -664,6 +714,11 @@ class StreamingPredictor:
             probs = torch.empty((N,), dtype=torch.float32, device=dev)
             _lib.check(lib.savad_overlap_merge(ctypes.c_void_p(logp.data_ptr()), W, N, T, hop, ctypes.c_void_p(probs.data_ptr()), stream))
         return probs
+
+    def _require_shipped_front_end(self, what: str):
+        if not self.front_end.is_shipped:
+            raise NotImplementedError(f"StreamingPredictor.{what} runs the shipped log-mel front-end only (spans at its 160-sample hop, "
+                                      f"features per span): {self.front_end} is not; extract the features whole and call predict_device")
 
     def predict(self, feature) -> np.ndarray:
         return self.predict_device(feature).cpu().numpy()
