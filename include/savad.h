@@ -281,6 +281,61 @@ int savad_frontend(const savad_frontend_config* config, const float* audio, long
 int savad_frontend_table_floats(const savad_frontend_config* config, int which);
 int savad_frontend_tables_host(const savad_frontend_config* config, int which, float* out);
 
+/* Audio ingest on the device: what AudioData.load does before the first feature (vad/data_models/audio_data.py:18-34) for a
+ * recording that is not 16 kHz mono -- the channel average (:26) and librosa.resample(audio, sr, 16000,
+ * res_type="kaiser_fast") (:27-30) = resampy 0.2.x's band-limited interpolation + librosa's fix_length.
+ *
+ * Resampler.  One lane per output sample walks the taps in resampy's order with resampy's arithmetic (weight and product in
+ * float64, the accumulator rounded to float32 after every tap, no contraction), and the time register takes the values of
+ * resampy's repeated float64 addition (from a table of (first output, time, exact step) segments, one per binade of the
+ * register; k * increment is NOT that value).  An output sample therefore has the bits of resampy's loop.
+ *   savad_resample_length       ceil(n_samples * 16000 / rate) (in float64, as librosa computes it); outputs at or past
+ *                               int(n_samples * 16000 / rate) are zero (fix_length).  n_samples for a 16 kHz source.
+ *   savad_resample_set_window   the filter: resampy's "kaiser_fast" half window, SAVAD_RESAMPLE_WINDOW float64 values (HOST) =
+ *                               kaiser(2 n + 1, 8.555504641634386)[n:] * (0.85 * sinc(0.85 * linspace(0, 16, n + 1))), n = 8192.
+ *                               It is an INPUT, once per process: the bits of numpy's exp differ between CPUs (its AVX-512
+ *                               path against libm), so a table built inside the library could not equal the one numpy /
+ *                               resampy hold on every host.  A second call must pass the same bits.
+ *   savad_resample_prepare      builds a rate's tables (the window scaled by the ratio when downsampling, its first
+ *                               differences, the time segments) and uploads them to the current device: it allocates and
+ *                               synchronises, so call it before a graph capture.  The compute entry points do this on
+ *                               first use of a (device, rate); afterwards they only launch on `stream`.
+ *   savad_resample              the whole signal: audio [n_samples] float32 (device) -> out [savad_resample_length] float32.
+ *   savad_resample_span         outputs [out_first, out_first + out_count) from a slice that starts at input sample
+ *                               audio_first and holds audio_count samples: the same bits as the rows of the whole call.  The
+ *                               slice must hold the samples savad_resample_span_samples names (it may start up to 3 samples
+ *                               later: *first is rounded down to a multiple of 4 so that a slice cut there keeps the 16-byte
+ *                               alignment of float data).
+ *   savad_resample_span_samples HOST arithmetic: [*first, *first + *count) contains every input sample those outputs read
+ *                               (a wing has at most 8193 / int(min(1, ratio) * 512) taps), clipped to the signal; the lowest
+ *                               sample read lies within 1 + 3 (one tap, alignment) of *first, the highest within 1 of the
+ *                               end, unless clipped.  A span of nothing but fix_length zeros reads nothing: count 0.
+ *   savad_resample_table_host / _segments_host   HOST copies for the CPU tests: the rate's window and differences
+ *                               (SAVAD_RESAMPLE_WINDOW each; delta may be NULL), and up to `max` time segments -- returns their
+ *                               number; *covered = the number of outputs the segments cover (2^45 input samples).
+ *   savad_resample_set_table_mode   experiments: 0 (default) = a workgroup keeps the table in LDS, 1 = reads it through the cache.
+ * Limits: 1000 <= rate <= 100000 Hz (a block's input span must fit the 160 KiB of LDS next to the 128 KiB table; outside:
+ * SAVAD_E_UNSUPPORTED), sample counts are long, 16000 Hz is a plain copy (no window needed).
+ *
+ * savad_ingest_downmix: interleaved [n_frames][channels] samples (device) -> float32 mono with the bits of the host loader:
+ * sample / 32768 for SAVAD_PCM_INT16, then numpy's float32 .mean(axis=1) = the left-to-right float32 sum divided by
+ * float32(channels).  int16: channels <= 256 (every partial sum is exact); float32: channels <= 7 (numpy sums a row of 8 or
+ * more elements in another order: refused with SAVAD_E_UNSUPPORTED).  One channel is savad_pcm16_to_f32 / a copy. */
+#define SAVAD_RESAMPLE_WINDOW 8193
+#define SAVAD_PCM_INT16 0
+#define SAVAD_PCM_FLOAT32 1
+long savad_resample_length(long n_samples, int rate);
+int savad_resample_set_window(const double* half_window);
+int savad_resample_prepare(int rate);
+int savad_resample(const float* audio, long n_samples, int rate, float* out, void* stream);
+int savad_resample_span_samples(long n_samples, int rate, long out_first, long out_count, long* first, long* count);
+int savad_resample_span(const float* audio, long audio_first, long audio_count, long n_samples, int rate, long out_first,
+                        long out_count, float* out, void* stream);
+int savad_resample_table_host(int rate, double* window, double* delta);
+int savad_resample_segments_host(int rate, int max, long* first, double* time, double* step, long* covered);
+int savad_resample_set_table_mode(int mode);
+int savad_ingest_downmix(const void* raw, int dtype, int channels, long n_frames, float* mono, void* stream);
+
 /* Post-processing of the predict path (next-row 3 of the scope table); HOST pointers.
  * savad_trim_voice_activity  : vad/postprocessing/trim.py:4-66 (valley fill, hill flatten, hang before/over; the
  *                              hang pass only runs when hang_before > 0, as in the reference)

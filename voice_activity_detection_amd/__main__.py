@@ -40,6 +40,9 @@ def main(argv=None) -> int:
     p.add_argument("--extended-front-end", action="store_true",
                    help="build any feature_extractor config of the checkpoint (spectrogram, mel, log-mel, mfcc at any geometry within "
                         "the limits, temporal differences); without it only the shipped log-mel is accepted")
+    p.add_argument("--device-ingest", action="store_true",
+                   help="average the channels and resample to 16 kHz on the GPU (the file's samples are uploaded as stored) instead "
+                        "of on the host: pays for every recording that is not 16 kHz mono")
     e = sub.add_parser("evaluate", help="frame metrics over a labelled data list (vad/evaluate.py:20-29)")
     e.add_argument("eval_path", type=Path)
     e.add_argument("checkpoint_path", type=Path)
@@ -53,18 +56,23 @@ def main(argv=None) -> int:
     e.add_argument("--extended-front-end", action="store_true",
                    help="build any feature_extractor config of the checkpoint (spectrogram, mel, log-mel, mfcc at any geometry within "
                         "the limits, temporal differences); without it only the shipped log-mel is accepted")
+    e.add_argument("--device-ingest", action="store_true",
+                   help="average the channels and resample to 16 kHz on the GPU (the file's samples are uploaded as stored) instead "
+                        "of on the host: pays for every recording that is not 16 kHz mono")
     args = ap.parse_args(argv)
 
     if args.command == "evaluate":
         from .evaluate import evaluate_vad_from_scratch
 
         evaluate_vad_from_scratch(args.eval_path, args.checkpoint_path, args.output_path, args.data_dir, args.threshold,
-                                  args.shuffle, args.limit, args.random_seed, args.device, extended_front_end=args.extended_front_end)
+                                  args.shuffle, args.limit, args.random_seed, args.device, extended_front_end=args.extended_front_end,
+                                  device_ingest=args.device_ingest)
         return 0
 
     from .predictor import VADFromScratchPredictor, VADPredictParameters
 
-    predictor = VADFromScratchPredictor.from_checkpoint(args.checkpoint_path, args.device, extended_front_end=args.extended_front_end)
+    predictor = VADFromScratchPredictor.from_checkpoint(args.checkpoint_path, args.device, extended_front_end=args.extended_front_end,
+                                                        device_ingest=args.device_ingest)
     predictor.model.precision, predictor.model.batch_invariant, predictor.graph = args.precision, args.batch_invariant, args.graph
     voice_activity = predictor.predict_from_path(
         args.audio_path,

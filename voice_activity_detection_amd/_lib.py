@@ -70,6 +70,16 @@ SYMBOLS = {
     "savad_frontend": (c_int, [POINTER(savad_frontend_config), c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     "savad_frontend_table_floats": (c_int, [POINTER(savad_frontend_config), c_int]),
     "savad_frontend_tables_host": (c_int, [POINTER(savad_frontend_config), c_int, c_void_p]),
+    "savad_resample_length": (c_long, [c_long, c_int]),
+    "savad_resample_set_window": (c_int, [c_void_p]),
+    "savad_resample_prepare": (c_int, [c_int]),
+    "savad_resample": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p]),
+    "savad_resample_span_samples": (c_int, [c_long, c_int, c_long, c_long, POINTER(c_long), POINTER(c_long)]),
+    "savad_resample_span": (c_int, [c_void_p, c_long, c_long, c_long, c_int, c_long, c_long, c_void_p, c_void_p]),
+    "savad_resample_table_host": (c_int, [c_int, c_void_p, c_void_p]),
+    "savad_resample_segments_host": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_long)]),
+    "savad_resample_set_table_mode": (c_int, [c_int]),
+    "savad_ingest_downmix": (c_int, [c_void_p, c_int, c_int, c_long, c_void_p, c_void_p]),
     "savad_trim_voice_activity": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "savad_frames_to_samples": (c_long, [c_void_p, c_int, c_int, c_double, c_double, c_void_p]),
     "savad_samples_to_segments": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int]),

@@ -10,6 +10,7 @@
 #include <type_traits>
 #include "savad_logmel.h"
 #include "savad_frontend.h"
+#include "savad_ingest.h"
 #include "savad_post.h"
 
 #include <math.h>
@@ -2274,6 +2275,257 @@ SAVAD_EXPORT int savad_frontend(const savad_frontend_config* config, const float
         }
     }
     if (c.deltas) hipLaunchKernelGGL(delta_kernel, dim3(grid_for((long)N * F)), dim3(256), 0, st, features, N, F, (long)Fo, tb.d_sg);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+// ---- audio ingest: channel average and resampling to 16 kHz on the device (savad_ingest.h) ----------------------------------
+namespace {
+
+struct RsHost {   // per source rate, host side: the plan, the scaled table with its differences, the time segments
+    savad::ingest::Plan plan;
+    std::vector<double> win, delta;
+    std::vector<savad::ingest::Seg> segs;
+    long long k_end = 0;
+};
+struct RsDev {
+    double2* d_tab = nullptr;
+    savad::ingest::Seg* d_segs = nullptr;
+    int n_cu = 0;
+};
+std::mutex g_rs_mutex;
+std::vector<double> g_rs_window;            // the caller's "kaiser_fast" half window (savad_resample_set_window)
+std::map<int, RsHost> g_rs_host;            // rate -> host tables; process lifetime
+std::map<std::pair<int, int>, RsDev> g_rs_dev;   // (device, rate) -> uploaded tables; process lifetime
+int g_rs_table_mode = 0;                    // 0 = table in LDS, 1 = through the cache
+
+int rs_check_rate(int rate) {
+    if (rate < savad::ingest::RATE_MIN || rate > savad::ingest::RATE_MAX)
+        return fail(SAVAD_E_UNSUPPORTED, "source rate %d Hz outside the limit %d <= rate <= %d", rate, savad::ingest::RATE_MIN, savad::ingest::RATE_MAX);
+    return SAVAD_OK;
+}
+
+// plan and time segments need no table: the host-only helpers (length, span samples, segments) work without a window
+int rs_host(int rate, bool need_table, const RsHost** out) {
+    namespace in = savad::ingest;
+    int rc;
+    if ((rc = rs_check_rate(rate))) return rc;
+    std::lock_guard<std::mutex> lock(g_rs_mutex);
+    RsHost& h = g_rs_host[rate];
+    if (h.segs.empty()) {
+        h.plan = in::plan_for(rate);
+        h.segs = in::time_segments(h.plan.inc, &h.k_end);
+        if (h.segs.empty()) {
+            g_rs_host.erase(rate);
+            return fail(SAVAD_E_UNSUPPORTED, "source rate %d Hz: its time register needs more than %d segments", rate, in::MAX_SEGS);
+        }
+        if (in::lds_bytes(h.plan, true) > (size_t)in::LDS_BYTES_MAX) {
+            g_rs_host.erase(rate);
+            return fail(SAVAD_E_UNSUPPORTED, "source rate %d Hz: a block's input span does not fit the LDS next to the table", rate);
+        }
+    }
+    if (need_table && h.win.empty()) {
+        if (g_rs_window.empty()) return fail(SAVAD_E_STATE, "the kaiser_fast half window was never set (savad_resample_set_window)");
+        h.win = g_rs_window;
+        if (h.plan.ratio < 1.0)
+            for (double& v : h.win) v = v * h.plan.ratio;   // resampy: interp_win *= sample_ratio when downsampling
+        h.delta.assign(in::NWIN, 0.0);
+        for (int i = 0; i + 1 < in::NWIN; ++i) h.delta[i] = h.win[i + 1] - h.win[i];   // np.diff; delta[last] = 0
+    }
+    *out = &h;
+    return SAVAD_OK;
+}
+
+int rs_dev(int rate, const RsHost** host, RsDev* out) {
+    namespace in = savad::ingest;
+    int rc, dev = 0;
+    if ((rc = rs_host(rate, true, host))) return rc;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_rs_mutex);
+    auto it = g_rs_dev.find({dev, rate});
+    if (it != g_rs_dev.end()) {
+        *out = it->second;
+        return SAVAD_OK;
+    }
+    const RsHost& h = **host;
+    std::vector<double2> tab(in::NWIN);
+    for (int i = 0; i < in::NWIN; ++i) tab[i] = double2{h.win[i], h.delta[i]};
+    RsDev d;
+    HIP_TRY(hipDeviceGetAttribute(&d.n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    HIP_TRY(hipMalloc(&d.d_tab, tab.size() * sizeof(double2)));
+    HIP_TRY(hipMalloc(&d.d_segs, h.segs.size() * sizeof(in::Seg)));
+    HIP_TRY(hipMemcpy(d.d_tab, tab.data(), tab.size() * sizeof(double2), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.d_segs, h.segs.data(), h.segs.size() * sizeof(in::Seg), hipMemcpyHostToDevice));
+    if ((rc = allow_lds(in::resample_kernel<true>, (int)in::lds_bytes(h.plan, true)))) return rc;
+    if ((rc = allow_lds(in::resample_kernel<false>, (int)in::lds_bytes(h.plan, false)))) return rc;
+    g_rs_dev[{dev, rate}] = d;
+    *out = d;
+    return SAVAD_OK;
+}
+
+long rs_n_out(const savad::ingest::Plan& p, long n) { return (long)((double)n * p.ratio); }          // int(n * ratio)
+long rs_n_fix(const savad::ingest::Plan& p, long n) { return (long)ceil((double)n * p.ratio); }     // ceil(n * ratio)
+
+}  // namespace
+
+SAVAD_EXPORT long savad_resample_length(long n_samples, int rate) {
+    if (n_samples < 0) return fail(SAVAD_E_INVALID, "n_samples %ld", n_samples);
+    if (rate == savad::ingest::TARGET) return n_samples;
+    int rc;
+    if ((rc = rs_check_rate(rate))) return rc;
+    return rs_n_fix(savad::ingest::plan_for(rate), n_samples);
+}
+
+SAVAD_EXPORT int savad_resample_set_window(const double* half_window) {
+    if (!half_window) return fail(SAVAD_E_INVALID, "null window");
+    std::lock_guard<std::mutex> lock(g_rs_mutex);
+    if (!g_rs_window.empty()) {
+        if (memcmp(g_rs_window.data(), half_window, sizeof(double) * savad::ingest::NWIN) == 0) return SAVAD_OK;
+        return fail(SAVAD_E_STATE, "a different half window is already set (tables built from it may be on a device)");
+    }
+    g_rs_window.assign(half_window, half_window + savad::ingest::NWIN);
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_resample_prepare(int rate) {
+    if (rate == savad::ingest::TARGET) return SAVAD_OK;
+    const RsHost* h;
+    RsDev d;
+    return rs_dev(rate, &h, &d);
+}
+
+SAVAD_EXPORT int savad_resample_set_table_mode(int mode) {
+    if (mode < 0 || mode > 1) return fail(SAVAD_E_INVALID, "table mode %d (0 = LDS, 1 = through the cache)", mode);
+    g_rs_table_mode = mode;
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_resample_table_host(int rate, double* window, double* delta) {
+    const RsHost* h;
+    int rc;
+    if (!window) return fail(SAVAD_E_INVALID, "null output");
+    if ((rc = rs_host(rate, true, &h))) return rc;
+    memcpy(window, h->win.data(), sizeof(double) * savad::ingest::NWIN);
+    if (delta) memcpy(delta, h->delta.data(), sizeof(double) * savad::ingest::NWIN);
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_resample_segments_host(int rate, int max, long* first, double* time, double* step, long* covered) {
+    const RsHost* h;
+    int rc;
+    if ((rc = rs_host(rate, false, &h))) return rc;
+    const int n = (int)h->segs.size();
+    if (covered) *covered = (long)h->k_end;
+    if (max > 0 && (!first || !time || !step)) return fail(SAVAD_E_INVALID, "null output");
+    for (int i = 0; i < n && i < max; ++i) {
+        first[i] = (long)h->segs[i].k0;
+        time[i] = h->segs[i].t0;
+        step[i] = h->segs[i].s;
+    }
+    return n;
+}
+
+SAVAD_EXPORT int savad_resample_span_samples(long n_samples, int rate, long out_first, long out_count, long* first, long* count) {
+    if (!first || !count || n_samples < 0 || out_first < 0 || out_count < 0) return fail(SAVAD_E_INVALID, "bad argument");
+    if (rate == savad::ingest::TARGET) {
+        if (out_first + out_count > n_samples) return fail(SAVAD_E_INVALID, "output span [%ld, +%ld) of %ld", out_first, out_count, n_samples);
+        *first = out_first / 4 * 4;
+        *count = out_first + out_count - *first;
+        return SAVAD_OK;
+    }
+    const RsHost* h;
+    int rc;
+    if ((rc = rs_host(rate, false, &h))) return rc;
+    const long n_fix = rs_n_fix(h->plan, n_samples), n_out = rs_n_out(h->plan, n_samples);
+    if (out_first + out_count > n_fix) return fail(SAVAD_E_INVALID, "output span [%ld, +%ld) of %ld", out_first, out_count, n_fix);
+    if (n_out > h->k_end) return fail(SAVAD_E_UNSUPPORTED, "%ld samples: beyond the time-register table", n_samples);
+    const long o1 = out_first + out_count < n_out ? out_first + out_count : n_out;
+    if (o1 <= out_first) {   // nothing but fix_length's zeros (or an empty span): no input is read
+        *first = 0;
+        *count = 0;
+        return SAVAD_OK;
+    }
+    long long a, c;
+    savad::ingest::span_inputs(h->plan, h->segs, n_samples, out_first, o1, &a, &c);
+    *first = (long)a;
+    *count = (long)c;
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_resample_span(const float* audio, long audio_first, long audio_count, long n_samples, int rate, long out_first,
+                                     long out_count, float* out, void* stream) {
+    namespace in = savad::ingest;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_samples < 0 || audio_first < 0 || audio_count < 0 || audio_first + audio_count > n_samples || out_first < 0 || out_count < 0)
+        return fail(SAVAD_E_INVALID, "bad argument");
+    if (out_count == 0) return SAVAD_OK;
+    if (!out || (audio_count > 0 && !audio)) return fail(SAVAD_E_INVALID, "null pointer");
+    long need_first, need_count;
+    int rc;
+    if ((rc = savad_resample_span_samples(n_samples, rate, out_first, out_count, &need_first, &need_count))) return rc;
+    if (rate == in::TARGET) {   // a 16 kHz source is a plain copy
+        if (out_first < audio_first || out_first + out_count > audio_first + audio_count)
+            return fail(SAVAD_E_INVALID, "the slice [%ld, +%ld) does not hold samples [%ld, +%ld)", audio_first, audio_count, out_first, out_count);
+        HIP_TRY(hipMemcpyAsync(out, audio + (out_first - audio_first), sizeof(float) * (size_t)out_count, hipMemcpyDeviceToDevice, st));
+        return SAVAD_OK;
+    }
+    const RsHost* h;
+    if ((rc = rs_host(rate, false, &h))) return rc;
+    if (need_count > 0) {   // (the slice may start after the aligned *first, as long as it holds every sample that is read)
+        long lo = (long)in::time_at(h->segs, out_first) - h->plan.taps + 1;
+        if (lo < 0) lo = 0;
+        if (audio_first > lo || audio_first + audio_count < need_first + need_count)
+            return fail(SAVAD_E_INVALID, "the slice [%ld, +%ld) does not hold the samples outputs [%ld, +%ld) read: [%ld, +%ld) (savad_resample_span_samples)",
+                        audio_first, audio_count, out_first, out_count, need_first, need_count);
+    }
+    RsDev d;
+    if ((rc = rs_dev(rate, &h, &d))) return rc;
+    const bool in_lds = g_rs_table_mode == 0;
+    const long blocks = (out_count + in::BLOCK - 1) / in::BLOCK;
+    const long cap = in_lds ? d.n_cu : 2L * d.n_cu;   // resident workgroups: one per CU around the table, two without it
+    const int grid = (int)(blocks < cap ? blocks : cap);
+    const size_t lds = in::lds_bytes(h->plan, in_lds);
+    const long long n_out = rs_n_out(h->plan, n_samples);
+    if (in_lds)
+        hipLaunchKernelGGL(in::resample_kernel<true>, dim3(grid), dim3(in::BLOCK), lds, st, audio, (long long)audio_first, (long long)audio_count,
+                           (long long)n_samples, (long long)out_first, (long long)out_count, n_out, d.d_tab, d.d_segs, (int)h->segs.size(),
+                           h->plan.scale, h->plan.step, h->plan.taps, h->plan.span, out);
+    else
+        hipLaunchKernelGGL(in::resample_kernel<false>, dim3(grid), dim3(in::BLOCK), lds, st, audio, (long long)audio_first, (long long)audio_count,
+                           (long long)n_samples, (long long)out_first, (long long)out_count, n_out, d.d_tab, d.d_segs, (int)h->segs.size(),
+                           h->plan.scale, h->plan.step, h->plan.taps, h->plan.span, out);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_resample(const float* audio, long n_samples, int rate, float* out, void* stream) {
+    const long n = savad_resample_length(n_samples, rate);
+    if (n < 0) return (int)n;
+    return savad_resample_span(audio, 0, n_samples, n_samples, rate, 0, n, out, stream);
+}
+
+SAVAD_EXPORT int savad_ingest_downmix(const void* raw, int dtype, int channels, long n_frames, float* mono, void* stream) {
+    namespace in = savad::ingest;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype != SAVAD_PCM_INT16 && dtype != SAVAD_PCM_FLOAT32) return fail(SAVAD_E_INVALID, "dtype %d (0 = int16, 1 = float32)", dtype);
+    if (channels < 1 || n_frames < 0) return fail(SAVAD_E_INVALID, "channels %d, frames %ld", channels, n_frames);
+    if (dtype == SAVAD_PCM_INT16 && channels > 256)
+        return fail(SAVAD_E_UNSUPPORTED, "%d channels of int16: the limit is 256 (partial sums stay exact in float32)", channels);
+    if (dtype == SAVAD_PCM_FLOAT32 && channels > 7)
+        return fail(SAVAD_E_UNSUPPORTED, "%d channels of float32: the limit is 7 (numpy's mean sums rows of 8 or more in another order)", channels);
+    if (n_frames == 0) return SAVAD_OK;
+    if (!raw || !mono) return fail(SAVAD_E_INVALID, "null pointer");
+    if (((uintptr_t)raw & (dtype == SAVAD_PCM_INT16 ? 1 : 3)) || ((uintptr_t)mono & 3)) return fail(SAVAD_E_INVALID, "misaligned pointer");
+    if (channels == 1 && dtype == SAVAD_PCM_INT16 && ((uintptr_t)mono & 15) == 0) return savad_pcm16_to_f32((const short*)raw, n_frames, mono, stream);
+    if (channels == 1 && dtype == SAVAD_PCM_FLOAT32) {
+        if (raw != (const void*)mono) HIP_TRY(hipMemcpyAsync(mono, raw, sizeof(float) * (size_t)n_frames, hipMemcpyDeviceToDevice, st));
+        return SAVAD_OK;
+    }
+    const int grid = grid_for(n_frames);
+    if (dtype == SAVAD_PCM_INT16)
+        hipLaunchKernelGGL(in::downmix_kernel<short>, dim3(grid), dim3(256), 0, st, (const short*)raw, channels, (long long)n_frames, mono);
+    else
+        hipLaunchKernelGGL(in::downmix_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)raw, channels, (long long)n_frames, mono);
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }

@@ -69,18 +69,21 @@ def evaluate_vad_from_scratch(eval_path: Path, checkpoint_path: Optional[Path] =
                               data_dir: Optional[Path] = None, threshold: float = 0.5, shuffle: bool = False,
                               limit: Optional[int] = None, random_seed: int = 0, device: str = "cuda",
                               probabilities_fn: Optional[Callable[[Path], np.ndarray]] = None, echo=print,
-                              extended_front_end: bool = False) -> dict:
+                              extended_front_end: bool = False, device_ingest: bool = False) -> dict:
     """Arguments as vad/evaluate.py:20-29.  `probabilities_fn(audio_path) -> [N, W]` replaces checkpoint + GPU
     predictor (host-logic tests); otherwise the audio goes WAV -> the checkpoint's front-end -> predict_probabilities on
-    `device` (`extended_front_end`: VADFromScratchPredictor.from_checkpoint)."""
+    `device` (`extended_front_end`: VADFromScratchPredictor.from_checkpoint).  `device_ingest`: a file's samples are uploaded as
+    stored, averaged over the channels and resampled to 16 kHz on the GPU (features.load_audio_device) instead of on the host."""
     eval_path = Path(eval_path)
     if probabilities_fn is None:
-        from .features import load_wav_mono16k
+        from .features import load_audio_device, load_wav_mono16k
         from .predictor import VADFromScratchPredictor
 
         predictor = VADFromScratchPredictor.from_checkpoint(checkpoint_path, device, extended_front_end=extended_front_end)
 
         def probabilities_fn(path):
+            if device_ingest:
+                return predictor.predict_probabilities(predictor.features(load_audio_device(path, predictor.device)))
             return predictor.predict_probabilities(predictor.features(load_wav_mono16k(path)))
 
     data_dir = eval_path.parent if data_dir is None else Path(data_dir)

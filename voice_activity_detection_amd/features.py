@@ -134,16 +134,15 @@ def _pcm_to_float(raw: bytes, width: int, big_endian: bool = False, unsigned8: b
     raise ValueError(f"unsupported PCM sample width {width}")
 
 
-def load_wav_mono16k(path) -> np.ndarray:
-    """Audio file -> float32 mono @16 kHz in [-1, 1): the reference's AudioData.load (vad/data_models/audio_data.py:
-    18-34) with the stdlib instead of soundfile: ``.pcm`` = headerless 16-bit mono @16 kHz (:21-24); WAV with integer PCM of
-    8 / 16 / 24 / 32 bits or IEEE float 32 / 64 (plain or WAVE_FORMAT_EXTENSIBLE); AIFF / AIFF-C (uncompressed) and Sun AU (linear PCM)
-    through the stdlib readers; any channel count (averaged, :26) and any rate (resampled, :27-30).  Compressed containers (FLAC,
-    OGG, MP3 ...) need a decoder this image does not have: convert them first."""
+def read_audio(path):
+    """Audio file -> (samples, rate, channels): the decode half of load_wav_mono16k.  `samples` is the file's interleaved
+    sample stream, 1-D: int16 as stored for a 16-bit source (what the device ingest uploads: 2 bytes per sample), float32 in
+    [-1, 1) for every other format (converted as soundfile does).  A trailing partial frame is dropped.  Formats: see
+    load_wav_mono16k."""
     path = Path(path)
     suffix = path.suffix.lower()
     if suffix == ".pcm":
-        return (np.fromfile(path, dtype=np.int16).astype(np.float32) / 32768.0).astype(np.float32)
+        return np.fromfile(path, dtype=np.int16), SAMPLE_RATE, 1
     if suffix in (".aiff", ".aif", ".aifc", ".au", ".snd"):
         import warnings
 
@@ -154,17 +153,37 @@ def load_wav_mono16k(path) -> np.ndarray:
             if r.getcomptype() not in (b"NONE", "NONE"):
                 raise ValueError(f"{path}: compressed {suffix} audio ({r.getcomptype()!r}) is not read")
             rate, width, ch = r.getframerate(), r.getsampwidth(), r.getnchannels()
-            pcm = _pcm_to_float(r.readframes(r.getnframes()), width, big_endian=True, unsigned8=False)
+            raw = r.readframes(r.getnframes())
+            pcm = np.frombuffer(raw, dtype=">i2").astype(np.int16) if width == 2 else _pcm_to_float(raw, width, big_endian=True, unsigned8=False)
     else:
         rate, ch, width, is_float, raw = _riff_wave(path)
+        raw = raw[:len(raw) // width * width]
         if is_float:
             if width not in (4, 8):
                 raise ValueError(f"{path}: IEEE float samples of {8 * width} bits")
-            pcm = np.frombuffer(raw[:len(raw) // width * width], dtype="<f4" if width == 4 else "<f8").astype(np.float32)
+            pcm = np.frombuffer(raw, dtype="<f4" if width == 4 else "<f8").astype(np.float32)
+        elif width == 2:
+            pcm = np.frombuffer(raw, dtype="<i2").astype(np.int16)
         else:
-            pcm = _pcm_to_float(raw[:len(raw) // width * width], width)
+            pcm = _pcm_to_float(raw, width)
     if ch > 1:
-        pcm = pcm[:pcm.size // ch * ch].reshape(-1, ch).mean(axis=1).astype(np.float32)
+        pcm = pcm[:pcm.size // ch * ch]
+    return pcm, int(rate), int(ch)
+
+
+def load_wav_mono16k(path) -> np.ndarray:
+    """Audio file -> float32 mono @16 kHz in [-1, 1): the reference's AudioData.load (vad/data_models/audio_data.py:
+    18-34) with the stdlib instead of soundfile: ``.pcm`` = headerless 16-bit mono @16 kHz (:21-24); WAV with integer PCM of
+    8 / 16 / 24 / 32 bits or IEEE float 32 / 64 (plain or WAVE_FORMAT_EXTENSIBLE); AIFF / AIFF-C (uncompressed) and Sun AU (linear PCM)
+    through the stdlib readers; any channel count (averaged, :26) and any rate (resampled, :27-30).  Compressed containers (FLAC,
+    OGG, MP3 ...) need a decoder this image does not have: convert them first."""
+    pcm, rate, ch = read_audio(path)
+    if pcm.dtype == np.int16:
+        pcm = pcm.astype(np.float32) / 32768.0
+    if Path(path).suffix.lower() == ".pcm":
+        return pcm.astype(np.float32)
+    if ch > 1:
+        pcm = pcm.reshape(-1, ch).mean(axis=1).astype(np.float32)
     return resample_to_16k(pcm, rate)
 
 
@@ -181,6 +200,131 @@ def pcm16_to_f32(pcm: torch.Tensor) -> torch.Tensor:
         _lib.check(_lib.load().savad_pcm16_to_f32(ctypes.c_void_p(pcm.data_ptr()), pcm.numel(), ctypes.c_void_p(out.data_ptr()),
                                                  ctypes.c_void_p(torch.cuda.current_stream(pcm.device).cuda_stream)))
     return out
+
+
+_RS_WINDOW = 8193   # include/savad.h: SAVAD_RESAMPLE_WINDOW
+_rs_window_set = False
+
+
+def kaiser_fast_window() -> np.ndarray:
+    """resampy's "kaiser_fast" half window as resampy.filters.sinc_window groups it: taper * (rolloff * sinc).  (`_kaiser_fast_table`
+    above multiplies in another order and differs in the last bit of some entries; resample_to_16k keeps that one and its bits.)"""
+    n = (1 << _RS_BITS) * _RS_ZEROS
+    sinc_win = _RS_ROLLOFF * np.sinc(_RS_ROLLOFF * np.linspace(0, _RS_ZEROS, num=n + 1, endpoint=True))
+    return np.ascontiguousarray(np.kaiser(2 * n + 1, _RS_BETA)[n:] * sinc_win, dtype=np.float64)
+
+
+def _resample_lib():
+    """the library with the resampler's filter handed over (savad_resample_set_window: the table is numpy's, see include/savad.h)"""
+    global _rs_window_set
+    lib = _lib.load()
+    if not _rs_window_set:
+        win = kaiser_fast_window()
+        assert win.shape == (_RS_WINDOW,)
+        _lib.check(lib.savad_resample_set_window(ctypes.c_void_p(win.ctypes.data)))
+        _rs_window_set = True
+    return lib
+
+
+def resample_length(n_samples: int, rate: int) -> int:
+    """samples of the 16 kHz signal: ceil(n_samples * 16000 / rate) (librosa's fix_length target)"""
+    n = _lib.load().savad_resample_length(int(n_samples), int(rate))
+    if n < 0:
+        _lib.check(n)
+    return n
+
+
+def resample_span_samples(n_samples: int, rate: int, out_first: int, out_count: int):
+    """(first, count): the input samples outputs [out_first, +out_count) of an n_samples-long recording read (first % 4 == 0)"""
+    first, count = ctypes.c_long(), ctypes.c_long()
+    _lib.check(_lib.load().savad_resample_span_samples(int(n_samples), int(rate), int(out_first), int(out_count),
+                                                       ctypes.byref(first), ctypes.byref(count)))
+    return first.value, count.value
+
+
+def resample_prepare(rate: int, device) -> None:
+    """build and upload a source rate's tables on `device` (synchronises; the compute calls do it on first use otherwise)"""
+    with torch.cuda.device(torch.device(device)):
+        _lib.check(_resample_lib().savad_resample_prepare(int(rate)))
+
+
+def _check_device_f32(audio, what="audio"):
+    if not (isinstance(audio, torch.Tensor) and audio.dtype == torch.float32 and audio.dim() == 1 and audio.device.type == "cuda"
+            and audio.is_contiguous()):
+        raise ValueError(f"{what} must be a contiguous 1-D float32 tensor on a HIP device")
+
+
+def resample_to_16k_device(audio_dev: torch.Tensor, rate: int) -> torch.Tensor:
+    """float32 mono samples at `rate` Hz on a HIP device -> the 16 kHz signal, ceil(n * 16000 / rate) samples, on the device: the
+    reference's librosa.resample(audio, sr, 16000, res_type="kaiser_fast") (vad/data_models/audio_data.py:27-30) with the bits of
+    resampy's loop (savad_resample; include/savad.h).  A 16 kHz source is returned as it is."""
+    _check_device_f32(audio_dev)
+    rate = int(rate)
+    if rate == SAMPLE_RATE:
+        return audio_dev
+    lib = _resample_lib()
+    n = audio_dev.numel()
+    with torch.cuda.device(audio_dev.device):
+        out = torch.empty(resample_length(n, rate), dtype=torch.float32, device=audio_dev.device)
+        _lib.check(lib.savad_resample(ctypes.c_void_p(audio_dev.data_ptr()), n, rate, ctypes.c_void_p(out.data_ptr()),
+                                      ctypes.c_void_p(torch.cuda.current_stream(audio_dev.device).cuda_stream)))
+    return out
+
+
+def resample_span_device(audio_dev: torch.Tensor, audio_first: int, n_samples: int, rate: int, out_first: int, out_count: int,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Samples [out_first, out_first + out_count) of the 16 kHz signal of an n_samples-long recording, from a device slice that starts
+    at input sample `audio_first` (savad_resample_span; `resample_span_samples` names the slice a span needs): the same bits as
+    resample_to_16k_device(whole recording)[out_first:out_first + out_count].  `out`: where to write them."""
+    _check_device_f32(audio_dev)
+    lib = _resample_lib()
+    with torch.cuda.device(audio_dev.device):
+        if out is None:
+            out = torch.empty(int(out_count), dtype=torch.float32, device=audio_dev.device)
+        elif out.numel() != int(out_count):
+            raise ValueError("out must hold out_count samples")
+        _check_device_f32(out, "out")
+        _lib.check(lib.savad_resample_span(ctypes.c_void_p(audio_dev.data_ptr()), int(audio_first), audio_dev.numel(), int(n_samples), int(rate),
+                                           int(out_first), int(out_count), ctypes.c_void_p(out.data_ptr()),
+                                           ctypes.c_void_p(torch.cuda.current_stream(audio_dev.device).cuda_stream)))
+    return out
+
+
+def downmix_device(raw_dev: torch.Tensor, channels: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """interleaved int16 or float32 samples [frames * channels] on a HIP device -> float32 mono [frames] in [-1, 1) with the bits of the
+    host loader (sample / 32768 for int16, then the float32 channel mean: vad/data_models/audio_data.py:26; savad_ingest_downmix).
+    Limits: int16 up to 256 channels, float32 up to 7 (beyond that numpy's mean sums in another order: refused)."""
+    channels = int(channels)
+    if not (isinstance(raw_dev, torch.Tensor) and raw_dev.dtype in (torch.int16, torch.float32) and raw_dev.dim() == 1
+            and raw_dev.device.type == "cuda" and raw_dev.is_contiguous()):
+        raise ValueError("raw must be a contiguous 1-D int16 or float32 tensor on a HIP device")
+    if channels < 1 or raw_dev.numel() % channels:
+        raise ValueError(f"{raw_dev.numel()} samples are not whole frames of {channels} channels")
+    if channels == 1 and raw_dev.dtype == torch.float32 and out is None:
+        return raw_dev
+    frames = raw_dev.numel() // channels
+    with torch.cuda.device(raw_dev.device):
+        if out is None:
+            out = torch.empty(frames, dtype=torch.float32, device=raw_dev.device)
+        elif out.numel() != frames:
+            raise ValueError("out must hold one sample per frame")
+        _check_device_f32(out, "out")
+        _lib.check(_lib.load().savad_ingest_downmix(ctypes.c_void_p(raw_dev.data_ptr()), 0 if raw_dev.dtype == torch.int16 else 1, channels,
+                                                    frames, ctypes.c_void_p(out.data_ptr()),
+                                                    ctypes.c_void_p(torch.cuda.current_stream(raw_dev.device).cuda_stream)))
+    return out
+
+
+def load_audio_device(path, device="cuda") -> torch.Tensor:
+    """Audio file -> float32 mono @16 kHz on `device`: load_wav_mono16k with the channel average and the resampling on the GPU.  The
+    file's samples go up as they are stored (16-bit PCM: 2 bytes per sample), then downmix_device and resample_to_16k_device."""
+    raw, rate, channels = read_audio(path)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.SavadError("the device ingest runs only on a HIP device (no CPU fallback)")
+    if raw.size == 0:
+        return torch.empty(0, dtype=torch.float32, device=dev)
+    return resample_to_16k_device(downmix_device(torch.from_numpy(raw).to(dev), channels), rate)
 
 
 def log_mel(audio, device="cuda") -> torch.Tensor:

@@ -68,17 +68,21 @@ class VADFromScratchPredictor:
 
     def __init__(self, model: SelfAttentiveVAD, device: torch.device, context: ContextResolution = ContextResolution(),
                  chunk_size: int = 16384, graph: bool = False, graph_max_seconds: float = 120.0, graph_cache: int = 8,
-                 front_end=None):
+                 front_end=None, device_ingest: bool = False):
         """`graph=True` (not in the reference's signature): clip-sized inputs -- up to `graph_max_seconds` of audio -- run as a
         replayed HIP graph of the whole chain log-mel -> window gather -> forward -> boost, captured on first use per (length, model
         knobs) and re-captured when the weights change; at most `graph_cache` graphs are kept (least recently used goes).  For a 10 s
         clip the four launches take less time than the Python and the library calls around them: the replay halves the time per clip,
         same bits (predict_audio_device).
         `front_end` (features.FrontEnd; None = the shipped log-mel): the transform predict / predict_audio_device / evaluate run
-        on the audio.  Only the shipped one has the host-upload path (predict_audio_host)."""
+        on the audio.  Only the shipped one has the host-upload path (predict_audio_host).
+        `device_ingest=True`: predict_from_path uploads a file's samples as they are stored and averages the channels and resamples
+        to 16 kHz on the GPU (features.load_audio_device) instead of on the host (features.load_wav_mono16k): the resampler has the
+        bits of resampy's loop, which the host function approaches within 2e-6."""
         from .features import SHIPPED_FRONT_END
 
         self.front_end = SHIPPED_FRONT_END if front_end is None else front_end
+        self.device_ingest = bool(device_ingest)
         self.graph, self.graph_max_seconds, self.graph_cache = bool(graph), float(graph_max_seconds), int(graph_cache)
         self._graphs: "OrderedDict[tuple, dict]" = OrderedDict()
         self.graph_stats = {"captures": 0, "replays": 0, "eager": 0}
@@ -140,7 +144,8 @@ class VADFromScratchPredictor:
         return full_unpickle()
 
     @classmethod
-    def from_checkpoint(cls, checkpoint_path, device, trust_checkpoint: bool = False, extended_front_end: bool = False):
+    def from_checkpoint(cls, checkpoint_path, device, trust_checkpoint: bool = False, extended_front_end: bool = False,
+                        device_ingest: bool = False):
         """vad/predictor.py:264-280: a training checkpoint holds {"config": ..., "state_dict": ...} plus what
         ModelCheckpointer adds (epoch, global_step, monitor_metric, a `metrics` dict of numpy scalars, optimizer /
         scheduler / grad-scaler state: vad/training/checkpointers/model_checkpointer.py:97-110); the model size, the
@@ -149,7 +154,7 @@ class VADFromScratchPredictor:
         `extended_front_end=True` builds every feature_extractor config features.FrontEnd takes (the four transforms at any
         geometry within its limits, temporal differences); the default refuses all but the shipped one.  The shipped
         features are pinned by goldens and trained-weights AUC, the others by a restatement of librosa 0.8.0: opting in
-        acknowledges that."""
+        acknowledges that.  `device_ingest`: as in the constructor."""
         ckpt = cls._load_checkpoint(checkpoint_path, trust_checkpoint)
         cfg = ckpt["config"]
 
@@ -180,7 +185,7 @@ class VADFromScratchPredictor:
             model.load_state_dict(ckpt["state_dict"])
             ctx = ContextResolution(get(cfg, "context_resolution", "context_window_half_frames"),
                                     get(cfg, "context_resolution", "context_window_jump_frames"))
-            predictor = cls(model.to(device).eval(), device, ctx, front_end=front)
+            predictor = cls(model.to(device).eval(), device, ctx, front_end=front, device_ingest=device_ingest)
             predictor.hop_ms, predictor.window_ms = front.hop_ms, front.window_ms  # vad/predictor.py:103-104
             return predictor
         tr = get(fe, "transform")
@@ -198,22 +203,28 @@ class VADFromScratchPredictor:
         model.load_state_dict(ckpt["state_dict"])
         ctx = ContextResolution(get(cfg, "context_resolution", "context_window_half_frames"),
                                 get(cfg, "context_resolution", "context_window_jump_frames"))
-        predictor = cls(model.to(device).eval(), device, ctx)
+        predictor = cls(model.to(device).eval(), device, ctx, device_ingest=device_ingest)
         predictor.hop_ms, predictor.window_ms = got["hop_ms"], got["window_ms"]  # vad/predictor.py:103-104
         return predictor
 
     def predict_from_path(self, audio_path, parameters: VADPredictParameters) -> VoiceActivity:
-        """vad/predictor.py:71-75 (16 kHz PCM WAV only; the reference also resamples via librosa)."""
-        from .features import load_wav_mono16k
+        """vad/predictor.py:71-75: AudioData.load (any channel count, any rate: averaged and resampled to 16 kHz mono) -> predict.
+        The loading runs on the host (features.load_wav_mono16k), or with `device_ingest` on the GPU (features.load_audio_device:
+        the raw samples are uploaded, the 16 kHz signal never visits the host)."""
+        from .features import load_audio_device, load_wav_mono16k
 
+        if self.device_ingest:
+            return self.predict(load_audio_device(audio_path, self.device), parameters)
         return self.predict(load_wav_mono16k(audio_path), parameters)
 
     def predict(self, audio: np.ndarray, parameters: VADPredictParameters, features_fn=None) -> VoiceActivity:
-        """vad/predictor.py:77-157.  audio: float32 mono @16 kHz.  features_fn(chunk_audio) -> [N, F] overrides
+        """vad/predictor.py:77-157.  audio: float32 mono @16 kHz, a numpy array or a 1-D float32 tensor on the predictor's device
+        (sliced and fed to the front-end where it is: no host round trip).  features_fn(chunk_audio) -> [N, F] overrides
         the GPU front-end (used by the parity tests to feed the reference's feature matrix)."""
         from .features import SAMPLE_RATE
 
-        audio = np.asarray(audio, dtype=np.float32)
+        if not (isinstance(audio, torch.Tensor) and audio.device.type == "cuda" and audio.dtype == torch.float32 and audio.dim() == 1):
+            audio = np.asarray(audio, dtype=np.float32)
         duration_s = len(audio) / SAMPLE_RATE
         num_chunks = math.ceil(duration_s / parameters.split_max_seconds) if parameters.split_max_seconds is not None else 1
         adjusted = duration_s / num_chunks
@@ -345,19 +356,26 @@ class VADFromScratchPredictor:
         return plan
 
     @torch.no_grad()
-    def predict_audio_host(self, audio, frames_per_chunk: int = 65536):
-        """The reference's mode END TO END from host memory: `audio` = the whole recording on the host, mono 16 kHz, 16-bit PCM
+    def predict_audio_host(self, audio, frames_per_chunk: int = 65536, sample_rate: int = 16000, channels: int = 1):
+        """The reference's mode END TO END from host memory: `audio` = the whole recording on the host, 16-bit PCM
         (uploaded as it is, converted on the device) or float32, numpy array or CPU tensor (pinned: asynchronous uploads) ->
         (probs [N, W], mean [N]) on the device.  Output frames are produced in chunks of `frames_per_chunk`; chunk c needs the feature
         frames within 2 x half of its own (every window that reaches one of its frames, vad/predictor.py:186-258), whose samples are
         uploaded on a copy stream while chunk c - 1 runs.  A chunk's first window keeps its place modulo the packed block (a multiple
-        of 32 // W windows), so the results are predict_audio_device's bits."""
+        of 32 // W windows), so the results are predict_audio_device's bits.
+        `sample_rate`, `channels`: the recording as a file holds it -- `audio` is then the interleaved 1-D sample stream at that rate
+        (features.read_audio), and a chunk uploads the raw frames its 16 kHz samples are interpolated from; on the device they are
+        averaged over the channels (downmix_device) and resampled (resample_span_device) into a 16 kHz signal that grows chunk by
+        chunk: the bits of predict_audio_device(resample_to_16k_device(downmix_device(audio))).  With the defaults (16 kHz mono) the
+        code path is the one above, unchanged."""
         from .features import log_mel_span, pcm16_to_f32, span_samples
 
         if self.device.type != "cuda":
             raise _lib.SavadError("the MI355X predictor needs a HIP device (no CPU fallback)")
         self._require_shipped_front_end("predict_audio_host")
         src = StreamingPredictor._host_source(audio)
+        if int(sample_rate) != 16000 or int(channels) != 1:
+            return self._predict_raw_host(src, int(frames_per_chunk), int(sample_rate), int(channels))
         n = int(src.shape[0])
         N = 1 + n // 160
         half, jump, Wn = self.context_window_half_frames, self.context_window_jump_frames, self.context_window_frames
@@ -396,6 +414,78 @@ class VADFromScratchPredictor:
                 if sl.dtype == torch.int16:
                     sl = pcm16_to_f32(sl)
                 feat = log_mel_span(sl, first, n, g0, g1 - g0)
+                p, mu = self.model.predict_windows(feat, half, jump, self.chunk_size)
+                probs[f0:f1].copy_(p[f0 - g0:f1 - g0])
+                mean[f0:f1].copy_(mu[f0 - g0:f1 - g0])
+                ev = nxt
+        return probs, mean
+
+    def _predict_raw_host(self, src, frames_per_chunk: int, rate: int, channels: int):
+        """predict_audio_host for a recording that is not 16 kHz mono (see there)"""
+        from .features import (SAMPLE_RATE, downmix_device, log_mel_span, resample_length, resample_prepare, resample_span_device,
+                               resample_span_samples, span_samples)
+
+        if channels < 1 or src.numel() % channels:
+            raise ValueError(f"{src.numel()} samples are not whole frames of {channels} channels")
+        n_in = src.numel() // channels
+        n = resample_length(n_in, rate)            # samples of the 16 kHz signal
+        if n < 1:
+            raise ValueError("audio must be a non-empty array")
+        N = 1 + n // 160
+        half, jump, Wn = self.context_window_half_frames, self.context_window_jump_frames, self.context_window_frames
+        plan = [(f0, f1, g0, g1) + tuple(span_samples(n, g0, g1 - g0))
+                for f0, f1, g0, g1 in self.host_chunk_plan(N, half, Wn, frames_per_chunk)]
+        self.model.eval()
+        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        with torch.cuda.device(dev):
+            if rate != SAMPLE_RATE:
+                resample_prepare(rate, dev)        # (the table upload synchronises: before the first copy is in flight)
+            cur = torch.cuda.current_stream(dev)
+            if getattr(self, "_copy_stream", None) is None or self._copy_stream.device != dev:
+                self._copy_stream = torch.cuda.Stream(dev)
+            cs = self._copy_stream
+            raw = torch.empty(n_in * channels, dtype=src.dtype, device=dev)
+            raw.record_stream(cs)
+            cs.wait_stream(cur)
+            plain = channels == 1 and src.dtype == torch.float32          # the raw buffer already is the mono signal
+            mono = raw if plain else torch.empty(n_in, dtype=torch.float32, device=dev)
+            audio16 = mono if rate == SAMPLE_RATE else torch.empty(n, dtype=torch.float32, device=dev)
+            probs = torch.empty((N, Wn), dtype=torch.float32, device=dev)
+            mean = torch.empty((N,), dtype=torch.float32, device=dev)
+            uploaded = mixed = done16 = 0          # frames on the device / averaged; 16 kHz samples produced
+
+            def frames_for(c):                     # raw frames [0, end) the 16 kHz samples of chunks 0 .. c are interpolated from
+                end16 = plan[c][4] + plan[c][5]
+                if rate == SAMPLE_RATE:
+                    return end16
+                first, count = resample_span_samples(n_in, rate, 0, end16)
+                return first + count
+
+            def upload(c):
+                nonlocal uploaded
+                end = frames_for(c)
+                ev = torch.cuda.Event()
+                with torch.cuda.stream(cs):
+                    if end > uploaded:
+                        raw[uploaded * channels:end * channels].copy_(src[uploaded * channels:end * channels], non_blocking=True)
+                        uploaded = end
+                    ev.record(cs)
+                return ev
+
+            ev = upload(0)
+            for c, (f0, f1, g0, g1, first, count) in enumerate(plan):
+                nxt = upload(c + 1) if c + 1 < len(plan) else None
+                cur.wait_event(ev)
+                have = frames_for(c)
+                if not plain and have > mixed:
+                    downmix_device(raw[mixed * channels:have * channels], channels, out=mono[mixed:have])
+                    mixed = have
+                end16 = first + count
+                if rate != SAMPLE_RATE and end16 > done16:
+                    need_first, _ = resample_span_samples(n_in, rate, done16, end16 - done16)
+                    resample_span_device(mono[need_first:have], need_first, n_in, rate, done16, end16 - done16, out=audio16[done16:end16])
+                    done16 = end16
+                feat = log_mel_span(audio16[first:end16], first, n, g0, g1 - g0)
                 p, mu = self.model.predict_windows(feat, half, jump, self.chunk_size)
                 probs[f0:f1].copy_(p[f0 - g0:f1 - g0])
                 mean[f0:f1].copy_(mu[f0 - g0:f1 - g0])
