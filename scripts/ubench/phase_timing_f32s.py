@@ -17,7 +17,9 @@ lib.savad_debug_stamps.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.c_i
 buf = (ctypes.c_longlong * 64)()
 lib.savad_debug_stamps(buf, 64)
 t = list(buf)
-names = {1: "prologue: K0 landed", 2: "scores of tile 0", 3: "key tiles", 4: "context -> triples", 5: "out-projection (+h)", 6: "LN + split", 7: "FFN chunk 0",
+# (T > 32: the out-projection is folded into V -- stamp 5 closes the wait for chain slot 0 and h1 = h + bo + O / l, and the chain's
+# slots are 0..15 W1 / W2 chunks, 16..21 Q / K / V; T <= 32 keeps Wo in slots 0, 1 and stamp 5 behind its out-projection)
+names = {1: "prologue: K0 landed", 2: "scores of tile 0", 3: "key tiles", 4: "context normalised", 5: "slot 0 wait, h + bo + O/l", 6: "LN + split", 7: "FFN chunk 0",
          8: "FFN chunk 1", 9: "FFN chunk 2", 10: "FFN chunk 3", 11: "LN + split", 12: "Q slot 0", 13: "Q slot 1", 14: "K slot 0", 15: "K slot 1", 16: "V slot 0", 17: "V slot 1", 18: "end"}
 prev = t[0]
 print(f"[{B},{T},80] fp32s fused launch, wave 0 of workgroup 0 (s_memtime ticks = shader cycles)")
@@ -40,8 +42,8 @@ print(f"  start spread {rt0.max() / 100:.2f} us; end: first {rt1.min() / 100:.2f
 order = np.argsort(dur)
 print("  slowest workgroups (index, cycles, start us, end us):", [(int(i), int(dur[i]), round(rt0[i] / 100, 1), round(rt1[i] / 100, 1)) for i in order[-6:]])
 print("  fastest:", [(int(i), int(dur[i]), round(rt0[i] / 100, 1), round(rt1[i] / 100, 1)) for i in order[:4]])
-print("row chain slots 1..7 (wait + barrier, MFMAs + DMA pieces, gap to the next slot):")
-for T_ in range(1, 8):
+print("row chain slots 0..7 = W1, W1, W2, W2 of FFN chunks 0 and 1 (wait + barrier -- slot 0's sits in front of stamp 5 --, MFMAs + DMA pieces, gap to the next slot):")
+for T_ in range(0, 8):
     a, b2, c = t[24 + 3 * T_], t[25 + 3 * T_], t[26 + 3 * T_]
     nxt = t[24 + 3 * (T_ + 1)] if T_ < 7 else 0
     print(f"  slot {T_}: acquire {b2 - a:6d}  gemm {c - b2:6d}  then {nxt - c if nxt else 0:6d}")

@@ -89,6 +89,7 @@ struct savad_model {
     size_t f_win = 0;
     struct LayerFrag {
         size_t wqkv, wo, w1, w2;
+        size_t wqkv_vo = 0;  // lf3 only: Wq' | Wk' | Wo Wv' (prepare_frags3: the out-projection folded into V)
     };
     std::vector<LayerFrag> lf;
     std::vector<LayerFrag> lf3;  // byte offsets into d_frag3
@@ -106,6 +107,7 @@ struct savad_model {
     // packed offsets
     struct LayerPacked {
         size_t wqkv, bqkv, w1, b1;
+        size_t wvo, bqkv_vo;  // fp32s, T > 32: Wo Wv' [D][D] and bq' | bk' | Wo bv' (fold_vo_kernel)
         size_t frag;  // the layer's matrices in fragment order (packed_forward_kernel)
     };
     std::vector<LayerPacked> lp;
@@ -454,6 +456,16 @@ int prepare_frags3(savad_model* m, hipStream_t st) {
         if ((rc = pack_frags3(m, st, m->d_raw + m->lr[l].wo, D, D, m->lf3[l].wo))) return rc;
         if ((rc = pack_frags3(m, st, m->d_packed + m->lp[l].w1, DFF, D, m->lf3[l].w1))) return rc;
         if ((rc = pack_frags3(m, st, m->d_raw + m->lr[l].w2, D, DFF, m->lf3[l].w2))) return rc;
+        // the fused launches of T > 32 never issue the out-projection: one head, softmax rows sum to 1, so
+        //   Wo (P (x Wv'^T + bv')) + bo = P (x (Wo Wv')^T + Wo bv') + bo
+        // and the V position of a SECOND Q/K/V image holds Wvo = Wo Wv' (bias image: bq' | bk' | Wo bv'); products in fp64, rounded once.
+        // The unfolded images stay: the T <= 32 kernels read them.
+        const auto& p = m->lp[l];
+        hipLaunchKernelGGL(fs::fold_vo_kernel, dim3(D), dim3(D), 0, st, m->d_raw + m->lr[l].wo, m->d_packed + p.wqkv + (size_t)2 * D * D,
+                           m->d_packed + p.bqkv, m->d_packed + p.wvo, m->d_packed + p.bqkv_vo);
+        HIP_TRY(hipGetLastError());
+        if ((rc = pack_frags3(m, st, m->d_packed + p.wqkv, 2 * D, D, m->lf3[l].wqkv_vo))) return rc;
+        if ((rc = pack_frags3(m, st, m->d_packed + p.wvo, D, D, m->lf3[l].wqkv_vo + (size_t)2 * D * D * 6))) return rc;
     }
     m->frag3_dirty = false;
     return SAVAD_OK;
@@ -708,6 +720,10 @@ SAVAD_EXPORT int savad_create(const savad_config* cfg, savad_handle* out) {
         m->packed_floats += (size_t)DFF * D;
         q.b1 = m->packed_floats;
         m->packed_floats += DFF;
+        q.wvo = m->packed_floats;
+        m->packed_floats += (size_t)D * D;
+        q.bqkv_vo = m->packed_floats;
+        m->packed_floats += 3 * D;
         q.frag = m->packed_floats;
         m->packed_floats += FRAG_LAYER;
     }
@@ -751,6 +767,8 @@ SAVAD_EXPORT int savad_create(const savad_config* cfg, savad_handle* out) {
         m->frag3_bytes += (size_t)DFF * D * 6;
         fl.w2 = m->frag3_bytes;
         m->frag3_bytes += (size_t)D * DFF * 6;
+        fl.wqkv_vo = m->frag3_bytes;
+        m->frag3_bytes += (size_t)3 * D * D * 6;
     }
     hipError_t e = hipMalloc(&m->d_raw, sizeof(float) * m->raw_floats);
     if (e == hipSuccess) e = hipMalloc(&m->d_frag, m->frag_bytes);
@@ -1242,11 +1260,14 @@ int forward_f32s(savad_model* m, const float* x, int B, int T, float* out, void*
         return SAVAD_OK;
     }
     char* sets[2][3] = {{W + bp.q, W + bp.k, W + bp.vt}, {W + bp.q2, W + bp.k2, W + bp.vt2}};
-    hipLaunchKernelGGL(fs::input_qkv_kernel_f32s, dim3(bp.nblk_pad / 4), dim3(256), fs::NRING3 * fs::SLOT_BYTES + 3 * D * 4, st, x, xbs, B, T, F,
-                       bp.nblk, Fr + m->f3_win, R + m->r_bin, m->d_pe, Fr + m->lf3[0].wqkv, P + m->lp[0].bqkv, hb, sets[0][0], sets[0][1],
-                       sets[0][2], c);
-    prof.mark("input_qkv_f32s");
     const bool packed = T <= 32;
+    // T > 32: V is projected with Wo Wv' (prepare_frags3), so that P V already is the out-projected context -- the fused launch's row
+    // chain has no out-projection.  The T <= 32 form of the launch keeps the plain images and its out-projection.
+    auto wqkv3 = [&](int l) { return Fr + (packed ? m->lf3[l].wqkv : m->lf3[l].wqkv_vo); };
+    auto bqkv3 = [&](int l) { return P + (packed ? m->lp[l].bqkv : m->lp[l].bqkv_vo); };
+    hipLaunchKernelGGL(fs::input_qkv_kernel_f32s, dim3(bp.nblk_pad / 4), dim3(256), fs::NRING3 * fs::SLOT_BYTES + 3 * D * 4, st, x, xbs, B, T, F,
+                       bp.nblk, Fr + m->f3_win, R + m->r_bin, m->d_pe, wqkv3(0), bqkv3(0), hb, sets[0][0], sets[0][1], sets[0][2], c);
+    prof.mark("input_qkv_f32s");
     const int QB = (T + 31) / 32, NG = (QB + 3) / 4;
     const dim3 grid(packed ? bp.nblk_pad / 4 : 8 * (((long)B * NG + 7) / 8));
     for (int l = 0; l < L; ++l) {
@@ -1261,15 +1282,15 @@ int forward_f32s(savad_model* m, const float* x, int B, int T, float* out, void*
         A.T = T;
         A.nblk = bp.nblk;
         A.hbuf = hb;
-        A.wo_frag = Fr + f.wo;
+        A.wo_frag = Fr + f.wo;   // (read by the T <= 32 form only)
         A.bo = R + r.bo;
         A.w1_frag = Fr + f.w1;
         A.b1 = P + p.b1;
         A.w2_frag = Fr + f.w2;
         A.b2 = R + r.b2;
-        A.wn_frag = last ? nullptr : Fr + m->lf3[l + 1].wqkv;
+        A.wn_frag = last ? nullptr : wqkv3(l + 1);
         A.wc = last ? P + m->p_wc : nullptr;
-        A.bn = last ? P + m->p_bc : P + m->lp[l + 1].bqkv;
+        A.bn = last ? P + m->p_bc : bqkv3(l + 1);
         A.qf = nxt[0];
         A.kf = nxt[1];
         A.vtf = nxt[2];

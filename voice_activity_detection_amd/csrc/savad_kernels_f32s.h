@@ -26,6 +26,17 @@
 //   ring      : 3 slots of 48 KiB = two n-blocks of a weight matrix (K = 128), or the K and V^T images of ONE key block;
 //               the DMA runs two slots ahead; one 4-wave workgroup per CU (one wave per SIMD, up to 512 VGPRs).
 //
+// T > 32 (the fused launches): the out-projection is folded into the value projection.  The encoder has one head
+// (vad/models/self_attention.py:17-18) and a softmax row sums to 1, so
+//
+//      final_projection(softmax(Q K^T) (x Wv'^T + bv')) = softmax(Q K^T) (x (Wo Wv')^T + Wo bv') + bo
+//
+// Wvo = Wo Wv' and bvo = Wo bv' depend on the weights alone and are built once when the weights are packed (fold_vo_kernel, fp64 sums
+// rounded once; a second Q / K / V image per layer with Wvo in the V position).  P V then IS the out-projected context: a launch's stream
+// is  K(0) | [V(j)^T, K(j+1)] x key tiles | W1 / W2 chunks (16 slots) | next layer's Wq, Wk, Wvo (6 slots; none in the last layer)  --
+// no Wo slots, no split of the context into operand triples; the row chain starts at h1 = h + bo + O / l.  The T <= 32 kernels keep
+// the plain images and their out-projection.
+//
 // Reference being restated: vad/models/self_attention.py:23-28, vad/modeling/transformer.py:24-61,227-238,258-363,366-382.
 #pragma once
 #include "savad_kernels_bf16.h"
@@ -144,6 +155,24 @@ __device__ __forceinline__ void load_hblock32(f32x16 (&x)[4], const float* hb, i
 #pragma unroll
             for (int s = 0; s < 4; ++s) x[nb][4 * g + s] += t[s];
         }
+}
+// The residual block of the T > 32 fused launch, requested BY HAND (16 x global_load_dwordx4, fragment g of n-block nb -> hr[4 nb + g])
+// in front of the last key tile and waited for by the ring wait at the head of the row chain: twelve DMA pieces are younger, so the
+// chain's vmcnt(12) retires it (in-order return).  Requested by the compiler, its own wait -- which counts none of the asm-issued
+// pieces -- sat in front of the first use and waited out the whole newest ring slot.  hr is in / out: the registers of the request
+// are the ones a wave without a block keeps its zeros in.  scripts/check_async_loads.py checks that nothing touches them in flight.
+__device__ __forceinline__ void request_hblock32(f32x4 (&hr)[16], const float* hb /* wave-uniform */, int lane) {
+#define SAVAD_H_LD(i)                                                                                                          \
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "+v"(hr[i]) : "v"((unsigned)lane * 16u + 4096u * ((i) / 4)), "s"(hb), \
+                 "n"(((i) % 4) * 1024) : "memory")
+    SAVAD_H_LD(0); SAVAD_H_LD(1); SAVAD_H_LD(2); SAVAD_H_LD(3); SAVAD_H_LD(4); SAVAD_H_LD(5); SAVAD_H_LD(6); SAVAD_H_LD(7);
+    SAVAD_H_LD(8); SAVAD_H_LD(9); SAVAD_H_LD(10); SAVAD_H_LD(11); SAVAD_H_LD(12); SAVAD_H_LD(13); SAVAD_H_LD(14); SAVAD_H_LD(15);
+#undef SAVAD_H_LD
+}
+// behind the wait that retired the request: from here on the compiler may read hr
+__device__ __forceinline__ void landed_hblock32(f32x4 (&hr)[16]) {
+    asm volatile("" : "+v"(hr[0]), "+v"(hr[1]), "+v"(hr[2]), "+v"(hr[3]), "+v"(hr[4]), "+v"(hr[5]), "+v"(hr[6]), "+v"(hr[7]), "+v"(hr[8]),
+                 "+v"(hr[9]), "+v"(hr[10]), "+v"(hr[11]), "+v"(hr[12]), "+v"(hr[13]), "+v"(hr[14]), "+v"(hr[15]));
 }
 __device__ __forceinline__ void store_hblock32(float* hb, const f32x16 (&x)[4], int lane) {
 #pragma unroll
@@ -289,6 +318,24 @@ __global__ void pack_weight_frags3_kernel(const float* __restrict__ W, int N, in
         out[o + 512] = pm;
         out[o + 1024] = pl;
     }
+}
+
+// The out-projection folded into the value projection.  The encoder has ONE head (vad/models/self_attention.py:17-18), and a softmax
+// row sums to 1, so final_projection(P (x Wv'^T + bv')) = P (x (Wo Wv')^T + Wo bv') + bo: with Wvo = Wo Wv' and bvo = Wo bv' in the V
+// position, P V already is the out-projected context.  Sums in fp64, rounded once.  Block n = row of Wvo, thread k = its column (D x D
+// threads); bqkv_vo = bq' | bk' | bvo.
+__global__ void fold_vo_kernel(const float* __restrict__ Wo, const float* __restrict__ Wv, const float* __restrict__ bqkv,
+                               float* __restrict__ Wvo, float* __restrict__ bqkv_vo) {
+    const int n = blockIdx.x, k = threadIdx.x;
+    double acc = 0.0, accb = 0.0;
+    for (int j = 0; j < D; ++j) {
+        const double w = (double)Wo[(size_t)n * D + j];
+        acc += w * (double)Wv[(size_t)j * D + k];
+        accb += w * (double)bqkv[2 * D + j];
+    }
+    Wvo[(size_t)n * D + k] = (float)acc;
+    if (k == 0) bqkv_vo[2 * D + n] = (float)accb;
+    if (n < 2) bqkv_vo[n * D + k] = bqkv[n * D + k];
 }
 
 // One of the six QKV slots: slot S covers n-blocks 2 (S & 1), 2 (S & 1) + 1 of projection rb = S >> 1 (0 query, 1 key:
@@ -627,36 +674,42 @@ __device__ __forceinline__ void attn_tile3_global(AttnState& st, const Tri (&qp)
 // ---------------------------------------------------------------------------------------------
 // Row chain of one block per wave (vad/modeling/transformer.py:347,234-238,366-382; LAST: :33 and
 // vad/models/self_attention.py:26-27): out-projection + residual -> LN -> FFN + residual -> next layer's LN + Q/K/V^T, or
-// the encoder LayerNorm + classifier + LogSoftmax.  Weight stream = slots
-//   0,1: Wo | 2+4c, 3+4c: W1 chunk c | 4+4c, 5+4c: W2 chunk c (c = 0..3) | 18..23: Wq, Wk, Wv  (two n-blocks per slot)
-// at ring positions base + t.  PREFETCHED: slots 0 and 1 are already in flight (the fused launch requests them under its last two
-// key tiles, so that the chain does not start with an exposed DMA round trip).
+// the encoder LayerNorm + classifier + LogSoftmax.  Weight stream = slots (two n-blocks per slot, at ring positions base + t)
+//   !FOLDED (T <= 32):  0,1: Wo | 2+4c, 3+4c: W1 chunk c | 4+4c, 5+4c: W2 chunk c (c = 0..3) | 18..23: Wq, Wk, Wv      24, LAST 18
+//   FOLDED  (T > 32):   4c, 4c+1: W1 chunk c | 4c+2, 4c+3: W2 chunk c (c = 0..3) | 16..21: Wq, Wk, Wvo                  22, LAST 16
+// FOLDED: V was projected with Wo Wv' (fold_vo_kernel), the caller's attention accumulators hc already are the out-projected context
+// and its residual block hr is in flight (request_hblock32); slots 0 and 1 are in flight too (the fused launch requests them under
+// its last two key tiles, so that the chain does not start with an exposed DMA round trip).
 // ---------------------------------------------------------------------------------------------
 struct RowArgs3 {
     int B, T, nblk;
     float* hbuf;
-    const char* wo_frag;
+    const char* wo_frag;  // !FOLDED only
     const float* bo;
     const char* w1_frag;
     const float* b1;
     const char* w2_frag;
     const float* b2;
-    const char* wn_frag;  // !LAST: next layer's Wqkv' triples
+    const char* wn_frag;  // !LAST: next layer's Wqkv' triples (FOLDED: the image with Wo Wv' in the V position)
     const float* wc;      // LAST: Wc' fp32 [2][D]
-    const float* bn;      // !LAST: bqkv' [384]; LAST: bc' [2]
+    const float* bn;      // !LAST: bqkv' [384] (FOLDED: bq' | bk' | Wo bv'); LAST: bc' [2]
     char *qf, *kf, *vtf;  // !LAST: written (the NEXT layer's buffers)
     float* out;           // LAST
     float qscale;
 };
-// the two segments of row-chain slot t (compile-time t in the chain itself; 0 / 1 at run time for the fused launch's prefetch)
-__device__ __forceinline__ const char* row_seg(const RowArgs3& A, int t, int sgm) {
-    if (t < 2) return A.wo_frag + (size_t)(2 * t + sgm) * BLK3_BYTES;
-    if (t < 18) {
-        const int c = (t - 2) >> 2, r = (t - 2) & 3;
+// the two segments of row-chain slot t (compile-time t in the chain itself; 0 / 1 at run time for the fused launch's prefetch);
+// folded (compile-time): the stream without the two Wo slots
+__device__ __forceinline__ const char* row_seg(const RowArgs3& A, int t, int sgm, bool folded) {
+    if (!folded) {
+        if (t < 2) return A.wo_frag + (size_t)(2 * t + sgm) * BLK3_BYTES;
+        t -= 2;
+    }
+    if (t < 16) {
+        const int c = t >> 2, r = t & 3;
         return r < 2 ? A.w1_frag + (size_t)(4 * c + 2 * r + sgm) * BLK3_BYTES
                      : A.w2_frag + (size_t)((2 * (r - 2) + sgm) * 32 + 8 * c) * TFRAG_BYTES;  // n-block, K-steps 8c..8c+7
     }
-    return A.wn_frag + (size_t)(2 * (t - 18) + sgm) * BLK3_BYTES;
+    return A.wn_frag + (size_t)(2 * (t - 16) + sgm) * BLK3_BYTES;
 }
 
 // the row chain's biases (LAST: the classifier's folded weights and bias in the Q/K/V slot) -> LDS behind the ring; called at the head
@@ -685,42 +738,56 @@ struct RowBiases {
     }
 };
 
-template <bool LAST, bool PREFETCHED>
-__device__ __forceinline__ void row_stage_f32s(const RowArgs3& A, char* smem, Tri (&xp)[8], int blk, bool live, const Ring3& ring, int base) {
+template <bool LAST, bool FOLDED>
+__device__ __forceinline__ void row_stage_f32s(const RowArgs3& A, char* smem, Tri (&xp)[8], const f32x16 (&hc)[4], f32x4 (&hr)[16], int blk,
+                                               bool live, const Ring3& ring, int base) {
     float* lbo = reinterpret_cast<float*>(smem + NRING3 * SLOT_BYTES);
     float* lb1 = lbo + D;
     float* lb2 = lb1 + DFF;
     float* lbn = lb2 + D;
     const int lane = ring.lane, m = lane & 31, h = lane >> 5;
-    constexpr int NSLOT = LAST ? 18 : 24;
-    auto job = [&](int t) { return ring.job(base + t, row_seg(A, t, 0), row_seg(A, t, 1)); };
+    constexpr int OFF = FOLDED ? 0 : 2;   // slots in front of the FFN's: Wo
+    constexpr int NSLOT = OFF + (LAST ? 16 : 22);
+    auto job = [&](int t) { return ring.job(base + t, row_seg(A, t, 0, FOLDED), row_seg(A, t, 1, FOLDED)); };
     const DmaJob none{nullptr, 0u};
-    if (!PREFETCHED) {
-        ring.issue_all(job(0));
-        ring.issue_all(job(1));
-    }
     // acquire slot T_, then acc0 / acc1 += slot . operand with the DMA of slot T_ + 2 between the MFMAs
 #define SAVAD_ROW_GEMM(T_, acc0, acc1, operand)                                                                               \
     if ((T_) < 8) SAVAD_STAMP(24 + 3 * (T_));                                                                                 \
-    ring.acquire<((T_) + 1 < NSLOT) ? 1 : 0>();                                                                               \
+    if constexpr (!(FOLDED && (T_) == 0)) ring.acquire<((T_) + 1 < NSLOT) ? 1 : 0>();   /* (FOLDED: slot 0 was acquired for h1) */ \
     if ((T_) < 8) SAVAD_STAMP(25 + 3 * (T_));                                                                                 \
     gemm_slot<false, ((T_) + 2 < NSLOT)>(acc0, acc1, ring.slot(base + (T_)), operand, ring, (T_) + 2 < NSLOT ? job((T_) + 2) : none); \
     if ((T_) < 8) SAVAD_STAMP(26 + 3 * (T_));
     float* hb = A.hbuf + (size_t)blk * (32 * D);
-    // the residual block is requested here and added BEHIND the out-projection's MFMAs: its round trip to memory hides under them
-    // ---- h1 = h + (bo + ctx Wo^T)   (the biases were staged by stage_row_biases at the head of the kernel; any barrier since publishes them)
-    ring.acquire<1>();
-    f32x16 hres[4];
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) hres[nb] = zero16();
-    if (live) load_hblock32(hres, hb, lane);
     f32x16 h1[4];
+    if constexpr (FOLDED) {
+        // ---- h1 = h + (bo + O / l): the caller's accumulators hc already are the out-projected context, in h1's register layout
+        // (the biases were staged at the head of the kernel; any barrier since publishes them).  The wait for chain slot 0 comes first:
+        // it is also the wait for the residual block hr (request_hblock32).
+        ring.acquire<1>();
+        landed_hblock32(hr);
 #pragma unroll
-    for (int nb = 0; nb < 4; ++nb) h1[nb] = bias_block(lbo + 32 * nb, h);
-    gemm_slot<false, true>(h1[0], h1[1], ring.slot(base), xp, ring, job(2));
-    SAVAD_ROW_GEMM(1, h1[2], h1[3], xp)
+        for (int nb = 0; nb < 4; ++nb) {
+            h1[nb] = bias_block(lbo + 32 * nb, h) + hc[nb];
 #pragma unroll
-    for (int nb = 0; nb < 4; ++nb) h1[nb] += hres[nb];
+            for (int r = 0; r < 16; ++r) h1[nb][r] += hr[4 * nb + (r >> 2)][r & 3];
+        }
+    } else {
+        ring.issue_all(job(0));
+        ring.issue_all(job(1));
+        // the residual block is requested here and added BEHIND the out-projection's MFMAs: its round trip to memory hides under them
+        // ---- h1 = h + (bo + ctx Wo^T)
+        ring.acquire<1>();
+        f32x16 hres[4];
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) hres[nb] = zero16();
+        if (live) load_hblock32(hres, hb, lane);
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) h1[nb] = bias_block(lbo + 32 * nb, h);
+        gemm_slot<false, true>(h1[0], h1[1], ring.slot(base), xp, ring, job(2));
+        SAVAD_ROW_GEMM(1, h1[2], h1[3], xp)
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) h1[nb] += hres[nb];
+    }
     SAVAD_STAMP(5);
     f32x4 xg[16];
     layernorm_regs(h1, xg);
@@ -734,8 +801,8 @@ __device__ __forceinline__ void row_stage_f32s(const RowArgs3& A, char* smem, Tr
     {                                                                                                                         \
         f32x16 a[4];                                                                                                          \
         _Pragma("unroll") for (int nbl = 0; nbl < 4; ++nbl) a[nbl] = bias_block(lb1 + 128 * (ch) + 32 * nbl, h);              \
-        SAVAD_ROW_GEMM(2 + 4 * (ch), a[0], a[1], xp)                                                                          \
-        SAVAD_ROW_GEMM(3 + 4 * (ch), a[2], a[3], xp)                                                                          \
+        SAVAD_ROW_GEMM(OFF + 4 * (ch), a[0], a[1], xp)                                                                        \
+        SAVAD_ROW_GEMM(OFF + 1 + 4 * (ch), a[2], a[3], xp)                                                                          \
         if ((ch) == 0) SAVAD_STAMP(20);                                                                                       \
         Tri ap[8];                                                                                                            \
         _Pragma("unroll") for (int nbl = 0; nbl < 4; ++nbl) {                                                                 \
@@ -744,8 +811,8 @@ __device__ __forceinline__ void row_stage_f32s(const RowArgs3& A, char* smem, Tr
             ap[2 * nbl + 1] = split_half(a[nbl], 1);                                                                          \
         }                                                                                                                     \
         if ((ch) == 0) SAVAD_STAMP(21);                                                                                       \
-        SAVAD_ROW_GEMM(4 + 4 * (ch), o[0], o[1], ap)                                                                          \
-        SAVAD_ROW_GEMM(5 + 4 * (ch), o[2], o[3], ap)                                                                          \
+        SAVAD_ROW_GEMM(OFF + 2 + 4 * (ch), o[0], o[1], ap)                                                                    \
+        SAVAD_ROW_GEMM(OFF + 3 + 4 * (ch), o[2], o[3], ap)                                                                          \
         SAVAD_STAMP(7 + (ch));                                                                                                \
     }
     SAVAD_ROW_FFN(0) SAVAD_ROW_FFN(1) SAVAD_ROW_FFN(2) SAVAD_ROW_FFN(3)
@@ -757,9 +824,9 @@ __device__ __forceinline__ void row_stage_f32s(const RowArgs3& A, char* smem, Tr
         split_row(xg, xp);
         SAVAD_STAMP(11);
 #define SAVAD_ROW_QKV(S_)                                                                                                     \
-    ring.acquire<(18 + (S_) + 1 < NSLOT) ? 1 : 0>();                                                                          \
-    qkv_slot<S_, (18 + (S_) + 2 < NSLOT)>(ring.slot(base + 18 + (S_)), xp, lbn, A.qf, A.kf, A.vtf, blk, ring,                 \
-                                          18 + (S_) + 2 < NSLOT ? job(18 + (S_) + 2) : none, A.qscale, live);                 \
+    ring.acquire<(OFF + 16 + (S_) + 1 < NSLOT) ? 1 : 0>();                                                                    \
+    qkv_slot<S_, (OFF + 16 + (S_) + 2 < NSLOT)>(ring.slot(base + OFF + 16 + (S_)), xp, lbn, A.qf, A.kf, A.vtf, blk, ring,     \
+                                                OFF + 16 + (S_) + 2 < NSLOT ? job(OFF + 16 + (S_) + 2) : none, A.qscale, live); \
     SAVAD_STAMP(12 + (S_));
         SAVAD_ROW_QKV(0) SAVAD_ROW_QKV(1) SAVAD_ROW_QKV(2) SAVAD_ROW_QKV(3) SAVAD_ROW_QKV(4) SAVAD_ROW_QKV(5)
 #undef SAVAD_ROW_QKV
@@ -806,6 +873,9 @@ __global__ __launch_bounds__(256, 1) void attention_row_kernel_f32s(const char* 
     Tri qp[8];
     int blk_q, base = 0;
     bool active, qvalid;
+    f32x4 hr[16];   // !PACKED: the wave's residual block (a wave without a block: zeros)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) hr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     SAVAD_STAMP(0);
 #ifdef SAVAD_TIMING
     if (threadIdx.x == 0 && blockIdx.x < 1024) {
@@ -853,7 +923,7 @@ __global__ __launch_bounds__(256, 1) void attention_row_kernel_f32s(const char* 
                 const int uv = u < 0 ? 0 : u, uk = u + 1 < QB ? u + 1 : QB - 1;
                 return ring.job(u + 3, vtf + (kb + uv) * BLK3_BYTES, kf + (kb + uk) * BLK3_BYTES);
             }
-            return ring.job(u, row_seg(A, u - QB, 0), row_seg(A, u - QB, 1));
+            return ring.job(u, row_seg(A, u - QB, 0, true), row_seg(A, u - QB, 1, true));
         };
         ring.issue_all(job(-1));   // K(0) first: the prologue's scores wait for it
 #pragma unroll
@@ -884,6 +954,9 @@ __global__ __launch_bounds__(256, 1) void attention_row_kernel_f32s(const char* 
             ring.acquire<1>();
             attn_step3<true, true>(st, qp, sc, ring.slot(QB - 2), tail_mask, ring, job(QB));        // -> the last tile's scores, masked
             ring.acquire<1>();
+            // the residual block is requested in front of the last key tile: its round trip to memory hides under that tile's MFMAs, and
+            // the ring wait at the head of the row chain covers it (request_hblock32)
+            request_hblock32(hr, A.hbuf + (size_t)blk_q * (32 * D), lane);
             attn_step3<false, true>(st, qp, sc, ring.slot(QB - 1), no_mask, ring, job(QB + 1));
             SAVAD_STAMP(3);
         } else {  // a wave without a query block still moves its share of the stream and meets the others at every barrier
@@ -894,7 +967,9 @@ __global__ __launch_bounds__(256, 1) void attention_row_kernel_f32s(const char* 
             }
         }
     }
-    // normalised context -> B-operand triples, in registers (invalid slots and waves without a block: exact zeros)
+    // normalised context (invalid slots and waves without a block: exact zeros).  PACKED: -> B-operand triples of the out-projection, in
+    // registers.  !PACKED: V was projected with Wo Wv', so this IS the out-projected context, and the row chain starts by adding the
+    // residual block to it.
     Tri xp[8];
     {
         const float inv = qvalid ? 1.0f / half_sum(st.l_run) : 0.0f;
@@ -902,12 +977,14 @@ __global__ __launch_bounds__(256, 1) void attention_row_kernel_f32s(const char* 
         for (int nbd = 0; nbd < 4; ++nbd) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) st.O[nbd][r] = qvalid ? st.O[nbd][r] * inv : 0.0f;
-            xp[2 * nbd] = split_half(st.O[nbd], 0);
-            xp[2 * nbd + 1] = split_half(st.O[nbd], 1);
+            if constexpr (PACKED) {
+                xp[2 * nbd] = split_half(st.O[nbd], 0);
+                xp[2 * nbd + 1] = split_half(st.O[nbd], 1);
+            }
         }
     }
     SAVAD_STAMP(4);
-    row_stage_f32s<LAST, !PACKED>(A, smem, xp, blk_q, active, ring, base);
+    row_stage_f32s<LAST, !PACKED>(A, smem, xp, st.O, hr, blk_q, active, ring, base);
     SAVAD_STAMP(18);
 #ifdef SAVAD_TIMING
     if (threadIdx.x == 0 && blockIdx.x < 1024) {
