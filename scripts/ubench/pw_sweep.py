@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """attention stage per layer, first-generation kernel (row_mode 1) against the persistent one (row_mode 5), over batch sizes and
-lengths: where should automatic pick the persistent kernel (savad.hip, pw_pays)?   python scripts/ubench/pw_sweep.py"""
+lengths: where should automatic pick the persistent kernel (savad_schedule.h, pw_pays)?   python scripts/ubench/pw_sweep.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

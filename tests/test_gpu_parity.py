@@ -1636,7 +1636,7 @@ def test_config4_one_hour_stream_full_size(torch_cuda, model, state1234, precisi
         if precision != "bf16":
             assert torch.equal(other, p)  # a window's result does not depend on its batch slot or on the chunking
         else:
-            # bf16: automatic picks the persistent attention kernel or the first-generation one by batch size (savad.hip, pw_pays);
+            # bf16: automatic picks the persistent attention kernel or the first-generation one by batch size (savad_schedule.h, pw_pays);
             # the two agree bit for bit except in how a sequence's last 32 frames are summed (key-split tail item).  So: with
             # either kernel forced, the same bits whatever the chunking; across the two, the bf16 rounding of those frames.
             forced = {}

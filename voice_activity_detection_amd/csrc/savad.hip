@@ -1,6 +1,8 @@
 // savad.hip -- host side of libsavad.so: the C ABI declared in include/savad.h.
-// Owns the packed weights, the positional-encoding cache, and the 7-launch forward schedule:
+// Owns the packed weights and the positional-encoding cache, and launches what savad_schedule.h plans for a forward: one of four
+// kernel families (generic, fp32, bf16, fp32s), each as a single launch for the whole forward (T <= 32), or as
 //   input_qkv -> [attention(l) -> row(l)] x L      (row(L-1) ends in classifier + log-softmax)
+// with attention and row chain of a layer in one launch (fused) or in two.
 #include "savad_kernels.h"
 #include "savad_kernels_bf16.h"
 #include "savad_attn_pw_bf16.h"
@@ -12,6 +14,7 @@
 #include "savad_frontend.h"
 #include "savad_ingest.h"
 #include "savad_post.h"
+#include "savad_schedule.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -71,7 +74,7 @@ struct savad_model {
     int pe_len = 0;
     std::vector<float> h_pe;
     int splits = 0;
-    int row_mode = 0;  // 0 auto, 1 N-split (32-row tiles), 2 M-split (128-row tiles)
+    int row_mode = 0;  // savad_set_row_mode: 0 automatic, 1 - 8 pin a form or variant of the precision's kernel family (include/savad.h; savad_schedule.h)
     bool batch_invariant = false;   // bf16: the persistent attention kernel without key-split tail items (savad_set_batch_invariant)
     int precision = 0;  // 0 = fp32 MFMA, 1 = bf16 MFMA operands (fp32 accumulate / statistics / residual stream),
                         // 2 = "fp32s": fp32 parity on the bf16 pipe, every operand as three bf16 pieces (savad_kernels_f32s.h)
@@ -128,89 +131,30 @@ size_t add_param(savad_model* m, const std::string& key, size_t numel) {
     return off;
 }
 
-int choose_splits(const savad_model* m, int B, int T) {
-    if (T <= 32) return 1;
-    const int NT = (T + 31) / 32, QB = NT;
-    if (m->splits > 0) return m->splits < NT ? m->splits : NT;
-    // Work quantisation model (MFMA-bound): a workgroup puts one wave on each SIMD of a CU, so a
-    // CU that receives n workgroups needs n * ceil(NT/S) tile-times whether or not they are
-    // co-resident; prologue + epilogue + partial write/re-read cost about 1.5 tile-times per
-    // workgroup.  Measured at B=32, T=800: S=1 120 us, S=2 119 us (+4 us in the row kernel), S=5
-    // 121 us (+25 us): splitting only pays when it fills idle CUs (small batches).
-    auto cost = [&](int S) {
-        const long wgs = (long)B * ((QB + 3) / 4) * S;
-        return (double)((wgs + 255) / 256) * ((NT + S - 1) / S + 1.5);
-    };
-    const double cost1 = cost(1);
-    double best = cost1;
-    int bestS = 1;
-    for (int S = 2; S <= 8 && S <= NT; ++S) {
-        const double cs = cost(S);
-        if (cs < 0.93 * cost1 && cs < best) {
-            best = cs;
-            bestS = S;
-        }
-    }
-    return bestS;
+// the kernel headers' sizes as savad_schedule.h restates them
+static_assert(sched::D == D && sched::TILE == TILE && sched::F32_MAX_LAYERS == PACKED_MAX_LAYERS, "savad_schedule.h: savad_kernels.h sizes");
+static_assert(sched::BF_BLK_BYTES == bf::BLK_BYTES && sched::BF_HBLK_FLOATS == bf::HBLK_FLOATS && sched::BF_HRES_BYTES == sizeof(bf::hres_t) &&
+                  sched::BF16_MAX_LAYERS == bf::PACKED_BF16_MAX_LAYERS && sched::PW_GRID == bf::PW_GRID, "savad_schedule.h: bf16 sizes");
+static_assert(sched::FS_BLK3_BYTES == fs::BLK3_BYTES && sched::FS_HBLK_BYTES == fs::HBLK_BYTES && sched::F32S_MAX_LAYERS == fs::PACKED_F32S_MAX_LAYERS,
+              "savad_schedule.h: fp32s sizes");
+static_assert(sched::GEN_SCORE_CAP == gen::SCORE_CAP, "savad_schedule.h: savad_generic.h sizes");
+
+sched::Knobs knobs_of(const savad_model* m) {
+    sched::Knobs k;
+    k.precision = m->precision;
+    k.row_mode = m->row_mode;
+    k.splits = m->splits;
+    k.batch_invariant = m->batch_invariant;
+    k.n_cu = m->n_cu;
+    k.num_layers = m->cfg.num_layers;
+    k.feature_size = m->cfg.feature_size;
+    k.FP = m->FP;
+    k.generic = m->generic;
+    k.d_model = m->cfg.d_model;
+    return k;
 }
 
-struct Workspace {
-    size_t rows, rows_pad;
-    int S;
-    bool msplit;  // row-wise stages on 128-row tiles with the weight stream shared through LDS
-    bool fused;   // attention + row chain in one launch per layer (q/k/v double-buffered: q2, k2, v2)
-    size_t h, q, k, v, q2, k2, v2, opart, ml, xpad, total;  // float offsets
-};
-
-Workspace plan(const savad_model* m, int B, int T) {
-    Workspace w;
-    w.rows = (size_t)B * T;
-    w.rows_pad = (w.rows + 127) / 128 * 128;  // whole 128-row tiles (M-split kernels); also a multiple of TILE
-    w.S = choose_splits(m, B, T);
-    // Row-wise stages: 128-row tiles with the weight stream shared through LDS (M split) when that
-    // fills the chip; 32-row tiles with the output features split over the 4 waves (N split) when
-    // the batch is small and the critical path per workgroup matters more than weight traffic.
-    // N-split works through ceil(tiles / 256) rounds of ~45 us, M-split through one round of ~118 us per 256 workgroups
-    // of 128 rows: M wins from the third N-split round on (more than 512 tiles of 32 rows).  Measured at T=800: B=20
-    // (500 tiles) N 0.504 / M 0.648 ms; B=24 (600 tiles) N 0.611 / M 0.589 ms.
-    const int row_mode = m->row_mode == 4 ? 0 : m->row_mode;  // 4 only differs from automatic for T <= 32 (savad_forward)
-    w.msplit = row_mode == 2 || row_mode == 3 || (row_mode == 0 && w.rows_pad / 32 > 512);
-    // In the M-split regime without key splits the attention stage and the row chain of a query-block group
-    // run back to back in one workgroup (attention_row_kernel).  row_mode 2 keeps them as separate launches.
-    // Automatic: only when a query-block group keeps at least 80 % of its 4 wave slots busy -- waves without a
-    // query block sit out the whole row chain (measured: T=50, two blocks per group, B=512: 0.63 ms fused against
-    // 0.42 ms separate; T=200 (7 blocks in 2 groups) 0.434 / 0.453; T=400 (13 in 4) 0.508 / 0.524; T=800 (25 in
-    // 7) 0.640 / 0.668).
-    const int QBp = (T + 31) / 32, NGp = (QBp + 3) / 4;
-    const bool ragged = QBp * 5 < NGp * 4 * 4;  // QB / (4 NG) < 0.8
-    w.fused = w.msplit && T > 32 && w.S == 1 && (row_mode == 3 || (row_mode != 2 && !ragged));
-    size_t off = 0;
-    w.h = off;
-    off += w.rows_pad * D;
-    w.q = off;
-    off += (w.rows_pad + TILE) * D;  // +32 rows of slack: key/value tiles may over-read the last block
-    w.k = off;
-    off += (w.rows_pad + TILE) * D;
-    w.v = off;
-    off += (w.rows_pad + TILE) * D;
-    w.q2 = w.k2 = w.v2 = off;
-    if (w.fused) {
-        w.q2 = off;
-        off += (w.rows_pad + TILE) * D;
-        w.k2 = off;
-        off += (w.rows_pad + TILE) * D;
-        w.v2 = off;
-        off += (w.rows_pad + TILE) * D;
-    }
-    w.opart = off;
-    off += (size_t)w.S * w.rows_pad * D;
-    w.ml = off;
-    off += (size_t)w.S * w.rows_pad * 2;
-    w.xpad = off;
-    if (m->FP != m->cfg.feature_size) off += w.rows * (size_t)m->FP;  // zero-padded features
-    w.total = off;
-    return w;
-}
+float qscale() { return (float)(1.4426950408889634 / sqrt((double)D)); }  // log2(e) / sqrt(d_head): the softmax runs on exp2
 
 // a3: vad/modeling/transformer.py:403-414 (fp32 semantics), pre-divided by sqrt(D) (:389,401)
 void build_pe(std::vector<float>& pe, int T) {
@@ -313,9 +257,8 @@ int pack_frags(savad_model* m, hipStream_t st, const float* W, int N, int K, siz
 
 int prepare_frags(savad_model* m, hipStream_t st) {
     if (!m->frag_dirty) return SAVAD_OK;
-    const int F = m->cfg.feature_size, L = m->cfg.num_layers;
+    const int L = m->cfg.num_layers;
     int rc;
-    (void)F;
     if ((rc = pack_frags(m, st, win_fp32(m), D, m->FP, m->f_win))) return rc;
     for (int l = 0; l < L; ++l) {
         if ((rc = pack_frags(m, st, m->d_packed + m->lp[l].wqkv, 3 * D, D, m->lf[l].wqkv))) return rc;
@@ -327,117 +270,6 @@ int prepare_frags(savad_model* m, hipStream_t st) {
     return SAVAD_OK;
 }
 
-// block space of the bf16 path (savad_kernels_bf16.h)
-struct BlockPlan {
-    int nblk, nblk_pad;
-    bool fused;  // attention + row chain in one launch per layer (q/k/v^T double-buffered: q2, k2, vt2)
-    size_t h, q, k, vt, q2, k2, vt2, ctx, xpad, total;  // byte offsets
-};
-BlockPlan plan_blocks(const savad_model* m, int B, int T) {
-    BlockPlan p;
-    if (T > 32)
-        p.nblk = B * ((T + 31) / 32);
-    else
-        p.nblk = (B + (32 / T) - 1) / (32 / T);
-    p.nblk_pad = (p.nblk + 7) / 8 * 8;  // whole workgroups for both the 4- and the 8-wave kernels
-    size_t off = 0;
-    p.h = off;
-    off += (size_t)p.nblk_pad * bf::HBLK_FLOATS * sizeof(bf::hres_t);
-    const size_t fb = (size_t)(p.nblk_pad + 1) * bf::BLK_BYTES;  // +1 block: a 2-block key stage may over-read
-    p.q = off;
-    off += fb;
-    p.k = off;
-    off += fb;
-    p.vt = off;
-    off += fb;
-    p.ctx = off;
-    off += fb;
-    // row_mode 1 / 2 keep attention and row chain as separate launches (4- / 8-wave workgroups), 3 fuses them.
-    // Automatic: fused up to ~4 workgroups per CU.  Measured on MI355X at T=800 (fused vs separate, ms per
-    // forward): B=32 0.128 / 0.142, B=64 0.197 / 0.204, B=128 0.355 / 0.370, B=192 0.509 / 0.501, B=256 0.642 /
-    // 0.641 -- with more work per CU the wave slots a ragged query-block group leaves idle (3 of 28 at T=800) cost
-    // the row chain as much as the context round trip and the extra launches cost the separate form.
-    const int QBp = (T + 31) / 32, NGp = (QBp + 3) / 4;
-    const long groups = T > 32 ? (long)B * NGp : 0;
-    const bool ragged = QBp * 5 < NGp * 4 * 4;  // fewer than 80 % of a group's wave slots hold a query block
-    // (below one workgroup per CU the forward is launch / latency bound and fusing wins even with idle slots:
-    // B=64, T=50: 0.070 / 0.074 ms; B=32, T=160: 0.072 / 0.080 ms)
-    const bool automatic = m->row_mode == 0 || m->row_mode == 4;
-    p.fused = T > 32 && (m->row_mode == 3 || (automatic && groups <= 1024 && (!ragged || groups <= 256)));
-    p.q2 = p.k2 = p.vt2 = off;
-    if (p.fused) {
-        p.q2 = off;
-        off += fb;
-        p.k2 = off;
-        off += fb;
-        p.vt2 = off;
-        off += fb;
-    }
-    p.xpad = off;
-    if (m->FP != m->cfg.feature_size) off += (size_t)B * T * m->FP * sizeof(float);
-    p.total = off;
-    return p;
-}
-
-// block space of the fp32s path (savad_kernels_f32s.h): fp32 residual blocks, Q / K / V^T as triples, double-buffered between
-// layers (the fused launch of layer l writes layer l + 1's Q / K / V^T while other workgroups still read layer l's)
-struct BlockPlan3 {
-    int nblk, nblk_pad;
-    size_t h, q, k, vt, q2, k2, vt2, xpad, total;  // byte offsets
-};
-BlockPlan3 plan_blocks3(const savad_model* m, int B, int T) {
-    BlockPlan3 p;
-    if (T > 32)
-        p.nblk = B * ((T + 31) / 32);
-    else
-        p.nblk = (B + (32 / T) - 1) / (32 / T);
-    p.nblk_pad = (p.nblk + 3) / 4 * 4;
-    size_t off = 0;
-    p.h = off;
-    off += (size_t)p.nblk_pad * fs::HBLK_BYTES;
-    const size_t fb = (size_t)p.nblk_pad * fs::BLK3_BYTES;
-    size_t* slots[6] = {&p.q, &p.k, &p.vt, &p.q2, &p.k2, &p.vt2};
-    for (size_t* s : slots) {
-        *s = off;
-        off += fb;
-    }
-    p.xpad = off;
-    if (m->FP != m->cfg.feature_size) off += (size_t)B * T * m->FP * sizeof(float);
-    p.total = off;
-    return p;
-}
-
-// T <= 32 in precision 2: ONE launch for the whole forward -- the latency variant (one packed block per workgroup, its four waves
-// splitting every GEMM's output features; round 6) while the blocks fill the CUs at most SAVAD_F32S_NS_MAX_ROUNDS times, the
-// wave-per-block kernel (four blocks per workgroup share the weight stream through the LDS ring; a block's chain is 7 320 bf16 MFMAs)
-// beyond.  (Until the latency variant existed, short clips ran the exact-fp32 kernels of precision 0: SAVAD_F32S_PACKED_MIN_BLOCKS.)
-#ifndef SAVAD_F32S_PACKED_MIN_BLOCKS
-#define SAVAD_F32S_PACKED_MIN_BLOCKS 0
-#endif
-bool packed_f32s_applies(const savad_model* m, int B, int T) {
-    // row_mode 0 (automatic) and 4: the single launch in the variant the number of blocks suggests (launch_packed_forward_f32s);
-    // 5 - 7: the wave-per-block variant, 8: the latency variant (one block per workgroup); 1 - 3 keep the per-layer launches
-    // (the cross-check of the tests).  SAVAD_F32S_PACKED_MIN_BLOCKS > 0 (experiment builds): exact-fp32 kernels below that many blocks
-    if (T > 32 || m->cfg.num_layers > fs::PACKED_F32S_MAX_LAYERS) return false;
-    const long nblk = ((long)B + 32 / T - 1) / (32 / T);
-    return m->row_mode >= 4 || (m->row_mode == 0 && nblk >= SAVAD_F32S_PACKED_MIN_BLOCKS);
-}
-// precision 2 shapes that run the exact-fp32 kernels under the automatic schedule ("fp32s" promises the fp32 result at the best speed
-// the library has, not a particular instruction): sequences longer than 32 frames in batches of at most SAVAD_F32S_MIN_BLOCKS_PER_CU
-// 32-row blocks per CU.  There a forward's time is the latency of ONE block's chain, and the exact-fp32 kernels split a block's
-// GEMMs over the four waves of a workgroup where the fp32s fused launch gives a block to one wave: same-box sweep
-// (scripts/ubench/f32s_vs_f32_sweep.py, us, exact fp32 / fp32s): [1,800] 208 / 295, [8,800] 253 / 300, [12,800] 371 / 301,
-// [2,3200] 403 / 668, [4,3200] 747 / 673, [64,100] 187 / 203, [24,400] 340 / 246 -- the crossing sits at one block per CU for every T.
-// Any non-zero row_mode keeps the fp32s kernels (3: its fused launches at every size -- the tests' way to reach them, and the way
-// to results that do not depend on the batch a sequence arrives in: the two kernel families agree to fp32 rounding, not bit for bit).
-#ifndef SAVAD_F32S_MIN_BLOCKS_PER_CU
-#define SAVAD_F32S_MIN_BLOCKS_PER_CU 1
-#endif
-bool f32s_uses_exact_fp32(const savad_model* m, int B, int T) {
-    if (m->row_mode != 0) return false;
-    if (T <= 32) return !packed_f32s_applies(m, B, T);
-    return (long)B * ((T + 31) / 32) <= (long)SAVAD_F32S_MIN_BLOCKS_PER_CU * m->n_cu;
-}
 int pack_frags3(savad_model* m, hipStream_t st, const float* W, int N, int K, size_t off) {
     const size_t total = (size_t)N * K;
     const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
@@ -583,17 +415,11 @@ void launch_linear(hipStream_t st, const float* x, long rows, int K, const float
 }
 
 // SelfAttentiveVAD.forward for any d_model, the reference's operation sequence (vad/models/self_attention.py:23-28) kernel by kernel
-int forward_generic(savad_model* m, const float* x, int B, int T, float* out, void* workspace, size_t workspace_bytes, hipStream_t st) {
+int forward_generic(savad_model* m, const sched::ForwardPlan& p, const float* x, int B, int T, float* out, void* workspace, hipStream_t st) {
     const int Dm = m->cfg.d_model, F = m->cfg.feature_size, L = m->cfg.num_layers;
-    const gen::Plan p = gen::plan(B, T, Dm, m->splits);
-    if (workspace_bytes < p.total * sizeof(float))
-        return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total * sizeof(float));
-    for (const Param& q : m->params)
-        if (!q.set) return fail(SAVAD_E_NOKEY, "missing key '%s' in state_dict", q.key.c_str());
-    int rc;
-    if ((rc = ensure_pe(m, T, st))) return rc;
-    float* W = (float*)workspace;
-    float *h = W + p.h, *n = W + p.n, *q = W + p.q, *k = W + p.k, *v = W + p.v, *ctx = W + p.ctx, *ff = W + p.ff, *sc = W + p.scores;
+    char* W = (char*)workspace;
+    auto at = [W](size_t off) { return (float*)(W + off); };
+    float *h = at(p.h), *n = at(p.n), *q = at(p.q), *k = at(p.k), *v = at(p.v), *ctx = at(p.ctx), *ff = at(p.ff), *sc = at(p.scores);
     const float* R = m->d_raw;
     const long rows = (long)B * T;
     const int ln_grid = (int)((rows + 3) / 4);
@@ -842,16 +668,7 @@ SAVAD_EXPORT int savad_set_batch_invariant(savad_handle m, int on) {
 SAVAD_EXPORT int savad_workspace_bytes(savad_handle m, int B, int T, size_t* bytes) {
     if (!m || !bytes || B < 0 || T < 0) return fail(SAVAD_E_INVALID, "bad argument");
     if ((double)B * T * D >= 2.0e9) return fail(SAVAD_E_UNSUPPORTED, "B*T=%ld rows exceed the 32-bit tile index range", (long)B * T);
-    if (B == 0 || T == 0)
-        *bytes = 0;
-    else if (m->generic)
-        *bytes = gen::plan(B, T, m->cfg.d_model, m->splits).total * sizeof(float);
-    else if (m->precision == 1)
-        *bytes = plan_blocks(m, B, T).total;
-    else if (m->precision == 2)
-        *bytes = f32s_uses_exact_fp32(m, B, T) ? plan(m, B, T).total * sizeof(float) : plan_blocks3(m, B, T).total;
-    else
-        *bytes = plan(m, B, T).total * sizeof(float);
+    *bytes = sched::plan_forward(knobs_of(m), B, T, false, 0).total;
     return SAVAD_OK;
 }
 
@@ -861,8 +678,7 @@ SAVAD_EXPORT int savad_workspace_bytes(savad_handle m, int B, int T, size_t* byt
 // kernels' LDS limits), so that even the FIRST forward after it launches nothing but its own kernels and can be captured
 // into a HIP graph.  With parameters still missing only the table is sized (the forward reports the missing key).
 namespace {
-int prepare_bf16_launch(savad_model* m);
-int prepare_f32s_launch(savad_model* m);
+int ensure_ready(savad_model* m, int family, int T, hipStream_t st);
 }
 SAVAD_EXPORT int savad_reserve(savad_handle m, int T_max, void* stream) {
     if (!m || T_max < 0) return fail(SAVAD_E_INVALID, "bad argument");
@@ -874,16 +690,7 @@ SAVAD_EXPORT int savad_reserve(savad_handle m, int T_max, void* stream) {
     bool all_set = true;
     for (const Param& p : m->params) all_set = all_set && p.set;
     if (!all_set) return SAVAD_OK;
-    if ((rc = prepare_weights(m, st))) return rc;
-    if (m->precision == 1) {
-        if ((rc = prepare_frags(m, st))) return rc;
-        if ((rc = prepare_bf16_launch(m))) return rc;
-    }
-    if (m->precision == 2) {
-        if ((rc = prepare_frags3(m, st))) return rc;
-        if ((rc = prepare_f32s_launch(m))) return rc;
-    }
-    return SAVAD_OK;
+    return ensure_ready(m, m->precision == 1 ? sched::BF16 : m->precision == 2 ? sched::F32S : sched::F32, T_max, st);
 }
 
 // bf16 precision stores the residual stream between kernels as fp16 (+-65504); every element that had to be clamped is
@@ -911,9 +718,6 @@ SAVAD_EXPORT int savad_set_precision(savad_handle m, int precision) {
     return SAVAD_OK;
 }
 
-#ifndef SAVAD_INPUT_PERSISTENT
-#define SAVAD_INPUT_PERSISTENT 1   // 0: experiment builds that keep the ring form of the bf16 input stage everywhere (scripts/ubench/input_p_ab.py)
-#endif
 namespace {
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) for every bf16 kernel, once per handle
@@ -947,18 +751,36 @@ int prepare_bf16_launch(savad_model* m) {
     return SAVAD_OK;
 }
 
-// T <= 32 with bf16 operands: the whole forward in one launch (savad_packed_bf16.h); a wave per packed block, NW blocks per
-// workgroup.  Weights, fragments, the PE table and the kernels' LDS attributes must be ready.
-#ifndef SAVAD_NS_MAX_ROUNDS
-#define SAVAD_NS_MAX_ROUNDS 1   // blocks per CU up to which one block per workgroup beats four (scripts/ubench/packed_bf16_bench.py)
-#endif
-bool packed_bf16_applies(const savad_model* m, int T) {
-    // row_mode 0 (automatic) and 4: picked by the number of blocks; 5 - 7: a fixed variant (launch_packed_forward_bf16; tuning
-    // knobs at T <= 32, where the persistent attention kernel that 5 selects for long sequences does not exist); 1 - 3 keep
-    // the per-layer launches (the cross-check of the tests)
-    return T <= 32 && m->cfg.num_layers <= bf::PACKED_BF16_MAX_LAYERS && (m->row_mode == 0 || m->row_mode >= 4);
+int prepare_f32s_launch(savad_model* m);
+
+// Everything a forward of `family` reads besides its input: folded weights, the family's fragment images and LDS limits, and a
+// positional-encoding table of at least T rows.  Nothing is launched or allocated once it has run for the handle's current parameters.
+int ensure_ready(savad_model* m, int family, int T, hipStream_t st) {
+    int rc;
+    if (family == sched::GENERIC) {  // nothing to fold or pack: the generic kernels read the raw parameters
+        for (const Param& q : m->params)
+            if (!q.set) return fail(SAVAD_E_NOKEY, "missing key '%s' in state_dict", q.key.c_str());
+        return ensure_pe(m, T, st);
+    }
+    if ((rc = prepare_weights(m, st))) return rc;
+    if (family == sched::BF16 && (rc = prepare_frags(m, st))) return rc;
+    if (family == sched::F32S && (rc = prepare_frags3(m, st))) return rc;
+    if ((rc = ensure_pe(m, T, st))) return rc;
+    if (family == sched::BF16) return prepare_bf16_launch(m);
+    if (family == sched::F32S) return prepare_f32s_launch(m);
+    return SAVAD_OK;
 }
-void launch_packed_forward_bf16(savad_model* m, hipStream_t st, const float* x, int B, int T, int F, float* out, const WindowOffsets& wo,
+
+// zero-pad the features to the kernels' K granularity (fp32 copy)
+template <typename XT>
+void pad_features(hipStream_t st, const XT* x, size_t rows, int F, int FP, float* xp) {
+    const int grid = (int)((rows * FP + 255) / 256 < 4096 ? (rows * FP + 255) / 256 : 4096);
+    hipLaunchKernelGGL(pad_rows_kernel<XT>, dim3(grid), dim3(256), 0, st, x, rows, F, FP, xp);
+}
+
+// T <= 32 with bf16 operands: the whole forward in one launch (savad_packed_bf16.h); a wave per packed block, NW blocks per
+// workgroup, in the variant the plan names (sched::single_bf16_variant).  The handle must be ready (ensure_ready).
+void launch_packed_forward_bf16(savad_model* m, int variant, hipStream_t st, const float* x, int B, int T, int F, float* out, const WindowOffsets& wo,
                                 int win_base) {
     const int L = m->cfg.num_layers;
     const char* Fr = m->d_frag;
@@ -975,13 +797,8 @@ void launch_packed_forward_bf16(savad_model* m, hipStream_t st, const float* x, 
     pm.wc = m->d_packed + m->p_wc;
     pm.bc = m->d_packed + m->p_bc;
     pm.L = L;
-    const float c = (float)(1.4426950408889634 / sqrt((double)D));
+    const float c = qscale();
     const size_t bias_bytes = ((size_t)L * LBIAS + 2 * D + 4) * 4;   // every layer's biases + the classifier
-    // variant: row_mode 5 = 8-wave workgroups, 6 = 4 waves + 4 that move the weight stream through a 4-slot ring, 7 = 4 waves +
-    // 2 slots; automatic: 6 while the 4-block workgroups fill at most half of the CUs ([1000,7,80], 63 workgroups: 0.044 against 0.049 ms;
-    // [4000,7,80], 250 workgroups: 0.059 against 0.053; scripts/ubench/packed_bf16_bench.py)
-    // 8 = the latency variant: ONE block per workgroup, its four waves split the output features (savad_packed_bf16.h)
-    const int variant = m->row_mode >= 5 ? m->row_mode : (nblk <= SAVAD_NS_MAX_ROUNDS * m->n_cu ? 8 : ((nblk + 3) / 4 <= m->n_cu / 2 ? 6 : 7));
     const size_t ring2 = (size_t)2 * bf::RING_BYTES, ring4 = (size_t)4 * bf::RING_BYTES;
     if (variant == 8)
         hipLaunchKernelGGL(bf::packed_forward_kernel_bf16_ns, dim3(nblk), dim3(256), bf::ns_lds_bytes(L), st, x, B, T, F, nblk, pm, c, out, wo, win_base,
@@ -998,102 +815,53 @@ void launch_packed_forward_bf16(savad_model* m, hipStream_t st, const float* x, 
 }
 
 // bf16-operand forward: input_qkv -> [attention -> row] x L on fragment-major buffers
-int forward_bf16(savad_model* m, const void* x, int x_is_bf16, int B, int T, float* out, void* workspace,
-                 size_t workspace_bytes, hipStream_t st, long xbs_in = 0 /* elements between consecutive sequences of x; 0: T * F (savad_forward_strided) */) {
-    const BlockPlan bp = plan_blocks(m, B, T);
-    if (workspace_bytes < bp.total) return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, bp.total);
-    int rc;
-    if ((rc = prepare_weights(m, st))) return rc;
-    if ((rc = prepare_frags(m, st))) return rc;
-    if ((rc = ensure_pe(m, T, st))) return rc;
+int forward_bf16(savad_model* m, const sched::ForwardPlan& bp, const void* x, int x_is_bf16, int B, int T, long xbs_in, float* out,
+                 void* workspace, hipStream_t st) {
     char* W = (char*)workspace;
     bf::hres_t* hb = (bf::hres_t*)(W + bp.h);
-    char *qf = W + bp.q, *kf = W + bp.k, *vtf = W + bp.vt, *ctxf = W + bp.ctx;
+    char *qf = W + bp.q, *kf = W + bp.k, *vtf = W + bp.v, *ctxf = W + bp.ctx;
     const int L = m->cfg.num_layers;
     int F = m->cfg.feature_size;
-    if (m->FP != F) {  // zero-pad the features to the kernels' K granularity (fp32 copy)
+    if (bp.pad) {
         float* xp = (float*)(W + bp.xpad);
-        const size_t rows = (size_t)B * T;
-        const int grid = (int)((rows * m->FP + 255) / 256 < 4096 ? (rows * m->FP + 255) / 256 : 4096);
         if (x_is_bf16)
-            hipLaunchKernelGGL(pad_rows_kernel<__bf16>, dim3(grid), dim3(256), 0, st, (const __bf16*)x, rows, F, m->FP, xp);
+            pad_features(st, (const __bf16*)x, (size_t)B * T, F, m->FP, xp);
         else
-            hipLaunchKernelGGL(pad_rows_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, rows, F, m->FP, xp);
+            pad_features(st, (const float*)x, (size_t)B * T, F, m->FP, xp);
         x = xp;
         x_is_bf16 = 0;
         F = m->FP;
     }
-    if (xbs_in > 0 && (m->FP != m->cfg.feature_size || packed_bf16_applies(m, T))) return fail(SAVAD_E_UNSUPPORTED, "strided input: no kernel takes the stride for this shape");
     const long xbs = xbs_in > 0 ? xbs_in : (long)T * F;
-    const float c = (float)(1.4426950408889634 / sqrt((double)D));
+    const float c = qscale();
     const float* R = m->d_raw;
     const float* P = m->d_packed;
     const char* Fr = m->d_frag;
-    // 4-wave workgroups (two per CU, 2-slot ring) by default.  row_mode 2 selects the 8-wave variant with a
-    // 4-deep ring (half the DMA stream per data row, one workgroup per CU): measured SLOWER on MI355X at
-    // every size tried (B=256, T=800: 0.86 vs 0.75 ms), kept as a tuning knob and covered by the tests.
-    // row_mode 0 / 3 fuse attention and row chain per layer when T > 32 (plan_blocks); 1 / 2 keep them apart.
-    const bool wide = m->row_mode == 2;
-    if ((rc = prepare_bf16_launch(m))) return rc;
     Prof prof(m, st);
-    if (!x_is_bf16 && packed_bf16_applies(m, T)) {
+    if (bp.form == sched::SINGLE) {
         WindowOffsets none;
         none.w = 0;
-        launch_packed_forward_bf16(m, st, (const float*)x, B, T, F, out, none, 0);
+        launch_packed_forward_bf16(m, bp.variant, st, (const float*)x, B, T, F, out, none, 0);
         prof.mark("packed_forward_bf16");
         prof.done();
         HIP_TRY(hipGetLastError());
         return SAVAD_OK;
     }
-    const bool automatic_bf16 = m->row_mode == 0 || m->row_mode == 4;
-    // The persistent attention kernel (one 4 x 64-row workgroup per CU walking (sequence, 8 query blocks) items) against the
-    // first-generation one: a cost model of both, from the sweep scripts/ubench/pw_sweep.py (round 4, us per launch, first-generation /
-    // persistent): [96,800] 43.4 / 50.1, [128,800] 52.6 / 52.0, [160,800] 67.3 / 58.3, [192,800] 77.9 / 74.1, [224,800] 90.8 / 78.1,
-    // [256,800] 97.7 / 82.4, [512,800] 193.3 / 163.7, [256,1000] 143.7 / 117.7, [128,1600] 176.1 / 144.3, [64,3200] 333.9 / 284.5,
-    // [512,400] 65.3 / 63.8.  Persistent: the busiest workgroup's items (the cursor of scripts/gen_attn_pw.py restated: full groups
-    // with a stride of 32 per XCD, a sequence's tail group attached to one of them; a key-split tail costs 0.55 of a full item) times
-    // 0.62 us per key block + 7 us per item, + 5 us per launch.  First generation: 0.54 ns per (query block x key block) + 2.5 ns per
-    // query block, per sequence.  The persistent kernel is picked unless the model has it more than 5 % behind.
-    const bool ks_tail = !m->batch_invariant;   // key-split tail items (0.55 of a full item) or ordinary ones (a full item's time)
-    auto pw_pays = [ks_tail](int Bq, int Tq) {
-        const int QBq = (Tq + 31) / 32, NGFq = QBq >> 3, TQq = QBq & 7;
-        if (NGFq == 0) return false;
-        const int wg = bf::PW_GRID / 8;
-        auto ff1 = [](int x) { return __builtin_ctz((unsigned)x); };
-        const int t0 = ff1(NGFq) < ff1(wg) ? ff1(NGFq) : ff1(wg), sh = ff1(wg) - t0, mask = (1 << t0) - 1;
-        const int S = (Bq + 7) / 8;  // sequences of the fullest XCD
-        const double ctail = TQq == 0 ? 0.0 : (TQq <= 2 && ks_tail ? 0.55 : 1.0);
-        double busiest = 0.0;
-        for (int j = 0; j < wg; ++j) {
-            double n = 0.0;
-            for (long i = j; i / NGFq < S; i += wg) {
-                const int bi = (int)(i / NGFq), g = (int)(i % NGFq);
-                n += 1.0 + ((TQq && g == ((bi >> sh) & mask)) ? ctail : 0.0);
-            }
-            busiest = n > busiest ? n : busiest;
-        }
-        const double t_pw = busiest * (0.62 * QBq + 7.0) + 5.0;
-        const double t_first = (double)Bq * (5.4e-4 * QBq * QBq + 2.5e-3 * QBq);
-        return t_pw < 1.05 * t_first;   // (the busiest-workgroup figure errs on the high side when the last round is thin: [320,800] 106.6 measured, 119.7 priced)
-    };
+    const bool fused = bp.form == sched::FUSED;
     auto run = [&](auto nw_tag) {
         constexpr int NW = decltype(nw_tag)::value;
         constexpr int ring = bf::Ring<NW>::NRING * bf::RING_BYTES;
         const int grid_rows = bp.nblk_pad / NW;
         const dim3 wg(64 * NW);
-        // Persistent weights-resident form of the stage (input_qkv_kernel_bf16_p) in the automatic schedules and in 5, from one block per
-        // CU up (scripts/ubench/input_p_ab.py, us per launch ring / persistent, fp32 features at T = 800: B=16 19.4 / 17.1, 32 20.5 / 19.1,
-        // 64 22.4 / 22.7, 128 39.9 / 33.2, 256 79.6 / 64.9, 512 151.4 / 114.6; the same bits); row_mode 1 - 3 keep the ring kernel.
-        const int KSx = F / 16;
-        if (SAVAD_INPUT_PERSISTENT && (automatic_bf16 || m->row_mode == 5) && KSx >= 1 && KSx <= 15 && bp.nblk_pad >= m->n_cu) {
+        if (bp.input_p) {  // the persistent weights-resident form of the stage
             auto go = [&](auto xt, auto ks_tag) {
                 using XT = decltype(xt);
                 constexpr int KSC = decltype(ks_tag)::value;
-                hipLaunchKernelGGL((bf::input_qkv_kernel_bf16_p<XT, 8, KSC>), dim3(m->n_cu), dim3(512), bf::input_p_lds_bytes(KSx), st,
+                hipLaunchKernelGGL((bf::input_qkv_kernel_bf16_p<XT, 8, KSC>), dim3(m->n_cu), dim3(512), bf::input_p_lds_bytes(F / 16), st,
                                    (const XT*)x, xbs, B, T, F, bp.nblk, bp.nblk_pad, Fr + m->f_win, R + m->r_bin, m->d_pe,
                                    Fr + m->lf[0].wqkv, P + m->lp[0].bqkv, hb, qf, kf, vtf, c, m->d_sat);
             };
-            if (KSx == 5) {
+            if (bp.KSC == 5) {
                 if (x_is_bf16) go(__bf16{}, std::integral_constant<int, 5>{}); else go(float{}, std::integral_constant<int, 5>{});
             } else {
                 if (x_is_bf16) go(__bf16{}, std::integral_constant<int, 0>{}); else go(float{}, std::integral_constant<int, 0>{});
@@ -1107,14 +875,14 @@ int forward_bf16(savad_model* m, const void* x, int x_is_bf16, int B, int T, flo
                                T, F, bp.nblk, Fr + m->f_win, R + m->r_bin, m->d_pe, Fr + m->lf[0].wqkv, P + m->lp[0].bqkv, hb, qf,
                                kf, vtf, c, m->d_sat);
         prof.mark("input_qkv_bf16");
-        char* sets[2][3] = {{qf, kf, vtf}, {W + bp.q2, W + bp.k2, W + bp.vt2}};
+        char* sets[2][3] = {{qf, kf, vtf}, {W + bp.q2, W + bp.k2, W + bp.v2}};
         for (int l = 0; l < L; ++l) {
             const auto& r = m->lr[l];
             const auto& p = m->lp[l];
             const auto& f = m->lf[l];
             const bool last = l + 1 == L;
-            char** cur = bp.fused ? sets[l & 1] : sets[0];
-            char** nxt = bp.fused ? sets[(l + 1) & 1] : sets[0];
+            char** cur = fused ? sets[l & 1] : sets[0];
+            char** nxt = fused ? sets[(l + 1) & 1] : sets[0];
             bf::RowArgsBf16 A;
             A.B = B;
             A.T = T;
@@ -1135,29 +903,24 @@ int forward_bf16(savad_model* m, const void* x, int x_is_bf16, int B, int T, flo
             A.out = out;
             A.qscale = c;
             A.satcnt = m->d_sat;
-            if (bp.fused) {
-                const int QB = (T + 31) / 32, NG = (QB + NW - 1) / NW;
-                const dim3 grid(8 * (((long)B * NG + 7) / 8));
+            const dim3 grid_groups(8 * (((long)B * bp.NG + 7) / 8));  // a workgroup per query-block group, whole XCD rounds
+            if (fused) {
                 if (last)
-                    hipLaunchKernelGGL((bf::attention_row_kernel_bf16<true, NW>), grid, wg, ring + 9 * D * 4, st, cur[0], cur[1], cur[2], NG, A);
+                    hipLaunchKernelGGL((bf::attention_row_kernel_bf16<true, NW>), grid_groups, wg, ring + 9 * D * 4, st, cur[0], cur[1], cur[2], bp.NG, A);
                 else
-                    hipLaunchKernelGGL((bf::attention_row_kernel_bf16<false, NW>), grid, wg, ring + 9 * D * 4, st, cur[0], cur[1], cur[2], NG, A);
+                    hipLaunchKernelGGL((bf::attention_row_kernel_bf16<false, NW>), grid_groups, wg, ring + 9 * D * 4, st, cur[0], cur[1], cur[2], bp.NG, A);
                 prof.mark(last ? "attention_row_last_bf16" : "attention_row_bf16");
                 continue;
             }
-            if (T <= 32) {
+            if (bp.attn == sched::ATTN_PACKED)
                 hipLaunchKernelGGL(bf::attention_packed_kernel_bf16, dim3((bp.nblk + 3) / 4), dim3(256), 0, st, qf, kf, vtf, ctxf,
                                    B, T, bp.nblk);
-            } else if (m->row_mode == 5 || (automatic_bf16 && pw_pays(B, T))) {  // persistent 4 x 64-row attention (savad_attn_pw_bf16.h)
-                if (m->batch_invariant)
-                    hipLaunchKernelGGL(bf::attention_pw_kernel_bf16_nosplit, dim3(bf::PW_GRID), dim3(256), bf::PW_LDS_BYTES, st, qf, kf, vtf, ctxf, B, T);
-                else
-                    hipLaunchKernelGGL(bf::attention_pw_kernel_bf16, dim3(bf::PW_GRID), dim3(256), bf::PW_LDS_BYTES, st, qf, kf, vtf, ctxf, B, T);
-            } else {
-                const int QB = (T + 31) / 32, NG = (QB + NW - 1) / NW;
-                hipLaunchKernelGGL((bf::attention_kernel_bf16<NW>), dim3(8 * (((long)B * NG + 7) / 8)), wg, ring, st, qf, kf, vtf, ctxf, B,
-                                   T, NG);
-            }
+            else if (bp.attn == sched::ATTN_PW_NOSPLIT)  // persistent 4 x 64-row attention (savad_attn_pw_bf16.h)
+                hipLaunchKernelGGL(bf::attention_pw_kernel_bf16_nosplit, dim3(bf::PW_GRID), dim3(256), bf::PW_LDS_BYTES, st, qf, kf, vtf, ctxf, B, T);
+            else if (bp.attn == sched::ATTN_PW)
+                hipLaunchKernelGGL(bf::attention_pw_kernel_bf16, dim3(bf::PW_GRID), dim3(256), bf::PW_LDS_BYTES, st, qf, kf, vtf, ctxf, B, T);
+            else
+                hipLaunchKernelGGL((bf::attention_kernel_bf16<NW>), grid_groups, wg, ring, st, qf, kf, vtf, ctxf, B, T, bp.NG);
             prof.mark("attention_bf16");
             if (last)
                 hipLaunchKernelGGL((bf::row_kernel_bf16<true, NW>), dim3(grid_rows), wg, ring + 9 * D * 4, st, ctxf, A);
@@ -1166,7 +929,7 @@ int forward_bf16(savad_model* m, const void* x, int x_is_bf16, int B, int T, flo
             prof.mark(last ? "row_last_bf16" : "row_bf16");
         }
     };
-    if (wide)
+    if (bp.wide)
         run(std::integral_constant<int, 8>{});
     else
         run(std::integral_constant<int, 4>{});
@@ -1190,10 +953,8 @@ int prepare_f32s_launch(savad_model* m) {
     return SAVAD_OK;
 }
 
-#ifndef SAVAD_F32S_NS_MAX_ROUNDS
-#define SAVAD_F32S_NS_MAX_ROUNDS 2   // blocks per CU up to which one block per workgroup beats a wave per block (scripts/ubench/f32s_check_t7.py)
-#endif
-void launch_packed_forward_f32s(savad_model* m, hipStream_t st, const float* x, int B, int T, int F, float* out, const WindowOffsets& wo,
+// T <= 32 in precision 2: the whole forward in one launch, in the variant the plan names (sched::single_f32s_variant)
+void launch_packed_forward_f32s(savad_model* m, int variant, hipStream_t st, const float* x, int B, int T, int F, float* out, const WindowOffsets& wo,
                                 int win_base) {
     const int L = m->cfg.num_layers;
     const char* Fr = m->d_frag3;
@@ -1210,11 +971,8 @@ void launch_packed_forward_f32s(savad_model* m, hipStream_t st, const float* x, 
     pm.wc = m->d_packed + m->p_wc;
     pm.bc = m->d_packed + m->p_bc;
     pm.L = L;
-    const float c = (float)(1.4426950408889634 / sqrt((double)D));
-    // the latency variant (one block per workgroup, its four waves splitting the output features) up to SAVAD_F32S_NS_MAX_ROUNDS blocks
-    // per CU; beyond, a wave per block with the weight stream shared through the LDS ring
-    const bool ns = m->row_mode >= 5 ? m->row_mode == 8 : nblk <= SAVAD_F32S_NS_MAX_ROUNDS * m->n_cu;
-    if (ns)
+    const float c = qscale();
+    if (variant == sched::VARIANT_LATENCY)
         hipLaunchKernelGGL(fs::packed_forward_kernel_f32s_ns, dim3(nblk), dim3(256), fs::nsf_lds_bytes(L), st, x, B, T, F, nblk, pm, c, out, wo, win_base);
     else
         hipLaunchKernelGGL(fs::packed_forward_kernel_f32s, dim3((nblk + 3) / 4), dim3(256), fs::packed_f32s_lds_bytes(L), st, x, B, T, F, nblk, pm, c,
@@ -1222,53 +980,41 @@ void launch_packed_forward_f32s(savad_model* m, hipStream_t st, const float* x, 
 }
 
 // fp32s forward (precision 2): input_qkv -> [attention + row chain] x L, every GEMM as six bf16 MFMA products of three-piece operands
-int forward_f32s(savad_model* m, const float* x, int B, int T, float* out, void* workspace, size_t workspace_bytes, hipStream_t st,
-                 long xbs_in = 0 /* elements between consecutive sequences of x; 0: T * F (savad_forward_strided) */) {
-    const BlockPlan3 bp = plan_blocks3(m, B, T);
-    if (workspace_bytes < bp.total) return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, bp.total);
-    int rc;
-    if ((rc = prepare_weights(m, st))) return rc;
-    if ((rc = prepare_frags3(m, st))) return rc;
-    if ((rc = ensure_pe(m, T, st))) return rc;
-    if ((rc = prepare_f32s_launch(m))) return rc;
+int forward_f32s(savad_model* m, const sched::ForwardPlan& bp, const float* x, int B, int T, long xbs_in, float* out, void* workspace,
+                 hipStream_t st) {
     char* W = (char*)workspace;
     float* hb = (float*)(W + bp.h);
     const int L = m->cfg.num_layers;
     int F = m->cfg.feature_size;
-    if (m->FP != F) {  // zero-pad the features to the kernels' K granularity
+    if (bp.pad) {
         float* xp = (float*)(W + bp.xpad);
-        const size_t rows = (size_t)B * T;
-        const int grid = (int)((rows * m->FP + 255) / 256 < 4096 ? (rows * m->FP + 255) / 256 : 4096);
-        hipLaunchKernelGGL(pad_rows_kernel<float>, dim3(grid), dim3(256), 0, st, x, rows, F, m->FP, xp);
+        pad_features(st, x, (size_t)B * T, F, m->FP, xp);
         x = xp;
         F = m->FP;
     }
-    if (xbs_in > 0 && (m->FP != m->cfg.feature_size || T <= 32)) return fail(SAVAD_E_UNSUPPORTED, "strided input: no kernel takes the stride for this shape");
     const long xbs = xbs_in > 0 ? xbs_in : (long)T * F;
-    const float c = (float)(1.4426950408889634 / sqrt((double)D));
+    const float c = qscale();
     const float* R = m->d_raw;
     const float* P = m->d_packed;
     const char* Fr = m->d_frag3;
     Prof prof(m, st);
-    if (packed_f32s_applies(m, B, T)) {
+    if (bp.form == sched::SINGLE) {
         WindowOffsets none;
         none.w = 0;
-        launch_packed_forward_f32s(m, st, x, B, T, F, out, none, 0);
+        launch_packed_forward_f32s(m, bp.variant, st, x, B, T, F, out, none, 0);
         prof.mark("packed_forward_f32s");
         prof.done();
         HIP_TRY(hipGetLastError());
         return SAVAD_OK;
     }
-    char* sets[2][3] = {{W + bp.q, W + bp.k, W + bp.vt}, {W + bp.q2, W + bp.k2, W + bp.vt2}};
-    const bool packed = T <= 32;
-    // T > 32: V is projected with Wo Wv' (prepare_frags3), so that P V already is the out-projected context -- the fused launch's row
-    // chain has no out-projection.  The T <= 32 form of the launch keeps the plain images and its out-projection.
+    char* sets[2][3] = {{W + bp.q, W + bp.k, W + bp.v}, {W + bp.q2, W + bp.k2, W + bp.v2}};
+    const bool packed = !bp.fold_v;  // the T <= 32 form of the launch: the plain Q/K/V images and its own out-projection
     auto wqkv3 = [&](int l) { return Fr + (packed ? m->lf3[l].wqkv : m->lf3[l].wqkv_vo); };
     auto bqkv3 = [&](int l) { return P + (packed ? m->lp[l].bqkv : m->lp[l].bqkv_vo); };
     hipLaunchKernelGGL(fs::input_qkv_kernel_f32s, dim3(bp.nblk_pad / 4), dim3(256), fs::NRING3 * fs::SLOT_BYTES + 3 * D * 4, st, x, xbs, B, T, F,
                        bp.nblk, Fr + m->f3_win, R + m->r_bin, m->d_pe, wqkv3(0), bqkv3(0), hb, sets[0][0], sets[0][1], sets[0][2], c);
     prof.mark("input_qkv_f32s");
-    const int QB = (T + 31) / 32, NG = (QB + 3) / 4;
+    const int NG = bp.NG;
     const dim3 grid(packed ? bp.nblk_pad / 4 : 8 * (((long)B * NG + 7) / 8));
     for (int l = 0; l < L; ++l) {
         const auto& r = m->lr[l];
@@ -1319,7 +1065,7 @@ void launch_packed_forward(savad_model* m, hipStream_t st, const float* x, int B
     const int L = m->cfg.num_layers;
     const float* R = m->d_raw;
     const float* P = m->d_packed;
-    const float c = (float)(1.4426950408889634 / sqrt((double)D));  // log2(e) / sqrt(d_head)
+    const float c = qscale();
     const int G = 32 / T, nblk = (B + G - 1) / G;
     PackedModel pm;
     for (int l = 0; l < L; ++l) pm.layer[l] = PackedLayer{P + m->lp[l].frag};
@@ -1333,104 +1079,31 @@ void launch_packed_forward(savad_model* m, hipStream_t st, const float* x, int B
     pm.L = L;
     hipLaunchKernelGGL(packed_forward_kernel, dim3(nblk), dim3(256), 0, st, x, B * T, T, F, pm, c, out, G * T, wo, win_base);
 }
-}  // namespace
 
-// x_dtype: 0 = fp32 features, 1 = bf16 features (bf16 precision only)
-SAVAD_EXPORT int savad_forward_ex(savad_handle m, const void* x, int x_dtype, int B, int T, float* out, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-    if (!m) return fail(SAVAD_E_INVALID, "null handle");
-    if (x_dtype == 0 && m->precision != 1) return savad_forward(m, (const float*)x, B, T, out, workspace, workspace_bytes, stream);
-    if (x_dtype < 0 || x_dtype > 1) return fail(SAVAD_E_INVALID, "x_dtype %d", x_dtype);
-    if (m->generic) return fail(SAVAD_E_UNSUPPORTED, "bf16 features need the d_model=128 kernels (this handle: d_model=%d, fp32)", m->cfg.d_model);
-    if (m->precision != 1) return fail(SAVAD_E_UNSUPPORTED, "bf16 features need savad_set_precision(h, 1)");
-    if (B < 0 || T < 0) return fail(SAVAD_E_INVALID, "negative shape B=%d T=%d", B, T);
-    if (B == 0 || T == 0) return SAVAD_OK;
-    if (!x || !out || !workspace) return fail(SAVAD_E_INVALID, "null tensor pointer");
-    if ((double)B * T * D >= 2.0e9) return fail(SAVAD_E_UNSUPPORTED, "B*T too large");
-    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)workspace) & 15)
-        return fail(SAVAD_E_INVALID, "x, out and workspace must be 16-byte aligned");
-    return forward_bf16(m, x, x_dtype, B, T, out, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-int forward_any(savad_handle m, const void* xv, int x_dtype, int B, int T, long xbs_in, float* out, void* workspace, size_t workspace_bytes,
-                void* stream);
-SAVAD_EXPORT int savad_forward_strided(savad_handle m, const void* x, int x_dtype, int B, int T, long x_batch_stride, float* out,
-                                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (!m) return fail(SAVAD_E_INVALID, "null handle");
-    if (m->generic) return fail(SAVAD_E_UNSUPPORTED, "strided input needs the d_model=128 kernels");
-    if (T <= 32) return fail(SAVAD_E_UNSUPPORTED, "strided input is for sequences longer than 32 frames (windows of T <= 32 are read in place by savad_predict_probabilities)");
-    if (m->FP != m->cfg.feature_size) return fail(SAVAD_E_UNSUPPORTED, "strided input needs feature_size %% 16 == 0 (no padding copy)");
-    const long F = m->cfg.feature_size;
-    if (x_batch_stride <= 0 || x_batch_stride % 4 || x_batch_stride % F)
-        return fail(SAVAD_E_INVALID, "x_batch_stride=%ld (a positive multiple of feature_size and of 4 elements)", x_batch_stride);
-    if (x_dtype < 0 || x_dtype > 1 || (x_dtype == 1 && m->precision != 1)) return fail(SAVAD_E_INVALID, "x_dtype %d (bf16 features need savad_set_precision(h, 1))", x_dtype);
-    return forward_any(m, x, x_dtype, B, T, x_batch_stride, out, workspace, workspace_bytes, stream);
-}
-
-SAVAD_EXPORT int savad_forward(savad_handle m, const float* x, int B, int T, float* out, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-    return forward_any(m, x, 0, B, T, 0, out, workspace, workspace_bytes, stream);
-}
-
-// every forward entry point ends here.  xbs_in: elements between consecutive sequences of x (savad_forward_strided), 0 = T * F; it
-// travels as an ARGUMENT to the one kernel per precision that reads the features, and every path that cannot honour it refuses
-int forward_any(savad_handle m, const void* xv, int x_dtype, int B, int T, long xbs_in, float* out, void* workspace, size_t workspace_bytes,
-                void* stream) {
-    const float* x = (const float*)xv;
-    if (!m) return fail(SAVAD_E_INVALID, "null handle");
-    if (B < 0 || T < 0) return fail(SAVAD_E_INVALID, "negative shape B=%d T=%d", B, T);
-    if (B == 0 || T == 0) return SAVAD_OK;
-    if (!x || !out || !workspace) return fail(SAVAD_E_INVALID, "null tensor pointer");
-    if ((double)B * T * D >= 2.0e9) return fail(SAVAD_E_UNSUPPORTED, "B*T too large");
-    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)workspace) & 15)
-        return fail(SAVAD_E_INVALID, "x, out and workspace must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (m->generic) return xbs_in > 0 ? fail(SAVAD_E_UNSUPPORTED, "strided input needs the d_model=128 kernels") : forward_generic(m, x, B, T, out, workspace, workspace_bytes, st);
-    if (m->precision == 1) return forward_bf16(m, xv, x_dtype, B, T, out, workspace, workspace_bytes, st, xbs_in);
-    if (m->precision == 2 && !f32s_uses_exact_fp32(m, B, T)) return forward_f32s(m, x, B, T, out, workspace, workspace_bytes, st, xbs_in);
-    if (xbs_in > 0 && (m->FP != m->cfg.feature_size || T <= 32)) return fail(SAVAD_E_UNSUPPORTED, "strided input: no kernel takes the stride for this shape");
-    const Workspace ws = plan(m, B, T);
-    if (workspace_bytes < ws.total * sizeof(float))
-        return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, ws.total * sizeof(float));
-    int rc;
-    if ((rc = prepare_weights(m, st))) return rc;
-    if ((rc = ensure_pe(m, T, st))) return rc;
-
-    float* W = (float*)workspace;
-    float *hb = W + ws.h, *q = W + ws.q, *k = W + ws.k, *v = W + ws.v, *op = W + ws.opart, *ml = W + ws.ml;
+// exact-fp32 forward (precision 0, and the shapes precision 2 hands over): input_qkv -> [attention -> row] x L on row-major fp32 buffers
+int forward_f32(savad_model* m, const sched::ForwardPlan& ws, const float* x, int B, int T, long xbs_in, float* out, void* workspace,
+                hipStream_t st) {
+    char* W = (char*)workspace;
+    auto at = [W](size_t off) { return (float*)(W + off); };
+    float *hb = at(ws.h), *q = at(ws.q), *k = at(ws.k), *v = at(ws.v), *op = at(ws.opart), *ml = at(ws.ml);
     const int L = m->cfg.num_layers;
     int F = m->cfg.feature_size;
-    if (m->FP != F) {  // zero-pad the features to the kernels' K granularity
-        float* xp = W + ws.xpad;
-        const int grid = (int)((ws.rows * m->FP + 255) / 256 < 4096 ? (ws.rows * m->FP + 255) / 256 : 4096);
-        hipLaunchKernelGGL(pad_rows_kernel<float>, dim3(grid), dim3(256), 0, st, x, ws.rows, F, m->FP, xp);
+    if (ws.pad) {
+        float* xp = at(ws.xpad);
+        pad_features(st, x, ws.rows, F, m->FP, xp);
         x = xp;
         F = m->FP;
     }
     const long xbs = xbs_in > 0 ? xbs_in : (long)T * F;
     const int tiles = (int)(ws.rows_pad / TILE);
-    const float c = (float)(1.4426950408889634 / sqrt((double)D));  // log2(e) / sqrt(d_head)
+    const float c = qscale();
     const float* R = m->d_raw;
     const float* P = m->d_packed;
     Prof prof(m, st);
 
     const int tiles_m = (int)(ws.rows_pad / 128);
     const bool msplit = ws.msplit;
-    // T <= 32 in the small-batch regime (the reference pipeline's 7-frame windows): the whole forward is ONE launch,
-    // a workgroup per packed tile of floor(32/T) sequences keeps every activation on its CU (packed_forward_kernel).
-    // Automatic up to 1024 tiles (four rounds of the 256 CUs); beyond that the 128-row M-split tiles, which fetch the
-    // weight stream once per 128 rows instead of once per tile, are ahead.  Measured at T=7, ms per forward, single
-    // launch / per-layer N-split launches / M-split: 250 tiles 0.100 / 0.156 / 0.356; 512 tiles 0.186 / 0.272 / 0.364;
-    // 1024 tiles 0.366 / 0.506 / 0.383; 2048 tiles 0.728 / 0.878 / 0.699; 4096 tiles (the predictor's 16384-window
-    // batches) 1.454 / 1.736 / 1.346.  row_mode 4 forces the single launch for any T <= 32 batch.
-    // A packed tile holds floor(32/T)*T of 32 rows (28 at T=7, 20 at T=20, 17 at T=17): while the DENSE 32-row tiles of the
-    // per-layer N-split launches still fit fewer rounds of the CUs, those win (T=20, B=400: 400 packed / 250 dense tiles,
-    // 0.184 against 0.160 ms).  Round model fitted to scripts/ubench/policy_sweep.py: 92 us per round of packed tiles, 45 +
-    // 110 us per round of dense tiles.
-    const long tiles_packed = T <= 32 ? ((long)B + 32 / T - 1) / (32 / T) : 0, tiles_dense = ((long)B * T + 31) / 32;
-    const bool one_launch = tiles_packed <= 1024 &&
-                            (tiles_dense > 512 || 92 * ((tiles_packed + 255) / 256) <= 45 + 110 * ((tiles_dense + 255) / 256));
-    if (T <= 32 && L <= PACKED_MAX_LAYERS && (m->row_mode == 4 || (m->row_mode == 0 && one_launch))) {
+    if (ws.form == sched::SINGLE) {
         WindowOffsets none;
         none.w = 0;
         launch_packed_forward(m, st, x, B, T, F, out, none, 0);
@@ -1446,9 +1119,9 @@ int forward_any(savad_handle m, const void* xv, int x_dtype, int B, int T, long 
         hipLaunchKernelGGL(input_qkv_kernel, dim3(tiles), dim3(256), 0, st, x, xbs, (int)ws.rows, T, F, win_fp32(m),
                            R + m->r_bin, m->d_pe, P + m->lp[0].frag, P + m->lp[0].bqkv, hb, q, k, v);
     prof.mark("input_qkv");
-    if (ws.fused) {
-        float* qkv[2][3] = {{q, k, v}, {W + ws.q2, W + ws.k2, W + ws.v2}};
-        const int QB = (T + 31) / 32, NG = (QB + 3) / 4;
+    const int NG = ws.NG;
+    if (ws.form == sched::FUSED) {
+        float* qkv[2][3] = {{q, k, v}, {at(ws.q2), at(ws.k2), at(ws.v2)}};
         const int grid = (int)(8 * (((long)B * NG + 7) / 8));
         for (int l = 0; l < L; ++l) {
             const auto& r = m->lr[l];
@@ -1472,11 +1145,9 @@ int forward_any(savad_handle m, const void* xv, int x_dtype, int B, int T, long 
         return SAVAD_OK;
     }
     for (int l = 0; l < L; ++l) {
-        if (T <= 32) {
-            const int G = 32 / T, nblk = (B + G - 1) / G;
-            hipLaunchKernelGGL(attention_packed_kernel, dim3(nblk), dim3(64), 0, st, q, k, v, op, ml, B, T, (int)ws.rows, c);
+        if (ws.attn == sched::ATTN_PACKED) {
+            hipLaunchKernelGGL(attention_packed_kernel, dim3(ws.nblk), dim3(64), 0, st, q, k, v, op, ml, B, T, (int)ws.rows, c);
         } else {
-            const int QB = (T + 31) / 32, NG = (QB + 3) / 4;
             const int grid = (int)(8 * (((long)B * NG * ws.S + 7) / 8));
             hipLaunchKernelGGL(attention_kernel, dim3(grid), dim3(256), 0, st, q, k, v, op, ml, B, T, (int)ws.rows_pad,
                                ws.S, NG, c);
@@ -1509,6 +1180,62 @@ int forward_any(savad_handle m, const void* xv, int x_dtype, int B, int T, long 
     prof.done();
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
+}
+
+// every forward entry point ends here: validate, plan once (savad_schedule.h), make the family's weights ready, launch what the plan
+// names.  xbs_in: elements between consecutive sequences of x (savad_forward_strided), 0 = T * F
+int forward_any(savad_handle m, const void* xv, int x_dtype, int B, int T, long xbs_in, float* out, void* workspace, size_t workspace_bytes,
+                void* stream) {
+    const float* x = (const float*)xv;
+    if (!m) return fail(SAVAD_E_INVALID, "null handle");
+    if (B < 0 || T < 0) return fail(SAVAD_E_INVALID, "negative shape B=%d T=%d", B, T);
+    if (B == 0 || T == 0) return SAVAD_OK;
+    if (!x || !out || !workspace) return fail(SAVAD_E_INVALID, "null tensor pointer");
+    if ((double)B * T * D >= 2.0e9) return fail(SAVAD_E_UNSUPPORTED, "B*T too large");
+    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)workspace) & 15)
+        return fail(SAVAD_E_INVALID, "x, out and workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const sched::ForwardPlan p = sched::plan_forward(knobs_of(m), B, T, x_dtype == 1, xbs_in);
+    if (p.err) return fail(p.err, "%s", p.msg);
+    if (workspace_bytes < p.total) return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
+    int rc;
+    if ((rc = ensure_ready(m, p.family, T, st))) return rc;
+    switch (p.family) {
+        case sched::GENERIC: return forward_generic(m, p, x, B, T, out, workspace, st);
+        case sched::BF16: return forward_bf16(m, p, xv, x_dtype, B, T, xbs_in, out, workspace, st);
+        case sched::F32S: return forward_f32s(m, p, x, B, T, xbs_in, out, workspace, st);
+        default: return forward_f32(m, p, x, B, T, xbs_in, out, workspace, st);
+    }
+}
+}  // namespace
+
+// x_dtype: 0 = fp32 features, 1 = bf16 features (bf16 precision only)
+SAVAD_EXPORT int savad_forward_ex(savad_handle m, const void* x, int x_dtype, int B, int T, float* out, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    if (!m) return fail(SAVAD_E_INVALID, "null handle");
+    if (x_dtype == 0 && m->precision != 1) return savad_forward(m, (const float*)x, B, T, out, workspace, workspace_bytes, stream);
+    if (x_dtype < 0 || x_dtype > 1) return fail(SAVAD_E_INVALID, "x_dtype %d", x_dtype);
+    if (m->generic) return fail(SAVAD_E_UNSUPPORTED, "bf16 features need the d_model=128 kernels (this handle: d_model=%d, fp32)", m->cfg.d_model);
+    if (m->precision != 1) return fail(SAVAD_E_UNSUPPORTED, "bf16 features need savad_set_precision(h, 1)");
+    return forward_any(m, x, x_dtype, B, T, 0, out, workspace, workspace_bytes, stream);
+}
+
+SAVAD_EXPORT int savad_forward_strided(savad_handle m, const void* x, int x_dtype, int B, int T, long x_batch_stride, float* out,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (!m) return fail(SAVAD_E_INVALID, "null handle");
+    if (m->generic) return fail(SAVAD_E_UNSUPPORTED, "strided input needs the d_model=128 kernels");
+    if (T <= 32) return fail(SAVAD_E_UNSUPPORTED, "strided input is for sequences longer than 32 frames (windows of T <= 32 are read in place by savad_predict_probabilities)");
+    if (m->FP != m->cfg.feature_size) return fail(SAVAD_E_UNSUPPORTED, "strided input needs feature_size %% 16 == 0 (no padding copy)");
+    const long F = m->cfg.feature_size;
+    if (x_batch_stride <= 0 || x_batch_stride % 4 || x_batch_stride % F)
+        return fail(SAVAD_E_INVALID, "x_batch_stride=%ld (a positive multiple of feature_size and of 4 elements)", x_batch_stride);
+    if (x_dtype < 0 || x_dtype > 1 || (x_dtype == 1 && m->precision != 1)) return fail(SAVAD_E_INVALID, "x_dtype %d (bf16 features need savad_set_precision(h, 1))", x_dtype);
+    return forward_any(m, x, x_dtype, B, T, x_batch_stride, out, workspace, workspace_bytes, stream);
+}
+
+SAVAD_EXPORT int savad_forward(savad_handle m, const float* x, int B, int T, float* out, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    return forward_any(m, x, 0, B, T, 0, out, workspace, workspace_bytes, stream);
 }
 
 SAVAD_EXPORT int savad_set_profiling(savad_handle m, int capacity) {
@@ -1605,57 +1332,20 @@ SAVAD_EXPORT int savad_boost(const float* logp, const int64_t* positions, int co
 
 // ---- the whole of predict_probabilities (vad/predictor.py:159-262) in one call -------------------------------
 namespace {
-struct PredictPlan {
-    int W, n_items, chunk;
-    bool windowed;  // the single-launch forward reads its windows straight out of the feature matrix
-    bool f32s;      // ... and it is the fp32s one (precision 2 from SAVAD_F32S_PACKED_MIN_BLOCKS blocks up; shorter clips: the exact-fp32 one)
-    size_t logp, windows, fwd, total;  // byte offsets into the workspace
-    size_t fwd_bytes;
-};
-int plan_predict(savad_model* m, int N, int half, int jump, int chunk, PredictPlan* p) {
+// validates the geometry and plans the call (savad_schedule.h: plan_predict)
+int plan_predict(savad_model* m, int N, int half, int jump, int chunk, sched::PredictPlan* p) {
     if (N < 0 || half < 0 || jump <= 0 || chunk <= 0) return fail(SAVAD_E_INVALID, "N=%d half=%d jump=%d chunk=%d", N, half, jump, chunk);
-    p->W = savad_window_offsets(half, jump, nullptr);
-    if (p->W > 64) return fail(SAVAD_E_UNSUPPORTED, "window longer than 64 frames");
-    p->n_items = N - 2 * half > 0 ? N - 2 * half : 0;  // vad/predictor.py:169
-    const int F = m->cfg.feature_size;
-    // windowed: the whole clip in ONE single-launch forward (up to 1024 packed tiles = 4096 windows of 7 frames, ~41 s of
-    // audio: savad_forward's own limit for that kernel); longer inputs go through `chunk`-sized M-split forwards, which
-    // are ~9 % faster per window than 4096-window launches (5.27 vs 5.36 ms for 10 min of audio)
-    // (bf16 operands: the single launch amortises the weight stream over the workgroup's blocks, so it takes any number of windows)
-    p->f32s = m->precision == 2 && !m->generic && p->W <= 32 && m->FP == F && p->n_items > 0 && packed_f32s_applies(m, p->n_items, p->W);
-    if (m->precision == 1)
-        p->windowed = !m->generic && p->W <= 32 && m->FP == F && packed_bf16_applies(m, p->W);
-    else if (p->f32s)   // (the fp32s single launch takes any number of windows)
-        p->windowed = true;
-    else
-        p->windowed = !m->generic && p->W <= 32 && m->cfg.num_layers <= PACKED_MAX_LAYERS && m->FP == F &&
-                      (m->row_mode == 4 || (m->row_mode == 0 && p->n_items <= 1024 * (32 / p->W)));
-    // chunk-sized forwards write their log-probs at logp + first*W*2 floats and savad_forward wants 16-byte aligned
-    // pointers: an even chunk keeps every offset a multiple of 16 bytes whatever W is (windows are independent, so the
-    // chunking never changes a result beyond fp32 summation order)
-    p->chunk = p->windowed ? (m->precision == 1 || p->f32s ? (1 << 22) : 1024 * (32 / p->W)) : chunk + (chunk & 1);
-    if (p->chunk > p->n_items) p->chunk = p->n_items > 0 ? p->n_items : 1;
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    size_t off = 0;
-    p->logp = off;
-    off += up(sizeof(float) * (size_t)(p->n_items > 0 ? p->n_items : 1) * p->W * 2);
-    p->windows = p->fwd = off;
-    p->fwd_bytes = 0;
-    if (!p->windowed) {
-        off += up(sizeof(float) * (size_t)p->chunk * p->W * F);
-        p->fwd = off;
-        int rc = savad_workspace_bytes(m, p->chunk, p->W, &p->fwd_bytes);
-        if (rc) return rc;
-        off += up(p->fwd_bytes);
-    }
-    p->total = off;
+    *p = sched::plan_predict(knobs_of(m), N, half, jump, chunk);
+    if (p->err) return fail(p->err, "%s", p->msg);
+    if (!p->windowed && (double)p->chunk * p->W * D >= 2.0e9)   // the chunk-sized forward's own limit (savad_workspace_bytes)
+        return fail(SAVAD_E_UNSUPPORTED, "B*T=%ld rows exceed the 32-bit tile index range", (long)p->chunk * p->W);
     return SAVAD_OK;
 }
 }  // namespace
 
 SAVAD_EXPORT int savad_predict_workspace_bytes(savad_handle m, int N, int half, int jump, int chunk, size_t* bytes) {
     if (!m || !bytes) return fail(SAVAD_E_INVALID, "null argument");
-    PredictPlan p;
+    sched::PredictPlan p;
     int rc = plan_predict(m, N, half, jump, chunk, &p);
     if (rc) return rc;
     *bytes = p.total;
@@ -1668,7 +1358,7 @@ SAVAD_EXPORT int savad_predict_probabilities(savad_handle m, const float* featur
     if (N == 0) return SAVAD_OK;
     if (!feature || !probs || !workspace) return fail(SAVAD_E_INVALID, "null tensor pointer");
     if (((uintptr_t)feature | (uintptr_t)workspace) & 15) return fail(SAVAD_E_INVALID, "feature and workspace must be 16-byte aligned");
-    PredictPlan p;
+    sched::PredictPlan p;
     int rc = plan_predict(m, N, half, jump, chunk, &p);
     if (rc) return rc;
     if (workspace_bytes < p.total) return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
@@ -1682,25 +1372,15 @@ SAVAD_EXPORT int savad_predict_probabilities(savad_handle m, const float* featur
         return fail(SAVAD_E_INVALID, "windows reach outside the %d feature frames", N);
     char* ws = (char*)workspace;
     float* logp = (float*)(ws + p.logp);
-    if (p.windowed && p.n_items > 0) {
-        if ((rc = prepare_weights(m, st))) return rc;
-        if ((rc = ensure_pe(m, W, st))) return rc;
-        if (m->precision == 1) {
-            if ((rc = prepare_frags(m, st))) return rc;
-            if ((rc = prepare_bf16_launch(m))) return rc;
-        }
-        if (p.f32s) {
-            if ((rc = prepare_frags3(m, st))) return rc;
-            if ((rc = prepare_f32s_launch(m))) return rc;
-        }
-    }
+    if (p.windowed && p.n_items > 0 && (rc = ensure_ready(m, p.family, W, st))) return rc;
     for (int first = 0; first < p.n_items; first += p.chunk) {
         const int count = p.n_items - first < p.chunk ? p.n_items - first : p.chunk;
         float* out = logp + (size_t)first * W * 2;
-        if (p.windowed && m->precision == 1) {
-            launch_packed_forward_bf16(m, st, feature, count, W, F, out, wo, half + first);
-        } else if (p.windowed && p.f32s) {
-            launch_packed_forward_f32s(m, st, feature, count, W, F, out, wo, half + first);
+        const int variant = count == p.chunk ? p.variant : p.variant_last;
+        if (p.windowed && p.family == sched::BF16) {
+            launch_packed_forward_bf16(m, variant, st, feature, count, W, F, out, wo, half + first);
+        } else if (p.windowed && p.family == sched::F32S) {
+            launch_packed_forward_f32s(m, variant, st, feature, count, W, F, out, wo, half + first);
         } else if (p.windowed) {
             launch_packed_forward(m, st, feature, count, W, F, out, wo, half + first);
         } else {
