@@ -350,6 +350,42 @@ long savad_frames_to_samples(const double* frames, int n, int sample_rate, doubl
 int savad_samples_to_segments(const double* samples, long n, long* starts, long* ends, int cap);
 int savad_optimal_split(const double* pred, const double* probs, long n, long max_samples, double* out);
 
+/* The same post-processing ON THE DEVICE (csrc/savad_post_device.h): probs [N, W] float32 -> the segments the four host
+ * functions above give, bit for bit; only a segment count and count x 2 sample indices return to the host.
+ *   savad_post_supported        HOST arithmetic, 1 or 0: 1 <= W <= 128 (numpy's float32 row mean sums longer rows in another
+ *                               order), and a geometry whose hop is a whole number of samples >= 1 with
+ *                               (n_frames - 1) * hop + window < 2^52 (then the reference's repeated `start += hop` is exact).
+ *   savad_post_workspace_bytes  one workspace size for _frames and _segments of n_frames frames at that geometry.
+ *   savad_post_frames           DEVICE pointers.  boosted [N] = numpy's float32 mean(axis=1) of probs; trimmed [N] (0 / 1) =
+ *                               savad_trim_voice_activity of (boosted > threshold).  Asynchronous on `stream`: launches only,
+ *                               no allocation, no synchronisation.  Trim parameters must not be negative.
+ *   savad_post_segments         trimmed, boosted: DEVICE; starts, ends: HOST.  The segments of savad_samples_to_segments over
+ *                               savad_frames_to_samples of `trimmed`; with max_samples > 0 after savad_optimal_split against
+ *                               savad_frames_to_samples of `boosted` (max_samples == 0: no split, boosted may be NULL).
+ *                               Returns the segment count and writes up to `cap` pairs.  SYNCHRONISES `stream` (at least
+ *                               once; with a split once more per range query of the recursion: a long segment needs on
+ *                               the order of length / max_samples queries).
+ *   savad_post_sample_probs     boosted [N] (device) -> out (device, float64, as many elements as the size query of
+ *                               savad_frames_to_samples names) = savad_frames_to_samples of boosted.  Asynchronous.
+ *   savad_post_frames_host / savad_post_sample_class_host   HOST twins for the CPU tests: the arithmetic the kernels run
+ *                               (shared inline functions) in plain loops on host pointers; the second writes the classes
+ *                               (0 = value 0.0, 1 = value 1.0, 2 = in between) of samples [first, first + count).
+ *   savad_post_set_block        process-wide test knob: elements per workgroup block of the scans, 0 (default) or a power of
+ *                               two from 64 to the default 2048, so that a small input runs three and more scan levels.
+ * N == 0 is a no-op (0 segments).  Frame counts are int, sample indices long. */
+int savad_post_supported(int W, int sample_rate, double hop_ms, double window_ms, int n_frames);
+int savad_post_workspace_bytes(int n_frames, int W, int sample_rate, double hop_ms, double window_ms, size_t* bytes);
+int savad_post_frames(const float* probs, int N, int W, float threshold, int min_vally, int min_hill, int hang_before, int hang_over,
+                      float* boosted, uint8_t* trimmed, void* ws, size_t ws_bytes, void* stream);
+int savad_post_segments(const uint8_t* trimmed, const float* boosted, int N, int sample_rate, double hop_ms, double window_ms,
+                        long max_samples, long* starts, long* ends, int cap, void* ws, size_t ws_bytes, void* stream);
+int savad_post_sample_probs(const float* boosted, int N, int sample_rate, double hop_ms, double window_ms, double* out, void* stream);
+int savad_post_frames_host(const float* probs, int N, int W, float threshold, int min_vally, int min_hill, int hang_before,
+                           int hang_over, float* boosted, uint8_t* trimmed);
+int savad_post_sample_class_host(const uint8_t* frames, int n, int sample_rate, double hop_ms, double window_ms, long first,
+                                 long count, uint8_t* cls);
+int savad_post_set_block(int elems);
+
 const char* savad_last_error(void);
 const char* savad_version(void);
 

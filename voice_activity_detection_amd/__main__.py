@@ -43,6 +43,9 @@ def main(argv=None) -> int:
     p.add_argument("--device-ingest", action="store_true",
                    help="average the channels and resample to 16 kHz on the GPU (the file's samples are uploaded as stored) instead "
                         "of on the host: pays for every recording that is not 16 kHz mono")
+    p.add_argument("--device-post", action="store_true",
+                   help="threshold, trim, frame -> sample conversion, split and segment extraction on the GPU (same results; only "
+                        "the segments return to the host): pays for long recordings, a short clip is launch-bound")
     e = sub.add_parser("evaluate", help="frame metrics over a labelled data list (vad/evaluate.py:20-29)")
     e.add_argument("eval_path", type=Path)
     e.add_argument("checkpoint_path", type=Path)
@@ -72,7 +75,7 @@ def main(argv=None) -> int:
     from .predictor import VADFromScratchPredictor, VADPredictParameters
 
     predictor = VADFromScratchPredictor.from_checkpoint(args.checkpoint_path, args.device, extended_front_end=args.extended_front_end,
-                                                        device_ingest=args.device_ingest)
+                                                        device_ingest=args.device_ingest, device_post=args.device_post)
     predictor.model.precision, predictor.model.batch_invariant, predictor.graph = args.precision, args.batch_invariant, args.graph
     voice_activity = predictor.predict_from_path(
         args.audio_path,

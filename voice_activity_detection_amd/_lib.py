@@ -84,6 +84,15 @@ SYMBOLS = {
     "savad_frames_to_samples": (c_long, [c_void_p, c_int, c_int, c_double, c_double, c_void_p]),
     "savad_samples_to_segments": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int]),
     "savad_optimal_split": (c_int, [c_void_p, c_void_p, c_long, c_long, c_void_p]),
+    "savad_post_supported": (c_int, [c_int, c_int, c_double, c_double, c_int]),
+    "savad_post_workspace_bytes": (c_int, [c_int, c_int, c_int, c_double, c_double, POINTER(c_size_t)]),
+    "savad_post_frames": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "savad_post_segments": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_long, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                    c_void_p]),
+    "savad_post_sample_probs": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
+    "savad_post_frames_host": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "savad_post_sample_class_host": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_long, c_long, c_void_p]),
+    "savad_post_set_block": (c_int, [c_int]),
     "savad_last_error": (c_char_p, []),
     "savad_version": (c_char_p, []),
 }

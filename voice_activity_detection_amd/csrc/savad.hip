@@ -14,6 +14,7 @@
 #include "savad_frontend.h"
 #include "savad_ingest.h"
 #include "savad_post.h"
+#include "savad_post_device.h"
 #include "savad_schedule.h"
 
 #include <math.h>
@@ -21,6 +22,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -2250,6 +2252,266 @@ SAVAD_EXPORT int savad_samples_to_segments(const double* samples, long n, long* 
 SAVAD_EXPORT int savad_optimal_split(const double* pred, const double* probs, long n, long max_samples, double* out) {
     if (n < 0 || (n > 0 && (!pred || !probs || !out)) || max_samples <= 1) return fail(SAVAD_E_INVALID, "bad argument");
     savad::post::optimal_split(pred, probs, n, max_samples, out);
+    return SAVAD_OK;
+}
+
+// ---- post-processing on the device (savad_post_device.h) -----------------------------------------------------------------
+namespace {
+
+namespace pd = savad::postdev;
+
+int g_post_block = 0;   // savad_post_set_block: elements per workgroup block of the scans (0 = the default)
+
+int post_block() { return g_post_block ? g_post_block : pd::SCAN_BLOCK_DEFAULT; }
+
+struct PostLayout {   // byte offsets into the caller's workspace
+    size_t last, next, sums_f, frames_end;                                  // savad_post_frames: a function of n_frames alone
+    size_t cls, state, sums_s, seg_starts, seg_ends, totals, partial, result, total;   // savad_post_segments
+    long seg_cap;                                                           // slots of the segment (and break) buffers
+};
+
+PostLayout post_layout(int N, const pd::Geometry& g) {
+    PostLayout L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    L.last = take(sizeof(int) * (size_t)N);
+    L.next = take(sizeof(int) * (size_t)N);
+    L.sums_f = take(sizeof(int) * (size_t)pd::scan_sums_elems(N));
+    L.frames_end = off;
+    L.seg_cap = (long)N + 2;   // without a split a segment needs a frame of its own
+    L.cls = take((size_t)g.num);
+    L.state = take((size_t)g.num);
+    L.sums_s = take(sizeof(pd::Long2) * (size_t)pd::scan_sums_elems(g.num + 1));
+    L.seg_starts = take(sizeof(long) * (size_t)L.seg_cap);
+    L.seg_ends = take(sizeof(long) * (size_t)L.seg_cap);
+    L.totals = take(sizeof(long) * 2);
+    L.partial = take(sizeof(pd::MinKey) * pd::ARGMIN_GRID);
+    L.result = take(sizeof(pd::MinKey));
+    L.total = off;
+    return L;
+}
+
+int post_check_trim(int min_vally, int min_hill, int hang_before, int hang_over) {
+    if (min_vally < 0 || min_hill < 0 || hang_before < 0 || hang_over < 0)
+        return fail(SAVAD_E_INVALID, "negative trim parameter (%d, %d, %d, %d)", min_vally, min_hill, hang_before, hang_over);
+    return SAVAD_OK;
+}
+
+int post_check_geometry(int sample_rate, double hop_ms, double window_ms, int n_frames) {
+    if (!pd::geometry_supported(sample_rate, hop_ms, window_ms, n_frames))
+        return fail(SAVAD_E_UNSUPPORTED, "geometry (%d Hz, hop %g ms, window %g ms, %d frames): the device post-processing needs a hop of a whole "
+                    "number of samples >= 1 and (n-1)*hop + window < 2^52", sample_rate, hop_ms, window_ms, n_frames);
+    return SAVAD_OK;
+}
+
+}  // namespace
+
+SAVAD_EXPORT int savad_post_supported(int W, int sample_rate, double hop_ms, double window_ms, int n_frames) {
+    return W >= 1 && W <= pd::W_MAX && pd::geometry_supported(sample_rate, hop_ms, window_ms, n_frames) ? 1 : 0;
+}
+
+SAVAD_EXPORT int savad_post_set_block(int elems) {
+    if (elems != 0 && (elems < pd::SCAN_BLOCK_MIN || elems > pd::SCAN_BLOCK_DEFAULT || (elems & (elems - 1))))
+        return fail(SAVAD_E_INVALID, "scan block %d (0 = default, or a power of two from %d to %d)", elems, pd::SCAN_BLOCK_MIN, pd::SCAN_BLOCK_DEFAULT);
+    g_post_block = elems;
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_post_workspace_bytes(int n_frames, int W, int sample_rate, double hop_ms, double window_ms, size_t* bytes) {
+    if (!bytes || n_frames < 0 || W < 1) return fail(SAVAD_E_INVALID, "bad argument");
+    if (W > pd::W_MAX) return fail(SAVAD_E_UNSUPPORTED, "W = %d: the device row mean has numpy's order up to %d", W, pd::W_MAX);
+    int rc;
+    if ((rc = post_check_geometry(sample_rate, hop_ms, window_ms, n_frames))) return rc;
+    *bytes = post_layout(n_frames, pd::make_geometry(n_frames, sample_rate, hop_ms, window_ms)).total;
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_post_frames(const float* probs, int N, int W, float threshold, int min_vally, int min_hill, int hang_before, int hang_over,
+                                   float* boosted, uint8_t* trimmed, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (N < 0 || W < 1) return fail(SAVAD_E_INVALID, "N = %d, W = %d", N, W);
+    if ((rc = post_check_trim(min_vally, min_hill, hang_before, hang_over))) return rc;
+    if (W > pd::W_MAX) return fail(SAVAD_E_UNSUPPORTED, "W = %d: the device row mean has numpy's order up to %d", W, pd::W_MAX);
+    if (N == 0) return SAVAD_OK;
+    if (!probs || !boosted || !trimmed || !ws) return fail(SAVAD_E_INVALID, "null pointer");
+    pd::Geometry none = pd::make_geometry(0, 1, 1000.0, 1000.0);
+    const PostLayout L = post_layout(N, none);
+    if (ws_bytes < L.frames_end) return fail(SAVAD_E_INVALID, "workspace of %zu bytes, %zu needed", ws_bytes, L.frames_end);
+    int* last = (int*)((char*)ws + L.last);
+    int* next = (int*)((char*)ws + L.next);
+    int* sums = (int*)((char*)ws + L.sums_f);
+    const int block = post_block();
+    hipLaunchKernelGGL(pd::frames_kernel, dim3(grid_for(N)), dim3(256), 0, st, probs, N, W, threshold, boosted, trimmed);
+    for (int pass = 0; pass < 3; ++pass) {
+        if ((pass == 0 && min_vally <= 0) || (pass == 1 && min_hill <= 0) || (pass == 2 && hang_before <= 0)) continue;
+        const int k_last = pass == 1 ? 0 : 1, k_next = pass == 1 ? 1 : 0;
+        pd::scan_run<pd::OpMax>(st, N, block, pd::EdgeLoad{trimmed, N, k_last, 0}, pd::EdgeStore{last, N, 0}, sums);
+        pd::scan_run<pd::OpMin>(st, N, block, pd::EdgeLoad{trimmed, N, k_next, 1}, pd::EdgeStore{next, N, 1}, sums);
+        hipLaunchKernelGGL(pd::trim_apply_kernel, dim3(grid_for(N)), dim3(256), 0, st, trimmed, N, pass, (const int*)last, (const int*)next, min_vally,
+                           min_hill, hang_before, hang_over);
+    }
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_post_segments(const uint8_t* trimmed, const float* boosted, int N, int sample_rate, double hop_ms, double window_ms,
+                                     long max_samples, long* starts, long* ends, int cap, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (N < 0 || cap < 0 || max_samples < 0 || max_samples == 1) return fail(SAVAD_E_INVALID, "N = %d, cap = %d, max_samples = %ld", N, cap, max_samples);
+    if (cap > 0 && (!starts || !ends)) return fail(SAVAD_E_INVALID, "null output");
+    if ((rc = post_check_geometry(sample_rate, hop_ms, window_ms, N))) return rc;
+    if (N == 0) return 0;
+    if (!trimmed || (max_samples > 0 && !boosted) || !ws) return fail(SAVAD_E_INVALID, "null pointer");
+    const pd::Geometry g = pd::make_geometry(N, sample_rate, hop_ms, window_ms);
+    const PostLayout L = post_layout(N, g);
+    if (ws_bytes < L.total) return fail(SAVAD_E_INVALID, "workspace of %zu bytes, %zu needed", ws_bytes, L.total);
+    if (g.num == 0) return 0;
+    char* base = (char*)ws;
+    uint8_t* cls = (uint8_t*)(base + L.cls);
+    uint8_t* state = (uint8_t*)(base + L.state);
+    pd::Long2* sums = (pd::Long2*)(base + L.sums_s);
+    long* d_starts = (long*)(base + L.seg_starts);
+    long* d_ends = (long*)(base + L.seg_ends);
+    long* d_totals = (long*)(base + L.totals);
+    pd::MinKey* d_partial = (pd::MinKey*)(base + L.partial);
+    pd::MinKey* d_result = (pd::MinKey*)(base + L.result);
+    const int block = post_block();
+    long tot[2] = {0, 0};
+    long have_first = -1;   // the window of segments the buffers hold
+
+    // the segments of the classes as they stand: state scan (when the classes changed), flags, prefix sums, scatter of the
+    // window [first, first + seg_cap), totals to the host.  Synchronises.
+    auto segments_pass = [&](bool classes_changed, long first) -> int {
+        if (classes_changed) pd::scan_run<pd::OpLast>(st, g.num, block, pd::ClassLoad{cls}, pd::ClassStore{state}, (int*)sums);
+        const pd::FlagLoad flags{cls, state, g.num};
+        pd::scan_run<pd::OpSum2>(st, g.num + 1, block, flags, pd::SegmentStore{flags, d_starts, d_ends, first, L.seg_cap, d_totals}, sums);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(tot, d_totals, sizeof(tot), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        have_first = first;
+        if (tot[0] != tot[1]) return fail(SAVAD_E_STATE, "%ld starts and %ld ends", tot[0], tot[1]);
+        if (tot[0] > INT_MAX) return fail(SAVAD_E_UNSUPPORTED, "%ld segments", tot[0]);
+        return SAVAD_OK;
+    };
+    // copies segments [first, first + count) to the host; count <= seg_cap
+    auto fetch = [&](long first, long count, long* hs, long* he) -> int {
+        if (have_first != first) {
+            int r = segments_pass(false, first);
+            if (r) return r;
+        }
+        HIP_TRY(hipMemcpyAsync(hs, d_starts, sizeof(long) * (size_t)count, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(he, d_ends, sizeof(long) * (size_t)count, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return SAVAD_OK;
+    };
+
+    hipLaunchKernelGGL(pd::sample_class_kernel, dim3(grid_for(g.num)), dim3(256), 0, st, trimmed, g, cls);
+    if ((rc = segments_pass(true, 0))) return rc;
+
+    if (max_samples > 0 && tot[0] > 0) {
+        // vad/postprocessing/split.py:26-109: the recursion of savad_post.h's split_long_block on the host, its argmin as range queries
+        // to the device (one stream synchronisation per query; a long segment needs on the order of len / max_samples of them)
+        const long half = max_samples / 2;
+        auto query = [&](long a, long b, long* best) -> int {
+            const long work = (b - a + 255) / 256;
+            const int grid = (int)(work < pd::ARGMIN_GRID ? work : pd::ARGMIN_GRID);
+            pd::MinKey r;
+            hipLaunchKernelGGL(pd::argmin_stage1_kernel, dim3(grid), dim3(256), 0, st, boosted, g, a, b, d_partial);
+            hipLaunchKernelGGL(pd::argmin_stage2_kernel, dim3(1), dim3(256), 0, st, (const pd::MinKey*)d_partial, grid, d_result);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&r, d_result, sizeof(r), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (r.index < a || r.index >= b) return fail(SAVAD_E_STATE, "argmin over [%ld, %ld) answered %ld", a, b, r.index);
+            *best = r.index;
+            return SAVAD_OK;
+        };
+        std::vector<long> breaks;
+        // break points of the long block [s, s + len) (len > max_samples); the right-hand remainder is walked in a loop
+        std::function<int(long, long)> split = [&](long s, long len) -> int {
+            for (;;) {
+                long best;
+                int r = query(s + half, s + len - half, &best);
+                if (r) return r;
+                const long bp = best - s;
+                if (bp > max_samples && (r = split(s, bp))) return r;
+                breaks.push_back(s + bp);
+                const long rlen = len - bp - 1;
+                if (rlen <= max_samples) return SAVAD_OK;
+                s += bp + 1;
+                len = rlen;
+            }
+        };
+        const long count = tot[0];
+        std::vector<long> hs((size_t)(count < L.seg_cap ? count : L.seg_cap)), he(hs.size());
+        for (long first = 0; first < count; first += L.seg_cap) {
+            const long c = count - first < L.seg_cap ? count - first : L.seg_cap;
+            if ((rc = fetch(first, c, hs.data(), he.data()))) return rc;
+            for (long k = 0; k < c; ++k)
+                if (he[k] + 1 - hs[k] > max_samples && (rc = split(hs[k], he[k] + 1 - hs[k]))) return rc;
+        }
+        if (!breaks.empty()) {   // (sorted: the recursion emits them in order.)  Uploaded through the segment buffer, a chunk at a time
+            for (size_t at = 0; at < breaks.size(); at += (size_t)L.seg_cap) {
+                const size_t c = breaks.size() - at < (size_t)L.seg_cap ? breaks.size() - at : (size_t)L.seg_cap;
+                HIP_TRY(hipMemcpyAsync(d_starts, breaks.data() + at, sizeof(long) * c, hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(pd::breaks_kernel, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, st, (const long*)d_starts, (int)c, g.num, cls);
+                HIP_TRY(hipStreamSynchronize(st));   // (the chunk's source and the buffer are free again)
+            }
+            if ((rc = segments_pass(true, 0))) return rc;
+        }
+    }
+    const long count = tot[0], want = count < cap ? count : cap;
+    for (long first = 0; first < want; first += L.seg_cap) {
+        const long c = want - first < L.seg_cap ? want - first : L.seg_cap;
+        if ((rc = fetch(first, c, starts + first, ends + first))) return rc;
+    }
+    return (int)count;
+}
+
+SAVAD_EXPORT int savad_post_sample_probs(const float* boosted, int N, int sample_rate, double hop_ms, double window_ms, double* out, void* stream) {
+    int rc;
+    if (N < 0) return fail(SAVAD_E_INVALID, "N = %d", N);
+    if ((rc = post_check_geometry(sample_rate, hop_ms, window_ms, N))) return rc;
+    const pd::Geometry g = pd::make_geometry(N, sample_rate, hop_ms, window_ms);
+    if (g.num == 0) return SAVAD_OK;
+    if ((N > 0 && !boosted) || !out) return fail(SAVAD_E_INVALID, "null pointer");
+    hipLaunchKernelGGL(pd::sample_probs_kernel, dim3(grid_for(g.num)), dim3(256), 0, (hipStream_t)stream, boosted, g, out);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_post_frames_host(const float* probs, int N, int W, float threshold, int min_vally, int min_hill, int hang_before, int hang_over,
+                                        float* boosted, uint8_t* trimmed) {
+    int rc;
+    if (N < 0 || W < 1) return fail(SAVAD_E_INVALID, "N = %d, W = %d", N, W);
+    if ((rc = post_check_trim(min_vally, min_hill, hang_before, hang_over))) return rc;
+    if (W > pd::W_MAX) return fail(SAVAD_E_UNSUPPORTED, "W = %d: the device row mean has numpy's order up to %d", W, pd::W_MAX);
+    if (N == 0) return SAVAD_OK;
+    if (!probs || !boosted || !trimmed) return fail(SAVAD_E_INVALID, "null pointer");
+    for (int i = 0; i < N; ++i) {
+        boosted[i] = pd::row_mean(probs + (size_t)i * W, W);
+        trimmed[i] = pd::above(boosted[i], threshold);
+    }
+    std::vector<int> last((size_t)N), next((size_t)N);
+    pd::trim_host(trimmed, N, min_vally, min_hill, hang_before, hang_over, last.data(), next.data());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_post_sample_class_host(const uint8_t* frames, int n, int sample_rate, double hop_ms, double window_ms, long first, long count,
+                                              uint8_t* cls) {
+    int rc;
+    if (n < 0 || first < 0 || count < 0) return fail(SAVAD_E_INVALID, "n = %d, samples [%ld, +%ld)", n, first, count);
+    if ((rc = post_check_geometry(sample_rate, hop_ms, window_ms, n))) return rc;
+    const pd::Geometry g = pd::make_geometry(n, sample_rate, hop_ms, window_ms);
+    if (first + count > g.num) return fail(SAVAD_E_INVALID, "samples [%ld, +%ld) of %ld", first, count, g.num);
+    if (count == 0) return SAVAD_OK;
+    if ((n > 0 && !frames) || !cls) return fail(SAVAD_E_INVALID, "null pointer");
+    for (long i = 0; i < count; ++i) cls[i] = pd::sample_class(frames, g, first + i);
     return SAVAD_OK;
 }
 

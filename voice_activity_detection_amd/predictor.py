@@ -68,7 +68,7 @@ class VADFromScratchPredictor:
 
     def __init__(self, model: SelfAttentiveVAD, device: torch.device, context: ContextResolution = ContextResolution(),
                  chunk_size: int = 16384, graph: bool = False, graph_max_seconds: float = 120.0, graph_cache: int = 8,
-                 front_end=None, device_ingest: bool = False):
+                 front_end=None, device_ingest: bool = False, device_post: bool = False):
         """`graph=True` (not in the reference's signature): clip-sized inputs -- up to `graph_max_seconds` of audio -- run as a
         replayed HIP graph of the whole chain log-mel -> window gather -> forward -> boost, captured on first use per (length, model
         knobs) and re-captured when the weights change; at most `graph_cache` graphs are kept (least recently used goes).  For a 10 s
@@ -78,11 +78,19 @@ class VADFromScratchPredictor:
         on the audio.  Only the shipped one has the host-upload path (predict_audio_host).
         `device_ingest=True`: predict_from_path uploads a file's samples as they are stored and averages the channels and resamples
         to 16 kHz on the GPU (features.load_audio_device) instead of on the host (features.load_wav_mono16k): the resampler has the
-        bits of resampy's loop, which the host function approaches within 2e-6."""
+        bits of resampy's loop, which the host function approaches within 2e-6.
+        `device_post=True`: predict() post-processes a chunk's probabilities on the GPU (postprocessing.post_frames_device /
+        segments_device / sample_probs_device: row mean, threshold, trim, frame -> sample classes, optimal split, segments) and
+        fetches only the segments -- the host functions' results, bit for bit -- where the geometry allows it (a hop of a whole
+        number of samples, at most 128 probabilities per frame); any other chunk takes the host code.  `post_stats` counts the
+        chunks either way.  Pays for long recordings (the host builds float64 arrays of one element per sample); a short clip
+        is launch-bound."""
         from .features import SHIPPED_FRONT_END
 
         self.front_end = SHIPPED_FRONT_END if front_end is None else front_end
         self.device_ingest = bool(device_ingest)
+        self.device_post = bool(device_post)
+        self.post_stats = {"device": 0, "host": 0}   # chunks post-processed on the GPU / on the host
         self.graph, self.graph_max_seconds, self.graph_cache = bool(graph), float(graph_max_seconds), int(graph_cache)
         self._graphs: "OrderedDict[tuple, dict]" = OrderedDict()
         self.graph_stats = {"captures": 0, "replays": 0, "eager": 0}
@@ -145,7 +153,7 @@ class VADFromScratchPredictor:
 
     @classmethod
     def from_checkpoint(cls, checkpoint_path, device, trust_checkpoint: bool = False, extended_front_end: bool = False,
-                        device_ingest: bool = False):
+                        device_ingest: bool = False, device_post: bool = False):
         """vad/predictor.py:264-280: a training checkpoint holds {"config": ..., "state_dict": ...} plus what
         ModelCheckpointer adds (epoch, global_step, monitor_metric, a `metrics` dict of numpy scalars, optimizer /
         scheduler / grad-scaler state: vad/training/checkpointers/model_checkpointer.py:97-110); the model size, the
@@ -154,7 +162,7 @@ class VADFromScratchPredictor:
         `extended_front_end=True` builds every feature_extractor config features.FrontEnd takes (the four transforms at any
         geometry within its limits, temporal differences); the default refuses all but the shipped one.  The shipped
         features are pinned by goldens and trained-weights AUC, the others by a restatement of librosa 0.8.0: opting in
-        acknowledges that.  `device_ingest`: as in the constructor."""
+        acknowledges that.  `device_ingest`, `device_post`: as in the constructor."""
         ckpt = cls._load_checkpoint(checkpoint_path, trust_checkpoint)
         cfg = ckpt["config"]
 
@@ -185,7 +193,7 @@ class VADFromScratchPredictor:
             model.load_state_dict(ckpt["state_dict"])
             ctx = ContextResolution(get(cfg, "context_resolution", "context_window_half_frames"),
                                     get(cfg, "context_resolution", "context_window_jump_frames"))
-            predictor = cls(model.to(device).eval(), device, ctx, front_end=front, device_ingest=device_ingest)
+            predictor = cls(model.to(device).eval(), device, ctx, front_end=front, device_ingest=device_ingest, device_post=device_post)
             predictor.hop_ms, predictor.window_ms = front.hop_ms, front.window_ms  # vad/predictor.py:103-104
             return predictor
         tr = get(fe, "transform")
@@ -203,7 +211,7 @@ class VADFromScratchPredictor:
         model.load_state_dict(ckpt["state_dict"])
         ctx = ContextResolution(get(cfg, "context_resolution", "context_window_half_frames"),
                                 get(cfg, "context_resolution", "context_window_jump_frames"))
-        predictor = cls(model.to(device).eval(), device, ctx, device_ingest=device_ingest)
+        predictor = cls(model.to(device).eval(), device, ctx, device_ingest=device_ingest, device_post=device_post)
         predictor.hop_ms, predictor.window_ms = got["hop_ms"], got["window_ms"]  # vad/predictor.py:103-104
         return predictor
 
@@ -237,29 +245,74 @@ class VADFromScratchPredictor:
                 probs_dev, mean_dev = self.predict_probabilities_device(features_fn(chunk))
             else:
                 probs_dev, mean_dev = self.predict_audio_device(chunk)   # (a replayed HIP graph for clip-sized chunks when graph=True)
-            # float64 mean of the float32 [N, 7] matrix, like numpy's probs.mean(axis=1) on the host (:95)
-            boosted = probs_dev.cpu().numpy().mean(axis=1)
-            predictions = boosted > parameters.threshold
-            hop_ms, window_ms = self.hop_ms, self.window_ms
-            trimmed = trim_voice_activity(predictions, min_vally=round(parameters.min_vally_ms / hop_ms),
-                                          min_hill=round(parameters.min_hill_ms / hop_ms),
-                                          hang_before=round(parameters.hang_before_ms / hop_ms),
-                                          hang_over=round(parameters.hang_over_ms / hop_ms))
-            sample_predictions = convert_frames_to_samples(trimmed, sample_rate=16000, hop_ms=hop_ms, window_ms=window_ms)
-            if parameters.activity_max_seconds is not None and parameters.activity_max_seconds > 0:
-                sample_full_probs = convert_frames_to_samples(boosted, sample_rate=16000, hop_ms=hop_ms, window_ms=window_ms)
-                sample_predictions = optimal_split_voice_activity(sample_predictions, sample_full_probs,
-                                                                  max_length_seconds=parameters.activity_max_seconds,
-                                                                  sample_rate=16000)
-            activities = [Activity(start=a, end=b) for a, b in convert_samples_to_segments(sample_predictions, 16000)]
-            probs = None
-            if parameters.return_probs:
-                probs = convert_frames_to_samples(boosted, sample_rate=parameters.probs_sample_rate, hop_ms=hop_ms,
-                                                  window_ms=window_ms).tolist()
+            if self.device_post and self._device_post_applies(probs_dev, parameters):
+                activities, probs = self._post_device(probs_dev, parameters)
+                self.post_stats["device"] += 1
+            else:
+                activities, probs = self._post_host(probs_dev, parameters)
+                self.post_stats["host"] += 1
             chunks.append(VoiceActivity(duration=timedelta(seconds=adjusted), activities=activities,
                                         probs_sample_rate=parameters.probs_sample_rate if parameters.return_probs else None,
                                         probs=probs))
         return merge_voice_activities(chunks)
+
+    def _post_host(self, probs_dev, parameters: VADPredictParameters):
+        """probs [N, W] on the device -> (activities, probs list or None) on the host: vad/predictor.py:95-141"""
+        # float64 mean of the float32 [N, 7] matrix, like numpy's probs.mean(axis=1) on the host (:95)
+        boosted = probs_dev.cpu().numpy().mean(axis=1)
+        predictions = boosted > parameters.threshold
+        hop_ms, window_ms = self.hop_ms, self.window_ms
+        trimmed = trim_voice_activity(predictions, min_vally=round(parameters.min_vally_ms / hop_ms),
+                                      min_hill=round(parameters.min_hill_ms / hop_ms),
+                                      hang_before=round(parameters.hang_before_ms / hop_ms),
+                                      hang_over=round(parameters.hang_over_ms / hop_ms))
+        sample_predictions = convert_frames_to_samples(trimmed, sample_rate=16000, hop_ms=hop_ms, window_ms=window_ms)
+        if parameters.activity_max_seconds is not None and parameters.activity_max_seconds > 0:
+            sample_full_probs = convert_frames_to_samples(boosted, sample_rate=16000, hop_ms=hop_ms, window_ms=window_ms)
+            sample_predictions = optimal_split_voice_activity(sample_predictions, sample_full_probs,
+                                                              max_length_seconds=parameters.activity_max_seconds,
+                                                              sample_rate=16000)
+        activities = [Activity(start=a, end=b) for a, b in convert_samples_to_segments(sample_predictions, 16000)]
+        probs = None
+        if parameters.return_probs:
+            probs = convert_frames_to_samples(boosted, sample_rate=parameters.probs_sample_rate, hop_ms=hop_ms,
+                                              window_ms=window_ms).tolist()
+        return activities, probs
+
+    def _device_post_applies(self, probs_dev, parameters: VADPredictParameters) -> bool:
+        """the conditions of the device post-processing for this chunk (host arithmetic): both geometries in use -- 16 kHz, and
+        probs_sample_rate when the probabilities are returned -- have a whole hop, the split length is one the host accepts"""
+        from .postprocessing import device_post_supported
+
+        N, W = int(probs_dev.shape[0]), int(probs_dev.shape[1])
+        hop_ms, window_ms = self.hop_ms, self.window_ms
+        if probs_dev.device.type != "cuda" or not device_post_supported(W, 16000, hop_ms, window_ms, N):
+            return False
+        if parameters.return_probs and not device_post_supported(W, parameters.probs_sample_rate, hop_ms, window_ms, N):
+            return False
+        if min(parameters.min_vally_ms, parameters.min_hill_ms, parameters.hang_before_ms, parameters.hang_over_ms) < 0:
+            return False
+        amax = parameters.activity_max_seconds
+        return not (amax is not None and amax > 0 and int(amax * 16000) < 2)
+
+    def _post_device(self, probs_dev, parameters: VADPredictParameters):
+        """_post_host's results from the GPU: only the segment indices (and the probability samples, when asked for) come back"""
+        from .postprocessing import post_frames_device, sample_probs_device, segments_device
+
+        hop_ms, window_ms = self.hop_ms, self.window_ms
+        boosted, trimmed = post_frames_device(probs_dev, parameters.threshold, min_vally=round(parameters.min_vally_ms / hop_ms),
+                                              min_hill=round(parameters.min_hill_ms / hop_ms),
+                                              hang_before=round(parameters.hang_before_ms / hop_ms),
+                                              hang_over=round(parameters.hang_over_ms / hop_ms))
+        amax = parameters.activity_max_seconds
+        starts, ends = segments_device(trimmed, boosted, sample_rate=16000, hop_ms=hop_ms, window_ms=window_ms,
+                                       max_length_seconds=amax if amax is not None and amax > 0 else None)
+        # (times as convert_samples_to_segments builds them)
+        activities = [Activity(start=timedelta(seconds=int(a) / 16000), end=timedelta(seconds=int(b) / 16000)) for a, b in zip(starts, ends)]
+        probs = None
+        if parameters.return_probs:
+            probs = sample_probs_device(boosted, sample_rate=parameters.probs_sample_rate, hop_ms=hop_ms, window_ms=window_ms).cpu().numpy().tolist()
+        return activities, probs
 
     def predict_probabilities(self, feature) -> np.ndarray:
         """feature [N, F] (numpy or tensor) -> positive-class probabilities [N, W] (float32 numpy),
