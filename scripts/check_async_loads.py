@@ -66,7 +66,7 @@ _F32S_PIECES = ("the twelve 1-KiB pieces of ring slot t + 2 are placed one at a 
                 "(savad_kernels_f32s.h, Ring3): one request, ordered by the barrier at the head of step t -- the slot they fill was last read "
                 "in step t - 1, which every wave has left")
 DMA_DISJOINT = {
-    "21input_qkv_kernel_f32s": _F32S_PIECES,
+    "input_qkv_kernel_f32s": _F32S_PIECES,   # (both forms: ..._f32s and ..._f32s_plain)
     "25attention_row_kernel_f32s": _F32S_PIECES,
     "26packed_forward_kernel_f32s": _F32S_PIECES,
     "logmel_fft_kernel": "the DMA fills the sample stage; between barrier 1 and the DMA statements the wave only reads the exchange "
@@ -422,7 +422,7 @@ _RUNTIME_WAITS = "the counted ring wait is picked at run time from the number of
 _LAST_PASS = "the tile loop's last pass requests nothing (`more` is false) and leaves through the hand-over barrier: the path 'requested, then left' is infeasible"
 _RING3 = "the 3-slot ring of the fp32s kernels runs two slots ahead: a slot's pieces cross the barrier of the slot in front of it"
 DMA_PUBLISH_BARRIERS = {
-    "21input_qkv_kernel_f32s": (1, _RING3),
+    "input_qkv_kernel_f32s": (1, _RING3),
     "25attention_row_kernel_f32s": (1, _RING3),
     "25attention_row_kernel_f32sILb0ELb0E": (2, _RING3 + "; its prologue requests THREE slots (K(0) alone in front of the stream): the third crosses the first two barriers"),
     "25attention_row_kernel_f32sILb1ELb0E": (2, _RING3 + "; its prologue requests THREE slots (K(0) alone in front of the stream): the third crosses the first two barriers"),

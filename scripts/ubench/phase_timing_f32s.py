@@ -17,14 +17,18 @@ lib.savad_debug_stamps.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.c_i
 buf = (ctypes.c_longlong * 64)()
 lib.savad_debug_stamps(buf, 64)
 t = list(buf)
-# (T > 32: the out-projection is folded into V -- stamp 5 closes the wait for chain slot 0 and h1 = h + bo + O / l, and the chain's
-# slots are 0..15 W1 / W2 chunks, 16..21 Q / K / V; T <= 32 keeps Wo in slots 0, 1 and stamp 5 behind its out-projection)
+# (T > 32: the out-projection is folded into V and the key projection into Q -- stamp 5 closes the wait for chain slot 0 and
+# h1 = h + bo + O / l, and the chain's slots are 0..15 W1 / W2 chunks, 16..19 Wq~ (with the K stores) / Wvo: stamps 12..15; T <= 32
+# keeps Wo in slots 0, 1, stamp 5 behind its out-projection, and the six Q / K / V slots: stamps 12..17)
+folded = T > 32
 names = {1: "prologue: K0 landed", 2: "scores of tile 0", 3: "key tiles", 4: "context normalised", 5: "slot 0 wait, h + bo + O/l", 6: "LN + split", 7: "FFN chunk 0",
-         8: "FFN chunk 1", 9: "FFN chunk 2", 10: "FFN chunk 3", 11: "LN + split", 12: "Q slot 0", 13: "Q slot 1", 14: "K slot 0", 15: "K slot 1", 16: "V slot 0", 17: "V slot 1", 18: "end"}
+         8: "FFN chunk 1", 9: "FFN chunk 2", 10: "FFN chunk 3", 11: "LN + split", 18: "end"}
+names.update({12: "Q~ slot 0 (+ K stores)", 13: "Q~ slot 1", 14: "Vo slot 0", 15: "Vo slot 1"} if folded else
+             {12: "Q slot 0", 13: "Q slot 1", 14: "K slot 0", 15: "K slot 1", 16: "V slot 0", 17: "V slot 1"})
 prev = t[0]
 print(f"[{B},{T},80] fp32s fused launch, wave 0 of workgroup 0 (s_memtime ticks = shader cycles)")
 for i in range(1, 19):
-    if t[i]:
+    if i in names and t[i]:
         print(f"  {names[i]:24s} {t[i] - prev:8d}")
         prev = t[i]
 print(f"  total {t[18] - t[0]}")

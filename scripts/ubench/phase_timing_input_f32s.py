@@ -16,7 +16,13 @@ lib.savad_debug_stamps.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.c_i
 buf = (ctypes.c_longlong * 64)()
 lib.savad_debug_stamps(buf, 64)
 t = list(buf[57:64])
-names = ["ring fill (24 DMA pieces) + bias staging", "features, input weights, bias / PE, input GEMM (120 MFMAs)", "residual store + LayerNorm + split", "Q slots (2 x 96 MFMAs + epilogues)", "K slots", "V^T slots"]
-print(f"[{B},{T},80] input_qkv_kernel_f32s, cycles:")
-for i, n in enumerate(names): print(f"  {n:60s} {t[i+1]-t[i]:8d}")
+# T > 32 (input_qkv_kernel_f32s): the folded image Wq~ | Wvo, four slots -- no K slots, stamp 62 is not taken; the K stores ride in the
+# Wq~ slots.  T <= 32 (input_qkv_kernel_f32s_plain): six slots
+head = ["ring fill (24 DMA pieces) + bias staging", "features, input weights, bias / PE, input GEMM (120 MFMAs)", "residual store + LayerNorm + split"]
+if T > 32:
+    names, at = head + ["Q~ slots (2 x 96 MFMAs + epilogues + K stores)", "Vo^T slots"], [0, 1, 2, 3, 4, 6]
+else:
+    names, at = head + ["Q slots (2 x 96 MFMAs + epilogues)", "K slots", "V^T slots"], [0, 1, 2, 3, 4, 5, 6]
+print(f"[{B},{T},80] input_qkv_kernel_f32s{'' if T > 32 else '_plain'}, cycles:")
+for i, n in enumerate(names): print(f"  {n:60s} {t[at[i+1]]-t[at[i]]:8d}")
 print("  total", t[6] - t[0])

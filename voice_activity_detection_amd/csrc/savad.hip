@@ -94,7 +94,7 @@ struct savad_model {
     size_t f_win = 0;
     struct LayerFrag {
         size_t wqkv, wo, w1, w2;
-        size_t wqkv_vo = 0;  // lf3 only: Wq' | Wk' | Wo Wv' (prepare_frags3: the out-projection folded into V)
+        size_t wq_vo = 0;  // lf3 only: Wq~ | Wo Wv' (prepare_frags3: the key projection folded into Q, the out-projection into V)
     };
     std::vector<LayerFrag> lf;
     std::vector<LayerFrag> lf3;  // byte offsets into d_frag3
@@ -112,7 +112,7 @@ struct savad_model {
     // packed offsets
     struct LayerPacked {
         size_t wqkv, bqkv, w1, b1;
-        size_t wvo, bqkv_vo;  // fp32s, T > 32: Wo Wv' [D][D] and bq' | bk' | Wo bv' (fold_vo_kernel)
+        size_t wq_vo, bq_vo;  // fp32s, T > 32: Wq~ | Wo Wv' [2 D][D] and bq~ | Wo bv' (fold_qk_kernel, fold_vo_kernel)
         size_t frag;  // the layer's matrices in fragment order (packed_forward_kernel)
     };
     std::vector<LayerPacked> lp;
@@ -292,14 +292,18 @@ int prepare_frags3(savad_model* m, hipStream_t st) {
         if ((rc = pack_frags3(m, st, m->d_raw + m->lr[l].w2, D, DFF, m->lf3[l].w2))) return rc;
         // the fused launches of T > 32 never issue the out-projection: one head, softmax rows sum to 1, so
         //   Wo (P (x Wv'^T + bv')) + bo = P (x (Wo Wv')^T + Wo bv') + bo
-        // and the V position of a SECOND Q/K/V image holds Wvo = Wo Wv' (bias image: bq' | bk' | Wo bv'); products in fp64, rounded once.
-        // The unfolded images stay: the T <= 32 kernels read them.
+        // nor the key projection: the part of a score that depends on the key is [c Wk'^T (Wq' x_i + bq')] . x_j, so the query is
+        // projected with Wq~ = c Wk'^T Wq' (bias c Wk'^T bq') and the key is the normalised row itself.  A SECOND image per layer holds
+        // Wq~ | Wvo (bias image: bq~ | Wo bv'); products in fp64, rounded once.  The plain images stay: the T <= 32 kernels read them.
         const auto& p = m->lp[l];
-        hipLaunchKernelGGL(fs::fold_vo_kernel, dim3(D), dim3(D), 0, st, m->d_raw + m->lr[l].wo, m->d_packed + p.wqkv + (size_t)2 * D * D,
-                           m->d_packed + p.bqkv, m->d_packed + p.wvo, m->d_packed + p.bqkv_vo);
+        const float* wqkv = m->d_packed + p.wqkv;
+        hipLaunchKernelGGL(fs::fold_qk_kernel, dim3(D), dim3(D), 0, st, wqkv, wqkv + (size_t)D * D, m->d_packed + p.bqkv,
+                           1.4426950408889634 / sqrt((double)D), m->d_packed + p.wq_vo, m->d_packed + p.bq_vo);
         HIP_TRY(hipGetLastError());
-        if ((rc = pack_frags3(m, st, m->d_packed + p.wqkv, 2 * D, D, m->lf3[l].wqkv_vo))) return rc;
-        if ((rc = pack_frags3(m, st, m->d_packed + p.wvo, D, D, m->lf3[l].wqkv_vo + (size_t)2 * D * D * 6))) return rc;
+        hipLaunchKernelGGL(fs::fold_vo_kernel, dim3(D), dim3(D), 0, st, m->d_raw + m->lr[l].wo, wqkv + (size_t)2 * D * D, m->d_packed + p.bqkv,
+                           m->d_packed + p.wq_vo + (size_t)D * D, m->d_packed + p.bq_vo + D);
+        HIP_TRY(hipGetLastError());
+        if ((rc = pack_frags3(m, st, m->d_packed + p.wq_vo, 2 * D, D, m->lf3[l].wq_vo))) return rc;
     }
     m->frag3_dirty = false;
     return SAVAD_OK;
@@ -548,10 +552,10 @@ SAVAD_EXPORT int savad_create(const savad_config* cfg, savad_handle* out) {
         m->packed_floats += (size_t)DFF * D;
         q.b1 = m->packed_floats;
         m->packed_floats += DFF;
-        q.wvo = m->packed_floats;
-        m->packed_floats += (size_t)D * D;
-        q.bqkv_vo = m->packed_floats;
-        m->packed_floats += 3 * D;
+        q.wq_vo = m->packed_floats;
+        m->packed_floats += (size_t)2 * D * D;
+        q.bq_vo = m->packed_floats;
+        m->packed_floats += 2 * D;
         q.frag = m->packed_floats;
         m->packed_floats += FRAG_LAYER;
     }
@@ -595,8 +599,8 @@ SAVAD_EXPORT int savad_create(const savad_config* cfg, savad_handle* out) {
         m->frag3_bytes += (size_t)DFF * D * 6;
         fl.w2 = m->frag3_bytes;
         m->frag3_bytes += (size_t)D * DFF * 6;
-        fl.wqkv_vo = m->frag3_bytes;
-        m->frag3_bytes += (size_t)3 * D * D * 6;
+        fl.wq_vo = m->frag3_bytes;
+        m->frag3_bytes += (size_t)2 * D * D * 6;
     }
     hipError_t e = hipMalloc(&m->d_raw, sizeof(float) * m->raw_floats);
     if (e == hipSuccess) e = hipMalloc(&m->d_frag, m->frag_bytes);
@@ -944,6 +948,7 @@ int forward_bf16(savad_model* m, const sched::ForwardPlan& bp, const void* x, in
 int prepare_f32s_launch(savad_model* m) {
     int rc;
     if (m->lds_attrs3_set) return SAVAD_OK;
+    if ((rc = allow_lds(fs::input_qkv_kernel_f32s_plain, fs::NRING3 * fs::SLOT_BYTES + 3 * D * 4))) return rc;
     if ((rc = allow_lds(fs::input_qkv_kernel_f32s, fs::NRING3 * fs::SLOT_BYTES + 3 * D * 4))) return rc;
     if ((rc = allow_lds(fs::attention_row_kernel_f32s<false, false>, fs::ROW_LDS_BYTES))) return rc;
     if ((rc = allow_lds(fs::attention_row_kernel_f32s<true, false>, fs::ROW_LDS_BYTES))) return rc;
@@ -1011,9 +1016,11 @@ int forward_f32s(savad_model* m, const sched::ForwardPlan& bp, const float* x, i
     }
     char* sets[2][3] = {{W + bp.q, W + bp.k, W + bp.v}, {W + bp.q2, W + bp.k2, W + bp.v2}};
     const bool packed = !bp.fold_v;  // the T <= 32 form of the launch: the plain Q/K/V images and its own out-projection
-    auto wqkv3 = [&](int l) { return Fr + (packed ? m->lf3[l].wqkv : m->lf3[l].wqkv_vo); };
-    auto bqkv3 = [&](int l) { return P + (packed ? m->lp[l].bqkv : m->lp[l].bqkv_vo); };
-    hipLaunchKernelGGL(fs::input_qkv_kernel_f32s, dim3(bp.nblk_pad / 4), dim3(256), fs::NRING3 * fs::SLOT_BYTES + 3 * D * 4, st, x, xbs, B, T, F,
+    // (bp.fold_v: the image Wq~ | Wo Wv' -- four slots, the keys are the normalised rows -- and its biases bq~ | Wo bv')
+    auto wqkv3 = [&](int l) { return Fr + (packed ? m->lf3[l].wqkv : m->lf3[l].wq_vo); };
+    auto bqkv3 = [&](int l) { return P + (packed ? m->lp[l].bqkv : m->lp[l].bq_vo); };
+    const auto input_qkv = packed ? fs::input_qkv_kernel_f32s_plain : fs::input_qkv_kernel_f32s;
+    hipLaunchKernelGGL(input_qkv, dim3(bp.nblk_pad / 4), dim3(256), fs::NRING3 * fs::SLOT_BYTES + 3 * D * 4, st, x, xbs, B, T, F,
                        bp.nblk, Fr + m->f3_win, R + m->r_bin, m->d_pe, wqkv3(0), bqkv3(0), hb, sets[0][0], sets[0][1], sets[0][2], c);
     prof.mark("input_qkv_f32s");
     const int NG = bp.NG;

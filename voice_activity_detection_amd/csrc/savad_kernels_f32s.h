@@ -33,9 +33,11 @@
 //
 // Wvo = Wo Wv' and bvo = Wo bv' depend on the weights alone and are built once when the weights are packed (fold_vo_kernel, fp64 sums
 // rounded once; a second Q / K / V image per layer with Wvo in the V position).  P V then IS the out-projected context: a launch's stream
-// is  K(0) | [V(j)^T, K(j+1)] x key tiles | W1 / W2 chunks (16 slots) | next layer's Wq, Wk, Wvo (6 slots; none in the last layer)  --
-// no Wo slots, no split of the context into operand triples; the row chain starts at h1 = h + bo + O / l.  The T <= 32 kernels keep
-// the plain images and their out-projection.
+// is  K(0) | [V(j)^T, K(j+1)] x key tiles | W1 / W2 chunks (16 slots) | next layer's Wq~, Wvo (4 slots; none in the last layer)  --
+// no Wo slots, no split of the context into operand triples; the row chain starts at h1 = h + bo + O / l.  The key projection is
+// folded into the query the same way (fold_qk_kernel: the term of a score that the fold drops is the same for every key of a row, and
+// the softmax removes it), so that a key is the normalised row itself: no Wk slots, no K bias, no scaling of Q at run time.  The
+// T <= 32 kernels keep the plain images and their out-projection.
 //
 // Reference being restated: vad/models/self_attention.py:23-28, vad/modeling/transformer.py:24-61,227-238,258-363,366-382.
 #pragma once
@@ -260,9 +262,14 @@ struct Ring3 {
 // consume them, with counted lgkmcnt waits (the compiler keeps two fragments in flight and waits out an LDS round trip every few
 // MFMAs; LDS data returns in order and scalar-memory returns can only add to what a counted wait has seen complete, so "at most six
 // outstanding" means the older six have landed).  DMA: the twelve pieces of `job` go out between the K-steps.
-template <bool SWAP, bool DMA>
+// MID: mid(K-step) runs in the middle of every K-step's twelve MFMAs (the K stores of the folded streams; nothing elsewhere).
+struct NoMid {
+    template <int KS>
+    __device__ __forceinline__ void operator()(std::integral_constant<int, KS>) const {}
+};
+template <bool SWAP, bool DMA, class Mid = NoMid>
 __device__ __forceinline__ void gemm_slot(f32x16& acc0, f32x16& acc1, const char* slot, const Tri (&xp)[8], const Ring3& ring,
-                                          const DmaJob& job) {
+                                          const DmaJob& job, const Mid& mid = Mid{}) {
     if (SAVAD_ABLATE & 8) {
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) mfma6x2<SWAP>(acc0, acc1, xp[7 - ks], xp[ks ^ 1], xp[ks]);
@@ -285,6 +292,7 @@ __device__ __forceinline__ void gemm_slot(f32x16& acc0, f32x16& acc1, const char
                       __builtin_bit_cast(bf16x8, f[(ks) & 1][5])};                                                            \
         mfma6x2_lo<SWAP>(acc0, acc1, w0_, w1_, xp[ks]);                                                                       \
         if constexpr (DMA && (P1) >= 0) ring.template piece<((P1) >= 0 ? (P1) : 0)>(job);                                     \
+        mid(std::integral_constant<int, (ks)>{});                                                                             \
         mfma6x2_hi<SWAP>(acc0, acc1, w0_, w1_, xp[ks]);                                                                       \
         if constexpr (DMA) ring.template piece<P0>(job);                                                                      \
     }
@@ -323,9 +331,9 @@ __global__ void pack_weight_frags3_kernel(const float* __restrict__ W, int N, in
 // The out-projection folded into the value projection.  The encoder has ONE head (vad/models/self_attention.py:17-18), and a softmax
 // row sums to 1, so final_projection(P (x Wv'^T + bv')) = P (x (Wo Wv')^T + Wo bv') + bo: with Wvo = Wo Wv' and bvo = Wo bv' in the V
 // position, P V already is the out-projected context.  Sums in fp64, rounded once.  Block n = row of Wvo, thread k = its column (D x D
-// threads); bqkv_vo = bq' | bk' | bvo.
+// threads).
 __global__ void fold_vo_kernel(const float* __restrict__ Wo, const float* __restrict__ Wv, const float* __restrict__ bqkv,
-                               float* __restrict__ Wvo, float* __restrict__ bqkv_vo) {
+                               float* __restrict__ Wvo, float* __restrict__ bvo) {
     const int n = blockIdx.x, k = threadIdx.x;
     double acc = 0.0, accb = 0.0;
     for (int j = 0; j < D; ++j) {
@@ -334,43 +342,118 @@ __global__ void fold_vo_kernel(const float* __restrict__ Wo, const float* __rest
         accb += w * (double)bqkv[2 * D + j];
     }
     Wvo[(size_t)n * D + k] = (float)acc;
-    if (k == 0) bqkv_vo[2 * D + n] = (float)accb;
-    if (n < 2) bqkv_vo[n * D + k] = bqkv[n * D + k];
+    if (k == 0) bvo[n] = (float)accb;
 }
 
-// One of the six QKV slots: slot S covers n-blocks 2 (S & 1), 2 (S & 1) + 1 of projection rb = S >> 1 (0 query, 1 key:
-// transposed form; 2 value: swapped form -> V^T).  Q is stored PRE-SCALED by qscale = log2(e) / sqrt(D).
-template <int S, bool DMA>
-__device__ __forceinline__ void qkv_slot(const char* slot, const Tri (&xp)[8], const float* lbq, char* __restrict__ qf, char* __restrict__ kf,
-                                         char* __restrict__ vtf, int blk, const Ring3& ring, const DmaJob& job, float qscale, bool live) {
+// The key projection folded into the query.  With x^ the normalised row the kernels hold in registers behind layernorm_regs, Wq', bq',
+// Wk', bk' the LayerNorm-folded projections ([out][in]) and c = log2(e) / sqrt(D), the score of query row i and key row j is
+//
+//      s_ij = c (Wq' x^_i + bq') . (Wk' x^_j + bk')  =  [c Wk'^T (Wq' x^_i + bq')] . x^_j  +  c (Wq' x^_i + bq') . bk'
+//
+// The second term does not depend on the key j: it is the same shift for every score of row i, and the softmax over the keys removes
+// it.  So with
+//
+//      Wq~[n][k] = c sum_o Wk'[o][n] Wq'[o][k],        bq~[n] = c sum_o Wk'[o][n] bq'[o]
+//
+// the query is q~_i = Wq~ x^_i + bq~ and the KEY IS x^_j ITSELF: no K projection, no K bias, no scaling of Q at run time.  Sums and c
+// in fp64, rounded once.  Block n = row of Wq~, thread k = its column (D x D threads).
+__global__ void fold_qk_kernel(const float* __restrict__ Wq, const float* __restrict__ Wk, const float* __restrict__ bq, double c,
+                               float* __restrict__ Wqt, float* __restrict__ bqt) {
+    const int n = blockIdx.x, k = threadIdx.x;
+    double acc = 0.0, accb = 0.0;
+    for (int o = 0; o < D; ++o) {
+        const double w = (double)Wk[(size_t)o * D + n];
+        acc += w * (double)Wq[(size_t)o * D + k];
+        accb += w * (double)bq[o];
+    }
+    Wqt[(size_t)n * D + k] = (float)(c * acc);
+    if (k == 0) bqt[n] = (float)(c * accb);
+}
+
+// One slot of a Q/K/V image: n-blocks 2 HALF, 2 HALF + 1 of projection RB (0 query, 1 key: transposed form; 2 value: swapped form ->
+// V^T), whose D biases start at lb and whose triples go to dst.  SCALE: the result is stored PRE-SCALED by qscale = log2(e) / sqrt(D)
+// (the plain query; Wq~ carries the factor).  The plain image is Wq' | Wk' | Wv' (six slots), the folded one Wq~ | Wvo (four).
+template <int RB, int HALF, bool DMA, bool SCALE, class Mid = NoMid>
+__device__ __forceinline__ void qkv_slot(const char* slot, const Tri (&xp)[8], const float* lb, char* __restrict__ dst, int blk,
+                                         const Ring3& ring, const DmaJob& job, float qscale, bool live, const Mid& mid = Mid{}) {
     const int lane = ring.lane, n = lane & 31, h = lane >> 5;
-    constexpr int rb = S >> 1, nb0 = 2 * (S & 1);
+    constexpr int nb0 = 2 * HALF;
     f32x16 acc[2];
-    if constexpr (rb < 2) {
+    if constexpr (RB < 2) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) acc[i] = bias_block(lbq + D * rb + 32 * (nb0 + i), h);
-        gemm_slot<false, DMA>(acc[0], acc[1], slot, xp, ring, job);
+        for (int i = 0; i < 2; ++i) acc[i] = bias_block(lb + 32 * (nb0 + i), h);
+        gemm_slot<false, DMA>(acc[0], acc[1], slot, xp, ring, job, mid);
     } else {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const float bv = lbq[2 * D + 32 * (nb0 + i) + n];  // lane = output feature
+            const float bv = lb[32 * (nb0 + i) + n];  // lane = output feature
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][r] = bv;
         }
-        gemm_slot<true, DMA>(acc[0], acc[1], slot, xp, ring, job);
+        gemm_slot<true, DMA>(acc[0], acc[1], slot, xp, ring, job, mid);
     }
-    if constexpr (rb == 0) {
+    if constexpr (SCALE) {
         acc[0] *= qscale;
         acc[1] *= qscale;
     }
     if (!live) return;
-    char* dst = rb == 0 ? qf : (rb == 1 ? kf : vtf);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
             sttri(dst + (size_t)blk * BLK3_BYTES + (2 * (nb0 + i) + j) * TFRAG_BYTES + lane * 16, split_half(acc[i], j));
 }
+// Slot S of the image a launch streams.  QKF (the folded image, T > 32): slots 0, 1 are Wq~ and 2, 3 Wvo, biases bq~ | bvo; otherwise
+// slots 2 rb, 2 rb + 1 are projection rb of Wq' | Wk' | Wv', biases bq' | bk' | bv'.
+template <int S, bool QKF, bool DMA, class Mid = NoMid>
+__device__ __forceinline__ void qkv_image_slot(const char* slot, const Tri (&xp)[8], const float* lbq, char* __restrict__ qf, char* __restrict__ kf,
+                                               char* __restrict__ vtf, int blk, const Ring3& ring, const DmaJob& job, float qscale, bool live,
+                                               const Mid& mid = Mid{}) {
+    constexpr int pos = S >> 1, rb = QKF ? 2 * pos : pos;
+    qkv_slot<rb, (S & 1), DMA, (rb == 0 && !QKF)>(slot, xp, lbq + D * pos, rb == 0 ? qf : (rb == 1 ? kf : vtf), blk, ring, job, qscale, live, mid);
+}
+
+// The folded streams' keys: K IS the normalised row, whose operand triples xp the wave holds anyway (split_row: K-step ks of xp has the
+// feature order and lane layout of K-step ks of a K image -- feature 16 ks + 8 (e >> 2) + 4 h + (e & 3), lane = row -- compare split_half
+// in qkv_slot).  Eight triples = 24 vector stores per block.  They count in vmcnt and retire in order, so where they sit in the stream
+// decides what the next ring wait has to wait for; SAVAD_KSTORE picks the place (measured: DESIGN 4k)
+//   0: in one burst behind split_row, in front of the wait for the first Wq~ slot
+//   1: in one burst behind that wait
+//   2: dealt into the first Wq~ slot: two triples in the middle of each odd K-step (the even ones have a DMA piece there)
+//   3: dealt into both Wq~ slots: one triple in the middle of each odd K-step
+#ifndef SAVAD_KSTORE
+#define SAVAD_KSTORE 2
+#endif
+__device__ __forceinline__ void store_k_tri(char* kblk /* the block's K image */, const Tri (&xp)[8], int ks, int lane) {
+    sttri(kblk + ks * TFRAG_BYTES + lane * 16, xp[ks]);
+}
+__device__ __forceinline__ void store_k_burst(char* kblk, const Tri (&xp)[8], int lane, bool live) {
+    if (!live) return;
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) store_k_tri(kblk, xp, ks, lane);
+}
+template <int S>   // the mid-K-step hook of Wq~ slot S (0, 1)
+struct KStoreMid {
+    char* kblk;
+    const Tri (&xp)[8];
+    int lane;
+    bool live;
+    template <int KS>
+    __device__ __forceinline__ void operator()(std::integral_constant<int, KS>) const {
+        if constexpr ((KS & 1) && ((SAVAD_KSTORE == 2 && S == 0) || SAVAD_KSTORE == 3)) {
+            __builtin_amdgcn_sched_barrier(SAVAD_PIECE_FENCE);   // (as a DMA piece: the stores stay between the two groups of MFMAs)
+            if (live) {
+                if constexpr (SAVAD_KSTORE == 2) {
+                    store_k_tri(kblk, xp, KS - 1, lane);
+                    store_k_tri(kblk, xp, KS, lane);
+                } else {
+                    store_k_tri(kblk, xp, 4 * S + (KS >> 1), lane);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(SAVAD_PIECE_FENCE);
+        }
+    }
+};
 
 // features f0..f0+3 and f0+8..f0+11 of one input row -> the triple of an input K-step
 // (non-temporal: the features are read once; the 3.5 MB of weight triples every workgroup streams fill an XCD's 4 MB L2 almost alone,
@@ -437,14 +520,14 @@ __device__ __forceinline__ void input_gemm_f32s(f32x16 (&h0)[4], const float* xr
 // ---------------------------------------------------------------------------------------------
 // Kernel 1 (fp32s): input Linear + PE -> h -> LN -> Q, K, V^T triples.  4 waves = 4 blocks.
 // (vad/models/self_attention.py:12-16,24; vad/modeling/transformer.py:281-284,392-401)
+// QKF (T > 32, input_qkv_kernel_f32s): wqkv_frag / bqkv are the folded image Wq~ | Wvo and bq~ | bvo (fold_qk_kernel, fold_vo_kernel):
+// four slots, and K is the normalised row's own triples.  !QKF (T <= 32, input_qkv_kernel_f32s_plain): the plain image, six slots.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 1) void input_qkv_kernel_f32s(const float* __restrict__ x, long xbs, int B, int T, int F, int nblk,
-                                                                const char* __restrict__ win_frag, const float* __restrict__ bin,
-                                                                const float* __restrict__ pe, const char* __restrict__ wqkv_frag,
-                                                                const float* __restrict__ bqkv, float* __restrict__ hbuf,
-                                                                char* __restrict__ qf, char* __restrict__ kf, char* __restrict__ vtf,
-                                                                float qscale) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+template <bool QKF>
+__device__ __forceinline__ void input_qkv_f32s(char* smem, const float* __restrict__ x, long xbs, int B, int T, int F, int nblk,
+                                               const char* __restrict__ win_frag, const float* __restrict__ bin, const float* __restrict__ pe,
+                                               const char* __restrict__ wqkv_frag, const float* __restrict__ bqkv, float* __restrict__ hbuf,
+                                               char* __restrict__ qf, char* __restrict__ kf, char* __restrict__ vtf, float qscale) {
     float* lbq = reinterpret_cast<float*>(smem + NRING3 * SLOT_BYTES);
     const int lane = threadIdx.x & 63, m = lane & 31, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -454,7 +537,7 @@ __global__ __launch_bounds__(256, 1) void input_qkv_kernel_f32s(const float* __r
     SAVAD_STAMP(57);
     ring.issue_all(job(0));
     ring.issue_all(job(1));
-    stage_bias(lbq, bqkv, 3 * D);
+    stage_bias(lbq, bqkv, (QKF ? 2 : 3) * D);
     SAVAD_STAMP(58);
     size_t row;
     int t_frame;
@@ -480,16 +563,46 @@ __global__ __launch_bounds__(256, 1) void input_qkv_kernel_f32s(const float* __r
     split_row(xg, xp);
     SAVAD_STAMP(60);
     const DmaJob none{nullptr, 0u};
-#define SAVAD_IQ_STEP(T_)                                                                                                      \
-    ring.acquire<((T_) + 1 < 6) ? 1 : 0>();                                                                                    \
-    qkv_slot<T_, ((T_) + 2 < 6)>(ring.slot(T_), xp, lbq, qf, kf, vtf, blk, ring, (T_) + 2 < 6 ? job((T_) + 2) : none, qscale, live);
-    SAVAD_IQ_STEP(0) SAVAD_IQ_STEP(1)
-    SAVAD_STAMP(61);
-    SAVAD_IQ_STEP(2) SAVAD_IQ_STEP(3)
-    SAVAD_STAMP(62);
-    SAVAD_IQ_STEP(4) SAVAD_IQ_STEP(5)
-    SAVAD_STAMP(63);
+    constexpr int NS = QKF ? 4 : 6;
+    char* kblk = kf + (size_t)blk * BLK3_BYTES;
+#define SAVAD_IQ_STEP(T_, mid)                                                                                                 \
+    ring.acquire<((T_) + 1 < NS) ? 1 : 0>();                                                                                   \
+    if (QKF && SAVAD_KSTORE == 1 && (T_) == 0) store_k_burst(kblk, xp, lane, live);                                            \
+    qkv_image_slot<T_, QKF, ((T_) + 2 < NS)>(ring.slot(T_), xp, lbq, qf, kf, vtf, blk, ring, (T_) + 2 < NS ? job((T_) + 2) : none, qscale, \
+                                             live, mid);
+    if constexpr (QKF) {
+        if (SAVAD_KSTORE == 0) store_k_burst(kblk, xp, lane, live);
+        SAVAD_IQ_STEP(0, (KStoreMid<0>{kblk, xp, lane, live})) SAVAD_IQ_STEP(1, (KStoreMid<1>{kblk, xp, lane, live}))
+        SAVAD_STAMP(61);
+        SAVAD_IQ_STEP(2, NoMid{}) SAVAD_IQ_STEP(3, NoMid{})
+        SAVAD_STAMP(63);
+    } else {
+        SAVAD_IQ_STEP(0, NoMid{}) SAVAD_IQ_STEP(1, NoMid{})
+        SAVAD_STAMP(61);
+        SAVAD_IQ_STEP(2, NoMid{}) SAVAD_IQ_STEP(3, NoMid{})
+        SAVAD_STAMP(62);
+        SAVAD_IQ_STEP(4, NoMid{}) SAVAD_IQ_STEP(5, NoMid{})
+        SAVAD_STAMP(63);
+    }
 #undef SAVAD_IQ_STEP
+}
+__global__ __launch_bounds__(256, 1) void input_qkv_kernel_f32s(const float* __restrict__ x, long xbs, int B, int T, int F, int nblk,
+                                                                const char* __restrict__ win_frag, const float* __restrict__ bin,
+                                                                const float* __restrict__ pe, const char* __restrict__ wqkv_frag,
+                                                                const float* __restrict__ bqkv, float* __restrict__ hbuf,
+                                                                char* __restrict__ qf, char* __restrict__ kf, char* __restrict__ vtf,
+                                                                float qscale) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    input_qkv_f32s<true>(smem, x, xbs, B, T, F, nblk, win_frag, bin, pe, wqkv_frag, bqkv, hbuf, qf, kf, vtf, qscale);
+}
+__global__ __launch_bounds__(256, 1) void input_qkv_kernel_f32s_plain(const float* __restrict__ x, long xbs, int B, int T, int F, int nblk,
+                                                                      const char* __restrict__ win_frag, const float* __restrict__ bin,
+                                                                      const float* __restrict__ pe, const char* __restrict__ wqkv_frag,
+                                                                      const float* __restrict__ bqkv, float* __restrict__ hbuf,
+                                                                      char* __restrict__ qf, char* __restrict__ kf, char* __restrict__ vtf,
+                                                                      float qscale) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    input_qkv_f32s<false>(smem, x, xbs, B, T, F, nblk, win_frag, bin, pe, wqkv_frag, bqkv, hbuf, qf, kf, vtf, qscale);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -676,10 +789,11 @@ __device__ __forceinline__ void attn_tile3_global(AttnState& st, const Tri (&qp)
 // vad/models/self_attention.py:26-27): out-projection + residual -> LN -> FFN + residual -> next layer's LN + Q/K/V^T, or
 // the encoder LayerNorm + classifier + LogSoftmax.  Weight stream = slots (two n-blocks per slot, at ring positions base + t)
 //   !FOLDED (T <= 32):  0,1: Wo | 2+4c, 3+4c: W1 chunk c | 4+4c, 5+4c: W2 chunk c (c = 0..3) | 18..23: Wq, Wk, Wv      24, LAST 18
-//   FOLDED  (T > 32):   4c, 4c+1: W1 chunk c | 4c+2, 4c+3: W2 chunk c (c = 0..3) | 16..21: Wq, Wk, Wvo                  22, LAST 16
+//   FOLDED  (T > 32):   4c, 4c+1: W1 chunk c | 4c+2, 4c+3: W2 chunk c (c = 0..3) | 16..19: Wq~, Wvo                     20, LAST 16
 // FOLDED: V was projected with Wo Wv' (fold_vo_kernel), the caller's attention accumulators hc already are the out-projected context
 // and its residual block hr is in flight (request_hblock32); slots 0 and 1 are in flight too (the fused launch requests them under
-// its last two key tiles, so that the chain does not start with an exposed DMA round trip).
+// its last two key tiles, so that the chain does not start with an exposed DMA round trip).  The next layer's query is projected with
+// Wq~ = c Wk'^T Wq' (fold_qk_kernel) and its keys are the normalised rows themselves: no Wk slots, the K image is xp as it stands.
 // ---------------------------------------------------------------------------------------------
 struct RowArgs3 {
     int B, T, nblk;
@@ -690,9 +804,9 @@ struct RowArgs3 {
     const float* b1;
     const char* w2_frag;
     const float* b2;
-    const char* wn_frag;  // !LAST: next layer's Wqkv' triples (FOLDED: the image with Wo Wv' in the V position)
+    const char* wn_frag;  // !LAST: next layer's Wqkv' triples (FOLDED: its Wq~ | Wvo triples)
     const float* wc;      // LAST: Wc' fp32 [2][D]
-    const float* bn;      // !LAST: bqkv' [384] (FOLDED: bq' | bk' | Wo bv'); LAST: bc' [2]
+    const float* bn;      // !LAST: bqkv' [384] (FOLDED: bq~ | Wo bv' [256]); LAST: bc' [2]
     char *qf, *kf, *vtf;  // !LAST: written (the NEXT layer's buffers)
     float* out;           // LAST
     float qscale;
@@ -714,7 +828,7 @@ __device__ __forceinline__ const char* row_seg(const RowArgs3& A, int t, int sgm
 
 // the row chain's biases (LAST: the classifier's folded weights and bias in the Q/K/V slot) -> LDS behind the ring; called at the head
 // of the kernel, so that their round trip to memory is long over when the chain starts; published by any workgroup barrier
-template <bool LAST>
+template <bool LAST, bool FOLDED>
 struct RowBiases {
     BiasPiece pieces[4];
     BiasRegs<4> regs;
@@ -728,7 +842,7 @@ struct RowBiases {
         pieces[0] = BiasPiece{lbo, A.bo, D};
         pieces[1] = BiasPiece{lb1, A.b1, DFF};
         pieces[2] = BiasPiece{lb2, A.b2, D};
-        pieces[3] = BiasPiece{lbn, LAST ? A.wc : A.bn, LAST ? 2 * D : 3 * D};
+        pieces[3] = BiasPiece{lbn, LAST ? A.wc : A.bn, (LAST || FOLDED) ? 2 * D : 3 * D};
         regs = request_bias_pieces(pieces);
         bc = LAST ? A.bn[threadIdx.x & 1] : 0.0f;
     }
@@ -747,7 +861,7 @@ __device__ __forceinline__ void row_stage_f32s(const RowArgs3& A, char* smem, Tr
     float* lbn = lb2 + D;
     const int lane = ring.lane, m = lane & 31, h = lane >> 5;
     constexpr int OFF = FOLDED ? 0 : 2;   // slots in front of the FFN's: Wo
-    constexpr int NSLOT = OFF + (LAST ? 16 : 22);
+    constexpr int NSLOT = OFF + (LAST ? 16 : FOLDED ? 20 : 22);
     auto job = [&](int t) { return ring.job(base + t, row_seg(A, t, 0, FOLDED), row_seg(A, t, 1, FOLDED)); };
     const DmaJob none{nullptr, 0u};
     // acquire slot T_, then acc0 / acc1 += slot . operand with the DMA of slot T_ + 2 between the MFMAs
@@ -823,12 +937,21 @@ __device__ __forceinline__ void row_stage_f32s(const RowArgs3& A, char* smem, Tr
     if constexpr (!LAST) {
         split_row(xg, xp);
         SAVAD_STAMP(11);
-#define SAVAD_ROW_QKV(S_)                                                                                                     \
+        char* kblk = A.kf + (size_t)blk * BLK3_BYTES;
+#define SAVAD_ROW_QKV(S_, mid)                                                                                                \
     ring.acquire<(OFF + 16 + (S_) + 1 < NSLOT) ? 1 : 0>();                                                                    \
-    qkv_slot<S_, (OFF + 16 + (S_) + 2 < NSLOT)>(ring.slot(base + OFF + 16 + (S_)), xp, lbn, A.qf, A.kf, A.vtf, blk, ring,     \
-                                                OFF + 16 + (S_) + 2 < NSLOT ? job(OFF + 16 + (S_) + 2) : none, A.qscale, live); \
+    if (FOLDED && SAVAD_KSTORE == 1 && (S_) == 0) store_k_burst(kblk, xp, lane, live);                                        \
+    qkv_image_slot<S_, FOLDED, (OFF + 16 + (S_) + 2 < NSLOT)>(ring.slot(base + OFF + 16 + (S_)), xp, lbn, A.qf, A.kf, A.vtf, blk, ring, \
+                                                              OFF + 16 + (S_) + 2 < NSLOT ? job(OFF + 16 + (S_) + 2) : none, A.qscale, live, mid); \
     SAVAD_STAMP(12 + (S_));
-        SAVAD_ROW_QKV(0) SAVAD_ROW_QKV(1) SAVAD_ROW_QKV(2) SAVAD_ROW_QKV(3) SAVAD_ROW_QKV(4) SAVAD_ROW_QKV(5)
+        if constexpr (FOLDED) {   // Wq~ (the K stores ride in its slots), Wvo
+            if (SAVAD_KSTORE == 0) store_k_burst(kblk, xp, lane, live);
+            SAVAD_ROW_QKV(0, (KStoreMid<0>{kblk, xp, lane, live})) SAVAD_ROW_QKV(1, (KStoreMid<1>{kblk, xp, lane, live}))
+            SAVAD_ROW_QKV(2, NoMid{}) SAVAD_ROW_QKV(3, NoMid{})
+        } else {
+            SAVAD_ROW_QKV(0, NoMid{}) SAVAD_ROW_QKV(1, NoMid{}) SAVAD_ROW_QKV(2, NoMid{}) SAVAD_ROW_QKV(3, NoMid{}) SAVAD_ROW_QKV(4, NoMid{})
+            SAVAD_ROW_QKV(5, NoMid{})
+        }
 #undef SAVAD_ROW_QKV
     } else {
         float z0 = 0.0f, z1 = 0.0f;
@@ -883,7 +1006,7 @@ __global__ __launch_bounds__(256, 1) void attention_row_kernel_f32s(const char* 
         g_savad_wg[blockIdx.x][2] = __builtin_amdgcn_s_memrealtime();
     }
 #endif
-    const RowBiases<LAST> biases(A, smem);   // requested first: their round trip is over long before the row chain wants them
+    const RowBiases<LAST, !PACKED> biases(A, smem);   // requested first: their round trip is over long before the row chain wants them
     if constexpr (PACKED) {
         biases.commit();
         blk_q = blockIdx.x * 4 + w;
