@@ -386,6 +386,51 @@ int savad_post_sample_class_host(const uint8_t* frames, int n, int sample_rate, 
                                  long count, uint8_t* cls);
 int savad_post_set_block(int elems);
 
+/* The metrics of the evaluate command ON THE DEVICE (csrc/savad_eval_device.h).  Every one of the 18 values of a file
+ * (vad/evaluate.py:56-80) is a float64 expression of integers -- confusion counts, edge counts, a rank sum and per-boundary hit
+ * counts -- so only those integers are computed here and return to the host; metrics.metrics_from_counts turns them into the
+ * values of the host path, bit for bit.  Everything works on n = min(N, n_labels) frames.
+ *   counters [SAVAD_EVAL_COUNTERS] (int64): SAVAD_EVAL_N = n; _POS = labels that are 1; _TRUE = true segments (rising edges of the
+ *       labels, a 1 at frame 0 included); _NAN = frames whose boosted or single score is NaN; _BAD_LABEL = labels above 1 (with
+ *       either above zero the other values mean nothing: use the host path); _U2 = twice the Mann-Whitney U of the boosted
+ *       scores (mean of a row, numpy's float32 bits) with mid-ranks for ties, -0.0 equal to +0.0; then for the single
+ *       prediction (probs[i][W / 2] > threshold) at SAVAD_EVAL_PRED and for the boosted one (mean > threshold) at
+ *       SAVAD_EVAL_PRED + SAVAD_EVAL_PRED_STRIDE: TP, FP, FN, TN and the prediction's rising edges.
+ *   seg [count x 8] (uint8), in the order of the true segments: (num, den) of the start boundary and (num, den) of the end
+ *       boundary for the single prediction, then the same four for the boosted one.  Start boundary b: den = the frames of
+ *       [b, min(b + L, n)), num = those where prediction == label; end boundary e: the frames of [max(e - L, 0), e].
+ *   savad_eval_supported        HOST arithmetic, 1 or 0: 1 <= W <= 128 and 1 <= n < 2^31.
+ *   savad_eval_workspace_bytes  the workspace of savad_eval_counts for n_frames frames, and of savad_eval_sort for n_frames elements.
+ *   savad_eval_counts           probs [N, W] float32, labels [n_labels] uint8, workspace: DEVICE; counters, seg: HOST.  1 <= L <= 254
+ *                               (5 in the reference).  Returns the number of true segments (their records are written), or a
+ *                               negative code; seg_cap below that number is SAVAD_E_INVALID.  SYNCHRONISES `stream` (twice when
+ *                               there are segments).  No allocation.
+ *   savad_eval_sort             DEVICE pointers; the stable sort alone, on the kernels and the key mapping of savad_eval_counts:
+ *                               sorted_keys = keys in ascending order of value (a -0.0 comes back as +0.0), sorted_labels = their
+ *                               payload bytes.  Asynchronous.
+ *   savad_eval_counts_host      HOST twin for the CPU tests: the same outputs from host pointers by the same inline functions,
+ *                               std::stable_sort in place of the radix passes.
+ *   savad_eval_set_block        process-wide test knob: elements per workgroup block of the sort and its scans, 0 (default) or a
+ *                               power of two from 64 to the default 2048. */
+#define SAVAD_EVAL_COUNTERS 16
+#define SAVAD_EVAL_N 0
+#define SAVAD_EVAL_POS 1
+#define SAVAD_EVAL_TRUE 2
+#define SAVAD_EVAL_NAN 3
+#define SAVAD_EVAL_BAD_LABEL 4
+#define SAVAD_EVAL_U2 5
+#define SAVAD_EVAL_PRED 6
+#define SAVAD_EVAL_PRED_STRIDE 5 /* TP, FP, FN, TN, rising edges */
+int savad_eval_supported(int W, long n_frames, long n_labels);
+int savad_eval_workspace_bytes(int n_frames, int W, size_t* bytes);
+long savad_eval_counts(const float* probs, int N, int W, const uint8_t* labels, long n_labels, float threshold, int L, long* counters,
+                       uint8_t* seg, long seg_cap, void* ws, size_t ws_bytes, void* stream);
+int savad_eval_sort(const float* keys, const uint8_t* labels, long n, float* sorted_keys, uint8_t* sorted_labels, void* ws,
+                    size_t ws_bytes, void* stream);
+long savad_eval_counts_host(const float* probs, int N, int W, const uint8_t* labels, long n_labels, float threshold, int L,
+                            long* counters, uint8_t* seg, long seg_cap);
+int savad_eval_set_block(int elems);
+
 const char* savad_last_error(void);
 const char* savad_version(void);
 

@@ -62,6 +62,10 @@ def main(argv=None) -> int:
     e.add_argument("--device-ingest", action="store_true",
                    help="average the channels and resample to 16 kHz on the GPU (the file's samples are uploaded as stored) instead "
                         "of on the host: pays for every recording that is not 16 kHz mono")
+    e.add_argument("--device-metrics", action="store_true",
+                   help="compute a file's metrics on the GPU (same values; the labels go up and a few hundred bytes come back instead "
+                        "of the probability matrix going down): pays for long recordings, a short clip is launch-bound")
+    e.add_argument("--precision", choices=("fp32", "fp32s", "bf16"), default="fp32", help="as for predict")
     args = ap.parse_args(argv)
 
     if args.command == "evaluate":
@@ -69,7 +73,7 @@ def main(argv=None) -> int:
 
         evaluate_vad_from_scratch(args.eval_path, args.checkpoint_path, args.output_path, args.data_dir, args.threshold,
                                   args.shuffle, args.limit, args.random_seed, args.device, extended_front_end=args.extended_front_end,
-                                  device_ingest=args.device_ingest)
+                                  device_ingest=args.device_ingest, device_metrics=args.device_metrics, precision=args.precision)
         return 0
 
     from .predictor import VADFromScratchPredictor, VADPredictParameters

@@ -93,6 +93,13 @@ SYMBOLS = {
     "savad_post_frames_host": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "savad_post_sample_class_host": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_long, c_long, c_void_p]),
     "savad_post_set_block": (c_int, [c_int]),
+    "savad_eval_supported": (c_int, [c_int, c_long, c_long]),
+    "savad_eval_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "savad_eval_counts": (c_long, [c_void_p, c_int, c_int, c_void_p, c_long, c_float, c_int, c_void_p, c_void_p, c_long, c_void_p, c_size_t,
+                                   c_void_p]),
+    "savad_eval_sort": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "savad_eval_counts_host": (c_long, [c_void_p, c_int, c_int, c_void_p, c_long, c_float, c_int, c_void_p, c_void_p, c_long]),
+    "savad_eval_set_block": (c_int, [c_int]),
     "savad_last_error": (c_char_p, []),
     "savad_version": (c_char_p, []),
 }

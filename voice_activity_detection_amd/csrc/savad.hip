@@ -15,6 +15,7 @@
 #include "savad_ingest.h"
 #include "savad_post.h"
 #include "savad_post_device.h"
+#include "savad_eval_device.h"
 #include "savad_schedule.h"
 
 #include <math.h>
@@ -2520,6 +2521,157 @@ SAVAD_EXPORT int savad_post_sample_class_host(const uint8_t* frames, int n, int 
     if ((n > 0 && !frames) || !cls) return fail(SAVAD_E_INVALID, "null pointer");
     for (long i = 0; i < count; ++i) cls[i] = pd::sample_class(frames, g, first + i);
     return SAVAD_OK;
+}
+
+// ---- evaluate's metrics on the device (savad_eval_device.h) --------------------------------------------------------------------
+namespace {
+
+namespace ed = savad::evaldev;
+
+int g_eval_block = 0;   // savad_eval_set_block: elements per workgroup block of the sort and of its scans (0 = the default)
+
+int eval_block() { return g_eval_block ? g_eval_block : ed::SORT_BLOCK_DEFAULT; }
+
+struct EvalLayout {   // byte offsets into the caller's workspace: a function of the frame count alone
+    size_t keys_a, keys_b, y, labels_a, labels_b, spred, bpred, table, sums, scan, seg, counters, total;
+    long seg_cap;     // records of the boundary buffer: a true segment needs a frame of its own and a gap
+};
+
+EvalLayout eval_layout(long N) {
+    EvalLayout L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t n = (size_t)N;
+    L.keys_a = take(sizeof(uint32_t) * n);
+    L.keys_b = take(sizeof(uint32_t) * n);
+    L.y = take(n);
+    L.labels_a = take(n);
+    L.labels_b = take(n);
+    L.spred = take(n);
+    L.bpred = take(n);
+    L.table = take(sizeof(unsigned) * (size_t)ed::sort_table_elems(N));
+    const size_t sums_sort = sizeof(unsigned) * (size_t)pd::scan_sums_elems(ed::sort_table_elems(N));
+    const size_t sums_frames = sizeof(pd::Long2) * (size_t)pd::scan_sums_elems(N);   // (Long2 is the larger of the two frame scans' types)
+    L.sums = take(sums_sort > sums_frames ? sums_sort : sums_frames);
+    L.scan = take(sizeof(ed::HeadNeg) * n);
+    L.seg_cap = (N + 1) / 2;
+    L.seg = take((size_t)ed::SEG_BYTES * (size_t)L.seg_cap);
+    L.counters = take(sizeof(long) * ed::COUNTERS);
+    L.total = off;
+    return L;
+}
+
+long eval_frames(long n_frames, long n_labels) { return n_frames < n_labels ? n_frames : n_labels; }
+
+int eval_check(int W, long n_frames, long n_labels, int L) {
+    if (n_frames < 0 || n_labels < 0 || W < 1) return fail(SAVAD_E_INVALID, "N = %ld, labels = %ld, W = %d", n_frames, n_labels, W);
+    if (L < 1 || L > ed::L_MAX) return fail(SAVAD_E_INVALID, "L = %d (1 .. %d)", L, ed::L_MAX);
+    if (!savad_eval_supported(W, n_frames, n_labels))
+        return fail(SAVAD_E_UNSUPPORTED, "W = %d, %ld frames, %ld labels: the device metrics take 1 <= W <= %d and 1 <= min(frames, labels) < 2^31", W,
+                    n_frames, n_labels, pd::W_MAX);
+    return SAVAD_OK;
+}
+
+}  // namespace
+
+SAVAD_EXPORT int savad_eval_supported(int W, long n_frames, long n_labels) {
+    const long n = eval_frames(n_frames, n_labels);
+    return W >= 1 && W <= pd::W_MAX && n >= 1 && n < 2147483648L ? 1 : 0;
+}
+
+SAVAD_EXPORT int savad_eval_set_block(int elems) {
+    if (elems != 0 && (elems < pd::SCAN_BLOCK_MIN || elems > ed::SORT_BLOCK_DEFAULT || (elems & (elems - 1))))
+        return fail(SAVAD_E_INVALID, "sort block %d (0 = default, or a power of two from %d to %d)", elems, pd::SCAN_BLOCK_MIN, ed::SORT_BLOCK_DEFAULT);
+    g_eval_block = elems;
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_eval_workspace_bytes(int n_frames, int W, size_t* bytes) {
+    if (!bytes || n_frames < 0 || W < 1) return fail(SAVAD_E_INVALID, "bad argument");
+    if (W > pd::W_MAX) return fail(SAVAD_E_UNSUPPORTED, "W = %d: the device row mean has numpy's order up to %d", W, pd::W_MAX);
+    *bytes = eval_layout(n_frames).total;
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT long savad_eval_counts(const float* probs, int N, int W, const uint8_t* labels, long n_labels, float threshold, int L, long* counters,
+                                    uint8_t* seg, long seg_cap, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = eval_check(W, N, n_labels, L))) return rc;
+    if (!probs || !labels || !counters || !ws || seg_cap < 0 || (seg_cap > 0 && !seg)) return fail(SAVAD_E_INVALID, "null pointer");
+    const int n = (int)eval_frames(N, n_labels);
+    const EvalLayout Y = eval_layout(N);
+    if (ws_bytes < Y.total) return fail(SAVAD_E_INVALID, "workspace of %zu bytes, %zu needed", ws_bytes, Y.total);
+    char* base = (char*)ws;
+    uint32_t* keys_a = (uint32_t*)(base + Y.keys_a);
+    uint32_t* keys_b = (uint32_t*)(base + Y.keys_b);
+    uint8_t* y = (uint8_t*)(base + Y.y);
+    uint8_t* labels_a = (uint8_t*)(base + Y.labels_a);
+    uint8_t* labels_b = (uint8_t*)(base + Y.labels_b);
+    uint8_t* spred = (uint8_t*)(base + Y.spred);
+    uint8_t* bpred = (uint8_t*)(base + Y.bpred);
+    unsigned* table = (unsigned*)(base + Y.table);
+    void* sums = base + Y.sums;
+    ed::HeadNeg* scan = (ed::HeadNeg*)(base + Y.scan);
+    uint8_t* d_seg = (uint8_t*)(base + Y.seg);
+    long* d_counters = (long*)(base + Y.counters);
+    const int block = eval_block();
+
+    HIP_TRY(hipMemsetAsync(d_counters, 0, sizeof(long) * ed::COUNTERS, st));
+    hipLaunchKernelGGL(ed::frames_kernel, dim3(grid_for(n)), dim3(256), 0, st, probs, W, labels, n, threshold, keys_a, y, spred, bpred, d_counters);
+    hipLaunchKernelGGL(ed::counts_kernel, dim3(grid_for(n)), dim3(256), 0, st, (const uint8_t*)y, (const uint8_t*)spred, (const uint8_t*)bpred, n, d_counters);
+    const ed::BoundaryLoad flags{y, n};
+    pd::scan_run<pd::OpSum2>(st, n, block, flags, ed::BoundaryStore{flags, spred, bpred, L, d_seg, Y.seg_cap}, (pd::Long2*)sums);
+    ed::sort_run(st, n, block, keys_a, keys_b, y, labels_a, labels_b, table, (unsigned*)sums);
+    pd::scan_run<ed::OpHeadNeg>(st, n, block, ed::HeadNegLoad{keys_a, labels_a}, pd::PtrStore<ed::HeadNeg>{scan}, (ed::HeadNeg*)sums);
+    hipLaunchKernelGGL(ed::u2_kernel, dim3(grid_for(n)), dim3(256), 0, st, (const uint32_t*)keys_a, (const uint8_t*)labels_a, (const ed::HeadNeg*)scan, n,
+                       d_counters);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(long) * ed::COUNTERS, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    counters[ed::C_N] = n;
+    const long n_true = counters[ed::C_TRUE];
+    if (n_true < 0 || n_true > Y.seg_cap) return fail(SAVAD_E_STATE, "%ld true segments in %d frames", n_true, n);
+    if (n_true > seg_cap) return fail(SAVAD_E_INVALID, "%ld true segments, room for %ld", n_true, seg_cap);
+    if (n_true > 0) {
+        HIP_TRY(hipMemcpyAsync(seg, d_seg, (size_t)ed::SEG_BYTES * (size_t)n_true, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return n_true;
+}
+
+SAVAD_EXPORT int savad_eval_sort(const float* keys, const uint8_t* labels, long n, float* sorted_keys, uint8_t* sorted_labels, void* ws, size_t ws_bytes,
+                                 void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (n < 0 || n >= 2147483648L) return fail(SAVAD_E_INVALID, "n = %ld", n);
+    if (n == 0) return SAVAD_OK;
+    if (!keys || !labels || !sorted_keys || !sorted_labels || !ws) return fail(SAVAD_E_INVALID, "null pointer");
+    const EvalLayout Y = eval_layout(n);
+    if (ws_bytes < Y.total) return fail(SAVAD_E_INVALID, "workspace of %zu bytes, %zu needed", ws_bytes, Y.total);
+    char* base = (char*)ws;
+    uint32_t* keys_a = (uint32_t*)(base + Y.keys_a);
+    uint8_t* labels_a = (uint8_t*)(base + Y.labels_a);
+    hipLaunchKernelGGL(ed::keys_kernel, dim3(grid_for(n)), dim3(256), 0, st, keys, n, keys_a);
+    ed::sort_run(st, n, eval_block(), keys_a, (uint32_t*)(base + Y.keys_b), labels, labels_a, (uint8_t*)(base + Y.labels_b), (unsigned*)(base + Y.table),
+                 (unsigned*)(base + Y.sums));
+    hipLaunchKernelGGL(ed::values_kernel, dim3(grid_for(n)), dim3(256), 0, st, (const uint32_t*)keys_a, (const uint8_t*)labels_a, n, sorted_keys, sorted_labels);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT long savad_eval_counts_host(const float* probs, int N, int W, const uint8_t* labels, long n_labels, float threshold, int L, long* counters,
+                                         uint8_t* seg, long seg_cap) {
+    int rc;
+    if ((rc = eval_check(W, N, n_labels, L))) return rc;
+    if (!probs || !labels || !counters || seg_cap < 0 || (seg_cap > 0 && !seg)) return fail(SAVAD_E_INVALID, "null pointer");
+    const int n = (int)eval_frames(N, n_labels);
+    const long n_true = ed::counts_host(probs, W, labels, n, threshold, L, counters, seg, seg_cap);
+    if (n_true > seg_cap) return fail(SAVAD_E_INVALID, "%ld true segments, room for %ld", n_true, seg_cap);
+    return n_true;
 }
 
 #ifdef SAVAD_TIMING

@@ -18,7 +18,7 @@ from typing import Callable, List, Optional
 import numpy as np
 
 from .data_models import VoiceActivity
-from .metrics import equal_error_rate, precision_recall, roc_auc, vad_accuracy
+from .metrics import EVAL_BAD_LABEL, EVAL_COUNTERS, EVAL_NAN, equal_error_rate, metrics_from_counts, precision_recall, roc_auc, vad_accuracy
 
 METRIC_KEYS = ("auc", "accuracy", "precision", "recall", "vacc", "sba", "eba", "bp", "eer")
 
@@ -56,6 +56,53 @@ def file_metrics(true_labels, all_frame_probabilities, threshold: float) -> "Ord
     return out
 
 
+BOUNDARY_HALF_WIDTH = 5   # vad_accuracy's L
+
+
+def _to_host(probs):
+    return probs.detach().cpu().numpy() if hasattr(probs, "detach") else np.asarray(probs)
+
+
+def file_metrics_device(true_labels, probs_dev, threshold: float) -> "OrderedDict[str, float]":
+    """file_metrics for probabilities that live on the GPU: [N, W] float32 tensor + label vector -> the same 18 values, bit for bit,
+    without the matrix leaving the device (savad_eval_counts: the labels go up, a block of integer counters and 8 bytes per true
+    segment come back; metrics.metrics_from_counts).  Falls back to file_metrics on the downloaded matrix, silently, when the
+    device path does not apply: no float32 [N, W] tensor on a HIP device, savad_eval_supported says no, labels that are no
+    0 .. 255 integers, or counters that report a NaN score or a label above 1."""
+    import ctypes
+
+    import torch
+
+    from . import _lib
+
+    y = np.asarray(true_labels)
+    p = probs_dev
+    if not (isinstance(p, torch.Tensor) and p.device.type == "cuda" and p.dtype == torch.float32 and p.dim() == 2):
+        return file_metrics(true_labels, _to_host(p), threshold)
+    N, W = int(p.shape[0]), int(p.shape[1])
+    lib = _lib.load()
+    labels = y.astype(np.uint8, copy=True) if y.ndim == 1 and y.dtype.kind in "biu" else None
+    if labels is None or not np.array_equal(labels, y) or not lib.savad_eval_supported(W, N, len(labels)):
+        return file_metrics(true_labels, _to_host(p), threshold)
+    p = p.contiguous()
+    n = min(N, len(labels))
+    counters = np.zeros(EVAL_COUNTERS, dtype=np.int64)
+    seg = np.empty(((n + 1) // 2, 8), dtype=np.uint8)
+    need = ctypes.c_size_t()
+    _lib.check(lib.savad_eval_workspace_bytes(N, W, ctypes.byref(need)))
+    with torch.cuda.device(p.device):
+        labels_dev = torch.from_numpy(labels).to(p.device)
+        ws = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=p.device)
+        count = lib.savad_eval_counts(ctypes.c_void_p(p.data_ptr()), N, W, ctypes.c_void_p(labels_dev.data_ptr()), len(labels), float(threshold),
+                                      BOUNDARY_HALF_WIDTH, ctypes.c_void_p(counters.ctypes.data), ctypes.c_void_p(seg.ctypes.data), len(seg),
+                                      ctypes.c_void_p(ws.data_ptr()), int(need.value), ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream))
+    if count < 0:
+        _lib.check(int(count))
+    if counters[EVAL_NAN] or counters[EVAL_BAD_LABEL]:
+        return file_metrics(true_labels, _to_host(p), threshold)
+    return metrics_from_counts(counters, seg[:count], n)
+
+
 def _report(title: str, m: dict) -> str:
     names = [("AUC", "auc"), ("Accuracy", "accuracy"), ("Precision", "precision"), ("Recall", "recall"), ("VACC", "vacc"),
              ("SBA", "sba"), ("EBA", "eba"), ("BP", "bp"), ("EER", "eer")]
@@ -69,22 +116,27 @@ def evaluate_vad_from_scratch(eval_path: Path, checkpoint_path: Optional[Path] =
                               data_dir: Optional[Path] = None, threshold: float = 0.5, shuffle: bool = False,
                               limit: Optional[int] = None, random_seed: int = 0, device: str = "cuda",
                               probabilities_fn: Optional[Callable[[Path], np.ndarray]] = None, echo=print,
-                              extended_front_end: bool = False, device_ingest: bool = False) -> dict:
+                              extended_front_end: bool = False, device_ingest: bool = False, device_metrics: bool = False,
+                              precision: str = "fp32") -> dict:
     """Arguments as vad/evaluate.py:20-29.  `probabilities_fn(audio_path) -> [N, W]` replaces checkpoint + GPU
     predictor (host-logic tests); otherwise the audio goes WAV -> the checkpoint's front-end -> predict_probabilities on
     `device` (`extended_front_end`: VADFromScratchPredictor.from_checkpoint).  `device_ingest`: a file's samples are uploaded as
-    stored, averaged over the channels and resampled to 16 kHz on the GPU (features.load_audio_device) instead of on the host."""
+    stored, averaged over the channels and resampled to 16 kHz on the GPU (features.load_audio_device) instead of on the host.
+    `device_metrics`: the probabilities stay on the GPU and a file's metrics come from file_metrics_device (same values; a
+    `probabilities_fn` that returns numpy keeps the host path).  `precision`: the model's ("fp32", "fp32s", "bf16")."""
     eval_path = Path(eval_path)
     if probabilities_fn is None:
         from .features import load_audio_device, load_wav_mono16k
         from .predictor import VADFromScratchPredictor
 
         predictor = VADFromScratchPredictor.from_checkpoint(checkpoint_path, device, extended_front_end=extended_front_end)
+        predictor.model.precision = precision
 
         def probabilities_fn(path):
-            if device_ingest:
-                return predictor.predict_probabilities(predictor.features(load_audio_device(path, predictor.device)))
-            return predictor.predict_probabilities(predictor.features(load_wav_mono16k(path)))
+            audio = load_audio_device(path, predictor.device) if device_ingest else load_wav_mono16k(path)
+            if device_metrics:
+                return predictor.predict_probabilities_device(predictor.features(audio))[0]
+            return predictor.predict_probabilities(predictor.features(audio))
 
     data_dir = eval_path.parent if data_dir is None else Path(data_dir)
     pairs = load_data_list(eval_path)
@@ -99,7 +151,7 @@ def evaluate_vad_from_scratch(eval_path: Path, checkpoint_path: Optional[Path] =
         audio_path = data_dir.joinpath(pair["audio_path"])
         voice_activity_path = data_dir.joinpath(pair["voice_activity_path"])
         true_labels = VoiceActivity.load(voice_activity_path).to_labels(100)
-        metrics = file_metrics(true_labels, probabilities_fn(audio_path), threshold)
+        metrics = (file_metrics_device if device_metrics else file_metrics)(true_labels, probabilities_fn(audio_path), threshold)
         echo(_report(str(pair["audio_path"]), metrics))
         result = OrderedDict(audio_path=str(audio_path), voice_activity_path=str(voice_activity_path))
         result.update(metrics)

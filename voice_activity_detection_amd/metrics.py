@@ -80,7 +80,10 @@ def roc_curve_points(labels, scores):
 
 def equal_error_rate(labels, scores) -> float:
     """vad/metrics.py:16-20: the x in [0,1] where 1 - x = TPR(x) on the linearly interpolated ROC."""
-    fpr, tpr = roc_curve_points(labels, scores)
+    return _eer_of_curve(*roc_curve_points(labels, scores))
+
+
+def _eer_of_curve(fpr, tpr) -> float:
     f = lambda x: 1.0 - x - np.interp(x, fpr, tpr)  # noqa: E731
     lo, hi = 0.0, 1.0
     for _ in range(200):  # bisection (the reference uses scipy.optimize.brentq; same root to 1e-12)
@@ -97,3 +100,75 @@ def precision_recall(labels, predictions):
     predictions = np.asarray(predictions).astype(bool)
     tp = float((labels & predictions).sum())
     return (tp / predictions.sum() if predictions.sum() else 0.0), (tp / labels.sum() if labels.sum() else 0.0)
+
+
+# ---- the same values from integer counts (csrc/savad_eval_device.h: the device path of evaluate) --------------------------------
+# slots of the counter block (include/savad.h: SAVAD_EVAL_*)
+EVAL_COUNTERS = 16
+EVAL_N, EVAL_POS, EVAL_TRUE, EVAL_NAN, EVAL_BAD_LABEL, EVAL_U2, EVAL_PRED, EVAL_PRED_STRIDE = 0, 1, 2, 3, 4, 5, 6, 5
+
+
+def _eer_from_counts(tp: int, fp: int, n_pos: int, n_neg: int) -> float:
+    """equal_error_rate(labels, prediction) for a 0/1 prediction: its ROC has the point after the 1s (when there are 1s and 0s) and
+    the end point, by the expressions of roc_curve_points"""
+    ones = tp + fp
+    if 0 < ones < n_pos + n_neg:
+        tps, fps = np.array([tp, n_pos], dtype=np.int64), np.array([fp, n_neg], dtype=np.int64)
+    else:
+        tps, fps = np.array([n_pos], dtype=np.int64), np.array([n_neg], dtype=np.int64)
+    tpr = np.r_[0.0, tps / max(tps[-1], 1)]
+    fpr = np.r_[0.0, fps / max(fps[-1], 1)]
+    return _eer_of_curve(fpr, tpr)
+
+
+def _boundary_mean(num, den, n_true: int):
+    total = 0.0
+    for a, b in zip(num.tolist(), den.tolist()):   # in boundary order, one addition at a time: _boundary_accuracy's sum
+        total += a / b
+    return total / n_true if n_true > 0 else 0
+
+
+def metrics_from_counts(counters, seg, n=None):
+    """The 18 values of evaluate.file_metrics from the integers of savad_eval_counts / savad_eval_counts_host: `counters`
+    [EVAL_COUNTERS] int64 and `seg` [n_true, 8] uint8 -- (num, den) of the start and of the end boundary for the single prediction,
+    then for the boosted one.  Every value is the host path's float64 expression of the same integers, so it has its bits.
+    `n`: the frame count, checked against the counters when given."""
+    from collections import OrderedDict
+    from statistics import harmonic_mean
+
+    c = [int(v) for v in np.asarray(counters).ravel()]
+    if len(c) != EVAL_COUNTERS:
+        raise ValueError(f"{len(c)} counters, {EVAL_COUNTERS} expected")
+    if n is None:
+        n = c[EVAL_N]
+    if int(n) != c[EVAL_N]:
+        raise ValueError(f"the counters are of {c[EVAL_N]} frames, not of {n}")
+    if c[EVAL_NAN] or c[EVAL_BAD_LABEL]:
+        raise ValueError("NaN scores or labels outside 0/1: these counters do not determine the metrics")
+    n, n_pos, n_true = int(n), c[EVAL_POS], c[EVAL_TRUE]
+    n_neg = n - n_pos
+    seg = np.asarray(seg, dtype=np.uint8).reshape(-1, 8)
+    if len(seg) != n_true:
+        raise ValueError(f"{len(seg)} boundary records for {n_true} true segments")
+    if n_pos == 0 or n_neg == 0:
+        raise ValueError("AUC needs both classes")
+    auc = float((c[EVAL_U2] / 2.0) / (n_pos * n_neg))
+
+    def of_prediction(p):
+        tp, fp, fn, tn, n_pred = c[EVAL_PRED + p * EVAL_PRED_STRIDE:EVAL_PRED + (p + 1) * EVAL_PRED_STRIDE]
+        acc = float((tp + tn) / n)
+        sba = _boundary_mean(seg[:, 4 * p + 0], seg[:, 4 * p + 1], n_true)
+        eba = _boundary_mean(seg[:, 4 * p + 2], seg[:, 4 * p + 3], n_true)
+        bp = n_true / (2 * n_pred) * (sba + eba) if n_pred > 0 else 0
+        precision = float(tp) / (tp + fp) if tp + fp else 0.0
+        recall = float(tp) / n_pos if n_pos else 0.0
+        return dict(acc=acc, precision=precision, recall=recall, vacc=harmonic_mean([acc, sba, eba, bp]), sba=sba, eba=eba, bp=bp,
+                    eer=_eer_from_counts(tp, fp, n_pos, n_neg))
+
+    single, boosted = of_prediction(0), of_prediction(1)
+    out = OrderedDict(auc=auc, accuracy=boosted["acc"], precision=boosted["precision"], recall=boosted["recall"], vacc=single["vacc"],
+                      sba=single["sba"], eba=single["eba"], bp=single["bp"], eer=single["eer"])
+    out.update(boosted_auc=auc, boosted_accuracy=boosted["acc"], boosted_precision=boosted["precision"], boosted_recall=boosted["recall"],
+               boosted_vacc=boosted["vacc"], boosted_sba=boosted["sba"], boosted_eba=boosted["eba"], boosted_bp=boosted["bp"],
+               boosted_eer=boosted["eer"])
+    return out
