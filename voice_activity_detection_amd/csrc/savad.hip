@@ -17,6 +17,7 @@
 #include "savad_post_device.h"
 #include "savad_eval_device.h"
 #include "savad_schedule.h"
+#include "savad_weights.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -52,25 +53,27 @@ int fail(int code, const char* fmt, ...) {
                                           __FILE__, __LINE__);                                        \
     } while (0)
 
-struct Param {
-    std::string key;
-    size_t numel;
-    size_t off;  // float offset into d_raw
-    bool set;
-};
-
 constexpr int MAX_EVENTS = 64;
 
 }  // namespace
 
+// a fragment image: the weights in the operand order of one kernel family's MFMAs (bf16, or the three bf16 pieces of fp32s)
+struct FragImage {
+    const savad::weights::FragLayout* at = nullptr;  // byte offsets into d (the handle's w.bf16 / w.f32s)
+    char* d = nullptr;
+    bool dirty = true;           // the raw parameters changed since it was packed
+    bool lds_attrs_set = false;  // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done for the family's kernels
+};
+
 struct savad_model {
     savad_config cfg;
-    bool generic = false;  // d_model != 128: the plain fp32 kernels of savad_generic.h on the raw parameters
-    std::vector<Param> params;
-    float* d_raw = nullptr;     // parameters exactly as handed over (state_dict layout)
-    float* d_packed = nullptr;  // LayerNorm-folded weights
-    size_t raw_floats = 0, packed_floats = 0;
+    savad::weights::Layout w;    // where every weight lies (savad_weights.h); w.generic: d_model != 128, the plain fp32 kernels of savad_generic.h
+    std::vector<char> param_set;  // per w.params entry
+    float* d_raw = nullptr;      // parameters exactly as handed over (state_dict layout)
+    float* d_packed = nullptr;   // LayerNorm-folded weights
     bool dirty = true;
+    FragImage bf16;  // savad_kernels_bf16.h, filled when precision == 1
+    FragImage f32s;  // savad_kernels_f32s.h, filled when precision == 2
     // positional-encoding cache (mirrors SinusoidalPositionalEncoding: rebuilt when T grows,
     // vad/modeling/transformer.py:392-397; initial length 10: vad/models/self_attention.py:14)
     float* d_pe = nullptr;
@@ -81,66 +84,41 @@ struct savad_model {
     bool batch_invariant = false;   // bf16: the persistent attention kernel without key-split tail items (savad_set_batch_invariant)
     int precision = 0;  // 0 = fp32 MFMA, 1 = bf16 MFMA operands (fp32 accumulate / statistics / residual stream),
                         // 2 = "fp32s": fp32 parity on the bf16 pipe, every operand as three bf16 pieces (savad_kernels_f32s.h)
-    char* d_frag3 = nullptr;  // fp32s weight triples (savad_kernels_f32s.h), filled when precision == 2
-    size_t frag3_bytes = 0;
-    bool frag3_dirty = true;
-    bool lds_attrs3_set = false;
-    size_t f3_win = 0;
     unsigned* d_sat = nullptr;  // bf16 path: elements of the fp16-stored residual stream that saturated since the last query
-    char* d_frag = nullptr;  // bf16 weight fragments (savad_kernels_bf16.h), filled when precision == 1
-    size_t frag_bytes = 0;
-    bool frag_dirty = true;
-    bool lds_attrs_set = false;  // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done for the bf16 kernels
-    int n_cu = 256;              // compute units of the handle's device (launch-shape decisions)
-    size_t f_win = 0;
-    struct LayerFrag {
-        size_t wqkv, wo, w1, w2;
-        size_t wq_vo = 0;  // lf3 only: Wq~ | Wo Wv' (prepare_frags3: the key projection folded into Q, the out-projection into V)
-    };
-    std::vector<LayerFrag> lf;
-    std::vector<LayerFrag> lf3;  // byte offsets into d_frag3
+    int n_cu = 256;             // compute units of the handle's device (launch-shape decisions)
     // profiling
     int prof_capacity = 0, prof_used = 0, prof_nk = 0, prof_skip = 0;
     std::vector<hipEvent_t> events;  // prof_capacity * MAX_EVENTS
     std::vector<const char*> knames;
 
-    // raw offsets
-    size_t r_win, r_bin, r_lnf_w, r_lnf_b, r_wc, r_bc;
-    struct LayerRaw {
-        size_t wq, bq, wk, bk, wv, bv, wo, bo, ln1w, ln1b, w1, b1, w2, b2, ln2w, ln2b;
-    };
-    std::vector<LayerRaw> lr;
-    // packed offsets
-    struct LayerPacked {
-        size_t wqkv, bqkv, w1, b1;
-        size_t wq_vo, bq_vo;  // fp32s, T > 32: Wq~ | Wo Wv' [2 D][D] and bq~ | Wo bv' (fold_qk_kernel, fold_vo_kernel)
-        size_t frag;  // the layer's matrices in fragment order (packed_forward_kernel)
-    };
-    std::vector<LayerPacked> lp;
-    size_t p_wc, p_bc;
-    size_t p_bias = 0;  // [L][LBIAS] b1' | b2 | bqkv' | bo (packed_forward_kernel stages them in one sweep)
-    int FP = 0;           // feature size rounded up to a multiple of 16 (kernels' K granularity)
-    size_t p_win_pad = 0;  // [D][FP] zero-padded copy of input_layer.0.weight (only when FP != feature_size)
+    void weights_changed() { dirty = bf16.dirty = f32s.dirty = true; }
 };
 
 namespace {
 
 using namespace savad;
 
-size_t add_param(savad_model* m, const std::string& key, size_t numel) {
-    const size_t off = m->raw_floats;
-    m->params.push_back(Param{key, numel, off, false});
-    m->raw_floats += (numel + 3) & ~size_t(3);  // keep every tensor 16-byte aligned
-    return off;
-}
-
-// the kernel headers' sizes as savad_schedule.h restates them
+// the kernel headers' sizes as savad_schedule.h and savad_weights.h restate them
 static_assert(sched::D == D && sched::TILE == TILE && sched::F32_MAX_LAYERS == PACKED_MAX_LAYERS, "savad_schedule.h: savad_kernels.h sizes");
 static_assert(sched::BF_BLK_BYTES == bf::BLK_BYTES && sched::BF_HBLK_FLOATS == bf::HBLK_FLOATS && sched::BF_HRES_BYTES == sizeof(bf::hres_t) &&
                   sched::BF16_MAX_LAYERS == bf::PACKED_BF16_MAX_LAYERS && sched::PW_GRID == bf::PW_GRID, "savad_schedule.h: bf16 sizes");
-static_assert(sched::FS_BLK3_BYTES == fs::BLK3_BYTES && sched::FS_HBLK_BYTES == fs::HBLK_BYTES && sched::F32S_MAX_LAYERS == fs::PACKED_F32S_MAX_LAYERS,
+static_assert(sched::FS_BLK3_BYTES == fs::BLK3_BYTES && sched::F32S_MAX_LAYERS == fs::PACKED_F32S_MAX_LAYERS && sched::FS_HBLK_BYTES == fs::HBLK_BYTES,
               "savad_schedule.h: fp32s sizes");
 static_assert(sched::GEN_SCORE_CAP == gen::SCORE_CAP, "savad_schedule.h: savad_generic.h sizes");
+static_assert(weights::D == D && weights::DFF == DFF && weights::LBIAS == LBIAS && weights::FRAG_LAYER == FRAG_LAYER, "savad_weights.h: savad_kernels.h sizes");
+
+// blocks of 256 threads for `work` elements, at most `cap` (the kernels stride over the rest)
+int grid_for(long work, int cap = 4096) { return (int)((work + 255) / 256 < cap ? (work + 255) / 256 : cap); }
+
+// consecutive 256-byte-aligned regions of a caller's workspace (post_layout, eval_layout)
+struct Arena {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return at;
+    }
+};
 
 sched::Knobs knobs_of(const savad_model* m) {
     sched::Knobs k;
@@ -151,8 +129,8 @@ sched::Knobs knobs_of(const savad_model* m) {
     k.n_cu = m->n_cu;
     k.num_layers = m->cfg.num_layers;
     k.feature_size = m->cfg.feature_size;
-    k.FP = m->FP;
-    k.generic = m->generic;
+    k.FP = m->w.FP;
+    k.generic = m->w.generic;
     k.d_model = m->cfg.d_model;
     return k;
 }
@@ -187,7 +165,7 @@ int ensure_pe(savad_model* m, int T, hipStream_t st) {
     }
     const size_t Dm = m->cfg.d_model;
     HIP_TRY(hipMalloc(&m->d_pe, sizeof(float) * (size_t)cap * Dm));
-    if (m->generic) {
+    if (m->w.generic) {
         m->h_pe.resize((size_t)cap * Dm);
         gen::build_pe_host(m->h_pe.data(), cap, (int)Dm);
     } else {
@@ -209,12 +187,13 @@ int fold(savad_model* m, hipStream_t st, size_t w, size_t b, size_t g, size_t be
 
 int prepare_weights(savad_model* m, hipStream_t st) {
     if (!m->dirty) return SAVAD_OK;
-    for (const Param& p : m->params)
-        if (!p.set) return fail(SAVAD_E_STATE, "parameter '%s' was never set", p.key.c_str());
+    const weights::Layout& w = m->w;
+    for (size_t i = 0; i < w.params.size(); ++i)
+        if (!m->param_set[i]) return fail(SAVAD_E_STATE, "parameter '%s' was never set", w.params[i].key.c_str());
     const int L = m->cfg.num_layers;
     for (int l = 0; l < L; ++l) {
-        const auto& r = m->lr[l];
-        const auto& p = m->lp[l];
+        const auto& r = w.lr[l];
+        const auto& p = w.lp[l];
         int rc;
         if ((rc = fold(m, st, r.wq, r.bq, r.ln1w, r.ln1b, p.wqkv, p.bqkv, D, D))) return rc;
         if ((rc = fold(m, st, r.wk, r.bk, r.ln1w, r.ln1b, p.wqkv + (size_t)D * D, p.bqkv + D, D, D))) return rc;
@@ -226,18 +205,18 @@ int prepare_weights(savad_model* m, hipStream_t st) {
         hipLaunchKernelGGL(pack_frag32_kernel, dim3(256), dim3(256), 0, st, m->d_packed + p.w1, 0, 16, frag + 16 * FRAG_BLOCK);
         hipLaunchKernelGGL(pack_frag32_kernel, dim3(256), dim3(256), 0, st, m->d_raw + r.w2, 1, 16, frag + 32 * FRAG_BLOCK);
         HIP_TRY(hipGetLastError());
-        float* lb = m->d_packed + m->p_bias + (size_t)l * LBIAS;
+        float* lb = m->d_packed + w.p_bias + (size_t)l * LBIAS;
         const size_t f = sizeof(float);
         HIP_TRY(hipMemcpyAsync(lb, m->d_packed + p.b1, DFF * f, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(lb + DFF, m->d_raw + r.b2, D * f, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(lb + DFF + D, m->d_packed + p.bqkv, 3 * D * f, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(lb + DFF + 4 * D, m->d_raw + r.bo, D * f, hipMemcpyDeviceToDevice, st));
     }
-    int rc = fold(m, st, m->r_wc, m->r_bc, m->r_lnf_w, m->r_lnf_b, m->p_wc, m->p_bc, 2, D);
+    int rc = fold(m, st, w.r_wc, w.r_bc, w.r_lnf_w, w.r_lnf_b, w.p_wc, w.p_bc, 2, D);
     if (rc) return rc;
-    if (m->FP != m->cfg.feature_size) {
-        hipLaunchKernelGGL(pad_rows_kernel<float>, dim3(64), dim3(256), 0, st, m->d_raw + m->r_win, (size_t)D,
-                           m->cfg.feature_size, m->FP, m->d_packed + m->p_win_pad);
+    if (w.FP != m->cfg.feature_size) {
+        hipLaunchKernelGGL(pad_rows_kernel<float>, dim3(64), dim3(256), 0, st, m->d_raw + w.r_win, (size_t)D,
+                           m->cfg.feature_size, w.FP, m->d_packed + w.p_win_pad);
         HIP_TRY(hipGetLastError());
     }
     m->dirty = false;
@@ -246,67 +225,48 @@ int prepare_weights(savad_model* m, hipStream_t st) {
 
 // input weight as the kernels read it: [D][FP], the raw tensor itself when no padding is needed
 const float* win_fp32(const savad_model* m) {
-    return m->FP == m->cfg.feature_size ? m->d_raw + m->r_win : m->d_packed + m->p_win_pad;
+    return m->w.FP == m->cfg.feature_size ? m->d_raw + m->w.r_win : m->d_packed + m->w.p_win_pad;
 }
 
-int pack_frags(savad_model* m, hipStream_t st, const float* W, int N, int K, size_t off) {
-    const size_t total = (size_t)N * K;
-    const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-    hipLaunchKernelGGL(bf::pack_weight_frags_kernel, dim3(grid), dim3(256), 0, st, W, N, K,
-                       reinterpret_cast<__bf16*>(m->d_frag + off));
+using PackKernel = void (*)(const float*, int, int, __bf16*);  // bf::pack_weight_frags_kernel, fs::pack_weight_frags3_kernel
+
+int pack_frags(FragImage& im, PackKernel pack, hipStream_t st, const float* W, int N, int K, size_t off) {
+    hipLaunchKernelGGL(pack, dim3(grid_for((long)N * K, 1024)), dim3(256), 0, st, W, N, K, reinterpret_cast<__bf16*>(im.d + off));
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }
 
-int prepare_frags(savad_model* m, hipStream_t st) {
-    if (!m->frag_dirty) return SAVAD_OK;
+// the folded fp32 weights (prepare_weights) into the image `im`, in the operand format `pack` writes
+int prepare_frags(savad_model* m, FragImage& im, PackKernel pack, hipStream_t st) {
+    if (!im.dirty) return SAVAD_OK;
     const int L = m->cfg.num_layers;
+    const float *R = m->d_raw, *P = m->d_packed;
     int rc;
-    if ((rc = pack_frags(m, st, win_fp32(m), D, m->FP, m->f_win))) return rc;
+    if ((rc = pack_frags(im, pack, st, win_fp32(m), D, m->w.FP, im.at->win))) return rc;
     for (int l = 0; l < L; ++l) {
-        if ((rc = pack_frags(m, st, m->d_packed + m->lp[l].wqkv, 3 * D, D, m->lf[l].wqkv))) return rc;
-        if ((rc = pack_frags(m, st, m->d_raw + m->lr[l].wo, D, D, m->lf[l].wo))) return rc;
-        if ((rc = pack_frags(m, st, m->d_packed + m->lp[l].w1, DFF, D, m->lf[l].w1))) return rc;
-        if ((rc = pack_frags(m, st, m->d_raw + m->lr[l].w2, D, DFF, m->lf[l].w2))) return rc;
-    }
-    m->frag_dirty = false;
-    return SAVAD_OK;
-}
-
-int pack_frags3(savad_model* m, hipStream_t st, const float* W, int N, int K, size_t off) {
-    const size_t total = (size_t)N * K;
-    const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-    hipLaunchKernelGGL(fs::pack_weight_frags3_kernel, dim3(grid), dim3(256), 0, st, W, N, K, reinterpret_cast<__bf16*>(m->d_frag3 + off));
-    HIP_TRY(hipGetLastError());
-    return SAVAD_OK;
-}
-
-int prepare_frags3(savad_model* m, hipStream_t st) {
-    if (!m->frag3_dirty) return SAVAD_OK;
-    const int L = m->cfg.num_layers;
-    int rc;
-    if ((rc = pack_frags3(m, st, win_fp32(m), D, m->FP, m->f3_win))) return rc;
-    for (int l = 0; l < L; ++l) {
-        if ((rc = pack_frags3(m, st, m->d_packed + m->lp[l].wqkv, 3 * D, D, m->lf3[l].wqkv))) return rc;
-        if ((rc = pack_frags3(m, st, m->d_raw + m->lr[l].wo, D, D, m->lf3[l].wo))) return rc;
-        if ((rc = pack_frags3(m, st, m->d_packed + m->lp[l].w1, DFF, D, m->lf3[l].w1))) return rc;
-        if ((rc = pack_frags3(m, st, m->d_raw + m->lr[l].w2, D, DFF, m->lf3[l].w2))) return rc;
-        // the fused launches of T > 32 never issue the out-projection: one head, softmax rows sum to 1, so
+        const auto& r = m->w.lr[l];
+        const auto& p = m->w.lp[l];
+        const auto& f = im.at->layer[l];
+        if ((rc = pack_frags(im, pack, st, P + p.wqkv, 3 * D, D, f.wqkv))) return rc;
+        if ((rc = pack_frags(im, pack, st, R + r.wo, D, D, f.wo))) return rc;
+        if ((rc = pack_frags(im, pack, st, P + p.w1, DFF, D, f.w1))) return rc;
+        if ((rc = pack_frags(im, pack, st, R + r.w2, D, DFF, f.w2))) return rc;
+        if (!im.at->folded) continue;
+        // the fused fp32s launches of T > 32 never issue the out-projection: one head, softmax rows sum to 1, so
         //   Wo (P (x Wv'^T + bv')) + bo = P (x (Wo Wv')^T + Wo bv') + bo
         // nor the key projection: the part of a score that depends on the key is [c Wk'^T (Wq' x_i + bq')] . x_j, so the query is
         // projected with Wq~ = c Wk'^T Wq' (bias c Wk'^T bq') and the key is the normalised row itself.  A SECOND image per layer holds
         // Wq~ | Wvo (bias image: bq~ | Wo bv'); products in fp64, rounded once.  The plain images stay: the T <= 32 kernels read them.
-        const auto& p = m->lp[l];
-        const float* wqkv = m->d_packed + p.wqkv;
-        hipLaunchKernelGGL(fs::fold_qk_kernel, dim3(D), dim3(D), 0, st, wqkv, wqkv + (size_t)D * D, m->d_packed + p.bqkv,
+        const float* wqkv = P + p.wqkv;
+        hipLaunchKernelGGL(fs::fold_qk_kernel, dim3(D), dim3(D), 0, st, wqkv, wqkv + (size_t)D * D, P + p.bqkv,
                            1.4426950408889634 / sqrt((double)D), m->d_packed + p.wq_vo, m->d_packed + p.bq_vo);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(fs::fold_vo_kernel, dim3(D), dim3(D), 0, st, m->d_raw + m->lr[l].wo, wqkv + (size_t)2 * D * D, m->d_packed + p.bqkv,
+        hipLaunchKernelGGL(fs::fold_vo_kernel, dim3(D), dim3(D), 0, st, R + r.wo, wqkv + (size_t)2 * D * D, P + p.bqkv,
                            m->d_packed + p.wq_vo + (size_t)D * D, m->d_packed + p.bq_vo + D);
         HIP_TRY(hipGetLastError());
-        if ((rc = pack_frags3(m, st, m->d_packed + p.wq_vo, 2 * D, D, m->lf3[l].wq_vo))) return rc;
+        if ((rc = pack_frags(im, pack, st, P + p.wq_vo, 2 * D, D, f.wq_vo))) return rc;
     }
-    m->frag3_dirty = false;
+    im.dirty = false;
     return SAVAD_OK;
 }
 
@@ -344,52 +304,6 @@ struct Prof {
 };
 
 
-// ---- d_model != 128: same parameter inventory with the runtime width, no folded / fragment copies
-int create_generic(const savad_config* cfg, savad_handle* out) {
-    if (cfg->feature_size <= 0 || cfg->feature_size > 4096) return fail(SAVAD_E_INVALID, "feature_size=%d", cfg->feature_size);
-    if (cfg->num_layers < 1 || cfg->num_layers > 64) return fail(SAVAD_E_INVALID, "num_layers=%d", cfg->num_layers);
-    savad_model* m = new savad_model();
-    m->cfg = *cfg;
-    m->generic = true;
-    const size_t Dm = cfg->d_model, Fm = cfg->feature_size, Hm = 4 * Dm;  // d_ff = 4 d_model: vad/models/self_attention.py:10
-    const int L = cfg->num_layers;
-    m->r_win = add_param(m, "input_layer.0.weight", Dm * Fm);
-    m->r_bin = add_param(m, "input_layer.0.bias", Dm);
-    m->lr.resize(L);
-    for (int l = 0; l < L; ++l) {
-        const std::string p = "encoder.layers." + std::to_string(l) + ".";
-        auto& r = m->lr[l];
-        r.wq = add_param(m, p + "self_attention.query_projection.weight", Dm * Dm);
-        r.bq = add_param(m, p + "self_attention.query_projection.bias", Dm);
-        r.wk = add_param(m, p + "self_attention.key_projection.weight", Dm * Dm);
-        r.bk = add_param(m, p + "self_attention.key_projection.bias", Dm);
-        r.wv = add_param(m, p + "self_attention.value_projection.weight", Dm * Dm);
-        r.bv = add_param(m, p + "self_attention.value_projection.bias", Dm);
-        r.wo = add_param(m, p + "self_attention.final_projection.weight", Dm * Dm);
-        r.bo = add_param(m, p + "self_attention.final_projection.bias", Dm);
-        r.ln1w = add_param(m, p + "self_attention_sublayer.layer_norm.weight", Dm);
-        r.ln1b = add_param(m, p + "self_attention_sublayer.layer_norm.bias", Dm);
-        r.w1 = add_param(m, p + "feed_forward.feed_forward.0.weight", Hm * Dm);
-        r.b1 = add_param(m, p + "feed_forward.feed_forward.0.bias", Hm);
-        r.w2 = add_param(m, p + "feed_forward.feed_forward.3.weight", Dm * Hm);
-        r.b2 = add_param(m, p + "feed_forward.feed_forward.3.bias", Dm);
-        r.ln2w = add_param(m, p + "feed_forward_sublayer.layer_norm.weight", Dm);
-        r.ln2b = add_param(m, p + "feed_forward_sublayer.layer_norm.bias", Dm);
-    }
-    m->r_lnf_w = add_param(m, "encoder.layer_norm.weight", Dm);
-    m->r_lnf_b = add_param(m, "encoder.layer_norm.bias", Dm);
-    m->r_wc = add_param(m, "classifier.weight", 2 * Dm);
-    m->r_bc = add_param(m, "classifier.bias", 2);
-    m->FP = cfg->feature_size;
-    hipError_t e = hipMalloc(&m->d_raw, sizeof(float) * m->raw_floats);
-    if (e != hipSuccess) {
-        delete m;
-        return fail(SAVAD_E_HIP, "hipMalloc(weights): %s", hipGetErrorString(e));
-    }
-    *out = m;
-    return SAVAD_OK;
-}
-
 void launch_gemm(hipStream_t st, const gen::GemmArgs& g, int batch) {
     hipLaunchKernelGGL(gen::gemm_kernel, dim3((g.N + gen::GT - 1) / gen::GT, (g.M + gen::GT - 1) / gen::GT, batch), dim3(256), 0, st, g);
 }
@@ -422,21 +336,21 @@ void launch_linear(hipStream_t st, const float* x, long rows, int K, const float
 }
 
 // SelfAttentiveVAD.forward for any d_model, the reference's operation sequence (vad/models/self_attention.py:23-28) kernel by kernel
-int forward_generic(savad_model* m, const sched::ForwardPlan& p, const float* x, int B, int T, float* out, void* workspace, hipStream_t st) {
+void forward_generic(savad_model* m, const sched::ForwardPlan& p, const float* x, int B, int T, float* out, void* workspace, hipStream_t st, Prof& prof) {
     const int Dm = m->cfg.d_model, F = m->cfg.feature_size, L = m->cfg.num_layers;
     char* W = (char*)workspace;
     auto at = [W](size_t off) { return (float*)(W + off); };
     float *h = at(p.h), *n = at(p.n), *q = at(p.q), *k = at(p.k), *v = at(p.v), *ctx = at(p.ctx), *ff = at(p.ff), *sc = at(p.scores);
     const float* R = m->d_raw;
+    const weights::Layout& w = m->w;
     const long rows = (long)B * T;
     const int ln_grid = (int)((rows + 3) / 4);
-    Prof prof(m, st);
     // input Linear + positional encoding / sqrt(d_model) (self_attention.py:13-15, transformer.py:401); dropout = identity
-    launch_linear(st, x, rows, F, R + m->r_win, R + m->r_bin, Dm, h, nullptr, false, m->d_pe, T);
+    launch_linear(st, x, rows, F, R + w.r_win, R + w.r_bin, Dm, h, nullptr, false, m->d_pe, T);
     prof.mark("input_generic");
     const float alpha = (float)(1.0 / sqrt((double)Dm));  // / sqrt(d_head), one head (transformer.py:362)
     for (int l = 0; l < L; ++l) {
-        const auto& r = m->lr[l];
+        const auto& r = w.lr[l];
         hipLaunchKernelGGL(gen::layernorm_kernel, dim3(ln_grid), dim3(256), 0, st, h, R + r.ln1w, R + r.ln1b, n, rows, Dm);
         launch_linear(st, n, rows, Dm, R + r.wq, R + r.bq, Dm, q, nullptr, false, nullptr, T);
         launch_linear(st, n, rows, Dm, R + r.wk, R + r.bk, Dm, k, nullptr, false, nullptr, T);
@@ -492,12 +406,9 @@ int forward_generic(savad_model* m, const sched::ForwardPlan& p, const float* x,
         launch_linear(st, ff, rows, 4 * Dm, R + r.w2, R + r.b2, Dm, h, h, false, nullptr, T);
         prof.mark("row_generic");
     }
-    hipLaunchKernelGGL(gen::layernorm_kernel, dim3(ln_grid), dim3(256), 0, st, h, R + m->r_lnf_w, R + m->r_lnf_b, n, rows, Dm);
-    hipLaunchKernelGGL(gen::classifier_kernel, dim3(ln_grid), dim3(256), 0, st, n, R + m->r_wc, R + m->r_bc, out, rows, Dm);
+    hipLaunchKernelGGL(gen::layernorm_kernel, dim3(ln_grid), dim3(256), 0, st, h, R + w.r_lnf_w, R + w.r_lnf_b, n, rows, Dm);
+    hipLaunchKernelGGL(gen::classifier_kernel, dim3(ln_grid), dim3(256), 0, st, n, R + w.r_wc, R + w.r_bc, out, rows, Dm);
     prof.mark("classifier_generic");
-    prof.done();
-    HIP_TRY(hipGetLastError());
-    return SAVAD_OK;
 }
 
 }  // namespace
@@ -505,11 +416,18 @@ int forward_generic(savad_model* m, const sched::ForwardPlan& p, const float* x,
 SAVAD_EXPORT const char* savad_last_error(void) { return g_err; }
 SAVAD_EXPORT const char* savad_version(void) { return "savad 0.1 (gfx950, fp32 MFMA)"; }
 
+SAVAD_EXPORT void savad_destroy(savad_handle m) {
+    if (!m) return;
+    for (hipEvent_t e : m->events) hipEventDestroy(e);
+    for (void* d : {(void*)m->d_raw, (void*)m->d_packed, (void*)m->bf16.d, (void*)m->f32s.d, (void*)m->d_sat, (void*)m->d_pe})
+        if (d) hipFree(d);
+    delete m;
+}
+
 SAVAD_EXPORT int savad_create(const savad_config* cfg, savad_handle* out) {
     if (!cfg || !out) return fail(SAVAD_E_INVALID, "null argument");
     if (cfg->d_model < 2 || cfg->d_model > 4096 || cfg->d_model % 2)  // the reference's positional encoding pairs sin / cos columns
         return fail(SAVAD_E_INVALID, "d_model=%d (an even value in [2, 4096])", cfg->d_model);
-    if (cfg->d_model != D) return create_generic(cfg, out);
     if (cfg->feature_size <= 0 || cfg->feature_size > 4096)
         return fail(SAVAD_E_INVALID, "feature_size=%d", cfg->feature_size);
     if (cfg->num_layers < 1 || cfg->num_layers > 64) return fail(SAVAD_E_INVALID, "num_layers=%d", cfg->num_layers);
@@ -519,136 +437,46 @@ SAVAD_EXPORT int savad_create(const savad_config* cfg, savad_handle* out) {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) m->n_cu = n;
     }
-    const int F = cfg->feature_size, L = cfg->num_layers;
-    // state_dict inventory: SURVEY.md section 8a / vad/models/self_attention.py:7-21
-    m->r_win = add_param(m, "input_layer.0.weight", (size_t)D * F);
-    m->r_bin = add_param(m, "input_layer.0.bias", D);
-    m->lr.resize(L);
-    m->lp.resize(L);
-    for (int l = 0; l < L; ++l) {
-        const std::string p = "encoder.layers." + std::to_string(l) + ".";
-        auto& r = m->lr[l];
-        r.wq = add_param(m, p + "self_attention.query_projection.weight", (size_t)D * D);
-        r.bq = add_param(m, p + "self_attention.query_projection.bias", D);
-        r.wk = add_param(m, p + "self_attention.key_projection.weight", (size_t)D * D);
-        r.bk = add_param(m, p + "self_attention.key_projection.bias", D);
-        r.wv = add_param(m, p + "self_attention.value_projection.weight", (size_t)D * D);
-        r.bv = add_param(m, p + "self_attention.value_projection.bias", D);
-        r.wo = add_param(m, p + "self_attention.final_projection.weight", (size_t)D * D);
-        r.bo = add_param(m, p + "self_attention.final_projection.bias", D);
-        r.ln1w = add_param(m, p + "self_attention_sublayer.layer_norm.weight", D);
-        r.ln1b = add_param(m, p + "self_attention_sublayer.layer_norm.bias", D);
-        r.w1 = add_param(m, p + "feed_forward.feed_forward.0.weight", (size_t)DFF * D);
-        r.b1 = add_param(m, p + "feed_forward.feed_forward.0.bias", DFF);
-        r.w2 = add_param(m, p + "feed_forward.feed_forward.3.weight", (size_t)D * DFF);
-        r.b2 = add_param(m, p + "feed_forward.feed_forward.3.bias", D);
-        r.ln2w = add_param(m, p + "feed_forward_sublayer.layer_norm.weight", D);
-        r.ln2b = add_param(m, p + "feed_forward_sublayer.layer_norm.bias", D);
-        auto& q = m->lp[l];
-        q.wqkv = m->packed_floats;
-        m->packed_floats += (size_t)3 * D * D;
-        q.bqkv = m->packed_floats;
-        m->packed_floats += 3 * D;
-        q.w1 = m->packed_floats;
-        m->packed_floats += (size_t)DFF * D;
-        q.b1 = m->packed_floats;
-        m->packed_floats += DFF;
-        q.wq_vo = m->packed_floats;
-        m->packed_floats += (size_t)2 * D * D;
-        q.bq_vo = m->packed_floats;
-        m->packed_floats += 2 * D;
-        q.frag = m->packed_floats;
-        m->packed_floats += FRAG_LAYER;
+    m->w = weights::make_layout(cfg->feature_size, cfg->num_layers, cfg->d_model);
+    const weights::Layout& w = m->w;
+    m->param_set.assign(w.params.size(), 0);
+    m->bf16.at = &w.bf16;
+    m->f32s.at = &w.f32s;
+    // every buffer of the handle now: a forward allocates nothing (d_model != 128: the raw parameters are all there is)
+    hipError_t e = hipMalloc(&m->d_raw, sizeof(float) * w.raw_floats);
+    if (!w.generic) {
+        if (e == hipSuccess) e = hipMalloc(&m->bf16.d, w.bf16.bytes);
+        if (e == hipSuccess) e = hipMalloc(&m->f32s.d, w.f32s.bytes);
+        if (e == hipSuccess) e = hipMalloc(&m->d_sat, sizeof(unsigned));
+        if (e == hipSuccess) e = hipMemset(m->d_sat, 0, sizeof(unsigned));
+        if (e == hipSuccess) e = hipMalloc(&m->d_packed, sizeof(float) * w.packed_floats);
     }
-    m->r_lnf_w = add_param(m, "encoder.layer_norm.weight", D);
-    m->r_lnf_b = add_param(m, "encoder.layer_norm.bias", D);
-    m->r_wc = add_param(m, "classifier.weight", 2 * D);
-    m->r_bc = add_param(m, "classifier.bias", 2);
-    m->p_bias = m->packed_floats;
-    m->packed_floats += (size_t)L * LBIAS;
-    m->p_wc = m->packed_floats;
-    m->packed_floats += 2 * D;
-    m->p_bc = m->packed_floats;
-    m->packed_floats += 4;
-    m->FP = (F + 15) / 16 * 16;
-    m->p_win_pad = m->packed_floats;
-    m->packed_floats += (size_t)D * m->FP;
-    m->lf.resize(L);
-    m->f_win = 0;
-    m->frag_bytes = (size_t)D * ((F + 15) / 16 * 16) * 2;
-    for (int l = 0; l < L; ++l) {
-        auto& fl = m->lf[l];
-        fl.wqkv = m->frag_bytes;
-        m->frag_bytes += (size_t)3 * D * D * 2;
-        fl.wo = m->frag_bytes;
-        m->frag_bytes += (size_t)D * D * 2;
-        fl.w1 = m->frag_bytes;
-        m->frag_bytes += (size_t)DFF * D * 2;
-        fl.w2 = m->frag_bytes;
-        m->frag_bytes += (size_t)D * DFF * 2;
-    }
-    m->lf3.resize(L);
-    m->f3_win = 0;
-    m->frag3_bytes = (size_t)D * ((F + 15) / 16 * 16) * 6;
-    for (int l = 0; l < L; ++l) {
-        auto& fl = m->lf3[l];
-        fl.wqkv = m->frag3_bytes;
-        m->frag3_bytes += (size_t)3 * D * D * 6;
-        fl.wo = m->frag3_bytes;
-        m->frag3_bytes += (size_t)D * D * 6;
-        fl.w1 = m->frag3_bytes;
-        m->frag3_bytes += (size_t)DFF * D * 6;
-        fl.w2 = m->frag3_bytes;
-        m->frag3_bytes += (size_t)D * DFF * 6;
-        fl.wq_vo = m->frag3_bytes;
-        m->frag3_bytes += (size_t)2 * D * D * 6;
-    }
-    hipError_t e = hipMalloc(&m->d_raw, sizeof(float) * m->raw_floats);
-    if (e == hipSuccess) e = hipMalloc(&m->d_frag, m->frag_bytes);
-    if (e == hipSuccess) e = hipMalloc(&m->d_frag3, m->frag3_bytes);
-    if (e == hipSuccess) e = hipMalloc(&m->d_sat, sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemset(m->d_sat, 0, sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc(&m->d_packed, sizeof(float) * m->packed_floats);
     if (e != hipSuccess) {
-        if (m->d_raw) hipFree(m->d_raw);
-        delete m;
+        savad_destroy(m);
         return fail(SAVAD_E_HIP, "hipMalloc(weights): %s", hipGetErrorString(e));
     }
     *out = m;
     return SAVAD_OK;
 }
 
-SAVAD_EXPORT void savad_destroy(savad_handle m) {
-    if (!m) return;
-    for (hipEvent_t e : m->events) hipEventDestroy(e);
-    if (m->d_raw) hipFree(m->d_raw);
-    if (m->d_packed) hipFree(m->d_packed);
-    if (m->d_frag) hipFree(m->d_frag);
-    if (m->d_frag3) hipFree(m->d_frag3);
-    if (m->d_sat) hipFree(m->d_sat);
-    if (m->d_pe) hipFree(m->d_pe);
-    delete m;
-}
-
-SAVAD_EXPORT int savad_num_params(savad_handle m) { return m ? (int)m->params.size() : 0; }
+SAVAD_EXPORT int savad_num_params(savad_handle m) { return m ? (int)m->w.params.size() : 0; }
 SAVAD_EXPORT const char* savad_param_key(savad_handle m, int i) {
-    return (m && i >= 0 && i < (int)m->params.size()) ? m->params[i].key.c_str() : nullptr;
+    return (m && i >= 0 && i < (int)m->w.params.size()) ? m->w.params[i].key.c_str() : nullptr;
 }
 SAVAD_EXPORT size_t savad_param_numel(savad_handle m, int i) {
-    return (m && i >= 0 && i < (int)m->params.size()) ? m->params[i].numel : 0;
+    return (m && i >= 0 && i < (int)m->w.params.size()) ? m->w.params[i].numel : 0;
 }
 
 SAVAD_EXPORT int savad_set_param(savad_handle m, const char* key, const float* data, size_t numel, void* stream) {
     if (!m || !key || !data) return fail(SAVAD_E_INVALID, "null argument");
-    for (Param& p : m->params) {
+    for (size_t i = 0; i < m->w.params.size(); ++i) {
+        const weights::Param& p = m->w.params[i];
         if (p.key != key) continue;
         if (p.numel != numel)
             return fail(SAVAD_E_INVALID, "size mismatch for '%s': got %zu elements, expected %zu", key, numel, p.numel);
         HIP_TRY(hipMemcpyAsync(m->d_raw + p.off, data, sizeof(float) * numel, hipMemcpyDefault, (hipStream_t)stream));
-        p.set = true;
-        m->dirty = true;
-        m->frag_dirty = true;
-        m->frag3_dirty = true;
+        m->param_set[i] = 1;
+        m->weights_changed();
         return SAVAD_OK;
     }
     return fail(SAVAD_E_NOKEY, "unexpected key '%s' in state_dict", key);
@@ -693,10 +521,9 @@ SAVAD_EXPORT int savad_reserve(savad_handle m, int T_max, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     int rc;
     if ((rc = ensure_pe(m, T_max, st))) return rc;
-    if (m->generic) return SAVAD_OK;  // nothing to fold or pack: the generic kernels read the raw parameters
-    bool all_set = true;
-    for (const Param& p : m->params) all_set = all_set && p.set;
-    if (!all_set) return SAVAD_OK;
+    if (m->w.generic) return SAVAD_OK;  // nothing to fold or pack: the generic kernels read the raw parameters
+    for (char set : m->param_set)
+        if (!set) return SAVAD_OK;
     return ensure_ready(m, m->precision == 1 ? sched::BF16 : m->precision == 2 ? sched::F32S : sched::F32, T_max, st);
 }
 
@@ -719,7 +546,7 @@ SAVAD_EXPORT int savad_residual_saturations(savad_handle m, unsigned long long* 
 
 SAVAD_EXPORT int savad_set_precision(savad_handle m, int precision) {
     if (!m || precision < 0 || precision > 2) return fail(SAVAD_E_INVALID, "precision %d (0 = fp32, 1 = bf16, 2 = fp32s)", precision);
-    if (m->generic && precision != 0)
+    if (m->w.generic && precision != 0)
         return fail(SAVAD_E_UNSUPPORTED, "bf16 / split-bf16 operands are implemented for d_model=128 only (this handle: d_model=%d, fp32)", m->cfg.d_model);
     m->precision = precision;
     return SAVAD_OK;
@@ -730,7 +557,7 @@ namespace {
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) for every bf16 kernel, once per handle
 int prepare_bf16_launch(savad_model* m) {
     int rc;
-    if (m->lds_attrs_set) return SAVAD_OK;
+    if (m->bf16.lds_attrs_set) return SAVAD_OK;
     constexpr int r4 = bf::Ring<4>::NRING * bf::RING_BYTES, r8 = bf::Ring<8>::NRING * bf::RING_BYTES;
     if ((rc = allow_lds(bf::input_qkv_kernel_bf16<float, 4>, r4 + 3 * D * 4))) return rc;
     if ((rc = allow_lds(bf::input_qkv_kernel_bf16<__bf16, 4>, r4 + 3 * D * 4))) return rc;
@@ -754,24 +581,24 @@ int prepare_bf16_launch(savad_model* m) {
     if ((rc = allow_lds(bf::packed_forward_kernel_bf16<4, 4, 4>, r8 + (bf::PACKED_BF16_MAX_LAYERS * LBIAS + 2 * D + 4) * 4))) return rc;
     if ((rc = allow_lds(bf::packed_forward_kernel_bf16<8, 4, 0>, r8 + (bf::PACKED_BF16_MAX_LAYERS * LBIAS + 2 * D + 4) * 4))) return rc;
     if ((rc = allow_lds(bf::packed_forward_kernel_bf16_ns, bf::ns_lds_bytes(bf::PACKED_BF16_MAX_LAYERS)))) return rc;
-    m->lds_attrs_set = true;
+    m->bf16.lds_attrs_set = true;
     return SAVAD_OK;
 }
 
-int prepare_f32s_launch(savad_model* m);
+int prepare_f32s_launch(savad_model* m);  // (beside forward_f32s)
 
-// Everything a forward of `family` reads besides its input: folded weights, the family's fragment images and LDS limits, and a
+// Everything a forward of `family` reads besides its input: folded weights, the family's fragment image and LDS limits, and a
 // positional-encoding table of at least T rows.  Nothing is launched or allocated once it has run for the handle's current parameters.
 int ensure_ready(savad_model* m, int family, int T, hipStream_t st) {
     int rc;
     if (family == sched::GENERIC) {  // nothing to fold or pack: the generic kernels read the raw parameters
-        for (const Param& q : m->params)
-            if (!q.set) return fail(SAVAD_E_NOKEY, "missing key '%s' in state_dict", q.key.c_str());
+        for (size_t i = 0; i < m->w.params.size(); ++i)
+            if (!m->param_set[i]) return fail(SAVAD_E_NOKEY, "missing key '%s' in state_dict", m->w.params[i].key.c_str());
         return ensure_pe(m, T, st);
     }
     if ((rc = prepare_weights(m, st))) return rc;
-    if (family == sched::BF16 && (rc = prepare_frags(m, st))) return rc;
-    if (family == sched::F32S && (rc = prepare_frags3(m, st))) return rc;
+    if (family == sched::BF16 && (rc = prepare_frags(m, m->bf16, bf::pack_weight_frags_kernel, st))) return rc;
+    if (family == sched::F32S && (rc = prepare_frags(m, m->f32s, fs::pack_weight_frags3_kernel, st))) return rc;
     if ((rc = ensure_pe(m, T, st))) return rc;
     if (family == sched::BF16) return prepare_bf16_launch(m);
     if (family == sched::F32S) return prepare_f32s_launch(m);
@@ -781,79 +608,149 @@ int ensure_ready(savad_model* m, int family, int T, hipStream_t st) {
 // zero-pad the features to the kernels' K granularity (fp32 copy)
 template <typename XT>
 void pad_features(hipStream_t st, const XT* x, size_t rows, int F, int FP, float* xp) {
-    const int grid = (int)((rows * FP + 255) / 256 < 4096 ? (rows * FP + 255) / 256 : 4096);
-    hipLaunchKernelGGL(pad_rows_kernel<XT>, dim3(grid), dim3(256), 0, st, x, rows, F, FP, xp);
+    hipLaunchKernelGGL(pad_rows_kernel<XT>, dim3(grid_for((long)(rows * FP))), dim3(256), 0, st, x, rows, F, FP, xp);
 }
 
-// T <= 32 with bf16 operands: the whole forward in one launch (savad_packed_bf16.h); a wave per packed block, NW blocks per
-// workgroup, in the variant the plan names (sched::single_bf16_variant).  The handle must be ready (ensure_ready).
-void launch_packed_forward_bf16(savad_model* m, int variant, hipStream_t st, const float* x, int B, int T, int F, float* out, const WindowOffsets& wo,
-                                int win_base) {
-    const int L = m->cfg.num_layers;
-    const char* Fr = m->d_frag;
-    const int G = 32 / T, nblk = (B + G - 1) / G;
-    bf::PackedBf16Model pm;
-    for (int l = 0; l < bf::PACKED_BF16_MAX_LAYERS; ++l) {
-        const auto& f = m->lf[l < L ? l : 0];
-        pm.layer[l] = bf::PackedBf16Layer{Fr + f.wqkv, Fr + f.wo, Fr + f.w1, Fr + f.w2};
+// what a forward's kernels read as their input: the caller's features, or their zero-padded fp32 copy in the workspace (plan.pad)
+struct Features {
+    const void* x;
+    int is_bf16;
+    int F;     // columns of x
+    long xbs;  // elements between consecutive sequences
+};
+
+Features forward_input(savad_model* m, const sched::ForwardPlan& p, const void* x, int x_is_bf16, int B, int T, long xbs_in, char* W, hipStream_t st) {
+    Features in{x, x_is_bf16, m->cfg.feature_size, 0};
+    if (p.pad) {
+        float* xp = (float*)(W + p.xpad);
+        if (x_is_bf16)
+            pad_features(st, (const __bf16*)x, (size_t)B * T, in.F, m->w.FP, xp);
+        else
+            pad_features(st, (const float*)x, (size_t)B * T, in.F, m->w.FP, xp);
+        in = Features{xp, 0, m->w.FP, 0};
     }
-    pm.win = Fr + m->f_win;
-    pm.bin = m->d_raw + m->r_bin;
-    pm.pe = m->d_pe;
-    pm.bias = m->d_packed + m->p_bias;
-    pm.wc = m->d_packed + m->p_wc;
-    pm.bc = m->d_packed + m->p_bc;
-    pm.L = L;
-    const float c = qscale();
-    const size_t bias_bytes = ((size_t)L * LBIAS + 2 * D + 4) * 4;   // every layer's biases + the classifier
-    const size_t ring2 = (size_t)2 * bf::RING_BYTES, ring4 = (size_t)4 * bf::RING_BYTES;
-    if (variant == 8)
-        hipLaunchKernelGGL(bf::packed_forward_kernel_bf16_ns, dim3(nblk), dim3(256), bf::ns_lds_bytes(L), st, x, B, T, F, nblk, pm, c, out, wo, win_base,
-                           m->d_sat);
-    else if (variant == 5)
-        hipLaunchKernelGGL((bf::packed_forward_kernel_bf16<8, 4, 0>), dim3((nblk + 7) / 8), dim3(512), ring4 + bias_bytes, st, x, B, T, F, nblk, pm, c, out,
-                           wo, win_base, m->d_sat);
-    else if (variant == 6)
-        hipLaunchKernelGGL((bf::packed_forward_kernel_bf16<4, 4, 4>), dim3((nblk + 3) / 4), dim3(512), ring4 + bias_bytes, st, x, B, T, F, nblk, pm, c, out,
-                           wo, win_base, m->d_sat);
-    else
-        hipLaunchKernelGGL((bf::packed_forward_kernel_bf16<4, 2, 0>), dim3((nblk + 3) / 4), dim3(256), ring2 + bias_bytes, st, x, B, T, F, nblk, pm, c, out,
-                           wo, win_base, m->d_sat);
+    in.xbs = xbs_in > 0 ? xbs_in : (long)T * in.F;
+    return in;
 }
 
-// bf16-operand forward: input_qkv -> [attention -> row] x L on fragment-major buffers
-int forward_bf16(savad_model* m, const sched::ForwardPlan& bp, const void* x, int x_is_bf16, int B, int T, long xbs_in, float* out,
-                 void* workspace, hipStream_t st) {
-    char* W = (char*)workspace;
+// the single-launch kernels' view of the weights: every layer's matrices in the image `im`, biases and classifier in fp32
+// (the slots past L are never read: they repeat layer 0)
+template <typename Model>
+Model packed_model(const savad_model* m, const FragImage& im) {
+    constexpr int MAX_LAYERS = (int)std::extent<decltype(Model::layer)>::value;
+    const weights::Layout& w = m->w;
+    const int L = m->cfg.num_layers;
+    Model pm;
+    for (int l = 0; l < MAX_LAYERS; ++l) {
+        const auto& f = im.at->layer[l < L ? l : 0];
+        pm.layer[l] = {im.d + f.wqkv, im.d + f.wo, im.d + f.w1, im.d + f.w2};
+    }
+    pm.win = im.d + im.at->win;
+    pm.bin = m->d_raw + w.r_bin;
+    pm.pe = m->d_pe;
+    pm.bias = m->d_packed + w.p_bias;
+    pm.wc = m->d_packed + w.p_wc;
+    pm.bc = m->d_packed + w.p_bc;
+    pm.L = L;
+    return pm;
+}
+
+// T <= 32: the whole forward in one launch, a packed block of 32 / T sequences per wave or workgroup, in the variant the plan names
+// (sched::single_bf16_variant, single_f32s_variant; fp32 has one).  wo.w == T: x is the predictor's feature matrix and sequence s its
+// window at win_base + s.  The handle must be ready (ensure_ready).  Returns the launch's name for the profile.
+const char* launch_single(savad_model* m, int family, int variant, hipStream_t st, const float* x, int B, int T, int F, float* out,
+                          const WindowOffsets& wo, int win_base) {
+    const int L = m->cfg.num_layers;
+    const int G = 32 / T, nblk = (B + G - 1) / G;
+    const float c = qscale();
+    if (family == sched::BF16) {  // savad_packed_bf16.h
+        const auto pm = packed_model<bf::PackedBf16Model>(m, m->bf16);
+        const size_t bias_bytes = ((size_t)L * LBIAS + 2 * D + 4) * 4;   // every layer's biases + the classifier
+        const size_t ring2 = (size_t)2 * bf::RING_BYTES, ring4 = (size_t)4 * bf::RING_BYTES;
+        if (variant == 8)
+            hipLaunchKernelGGL(bf::packed_forward_kernel_bf16_ns, dim3(nblk), dim3(256), bf::ns_lds_bytes(L), st, x, B, T, F, nblk, pm, c, out, wo, win_base,
+                               m->d_sat);
+        else if (variant == 5)
+            hipLaunchKernelGGL((bf::packed_forward_kernel_bf16<8, 4, 0>), dim3((nblk + 7) / 8), dim3(512), ring4 + bias_bytes, st, x, B, T, F, nblk, pm, c, out,
+                               wo, win_base, m->d_sat);
+        else if (variant == 6)
+            hipLaunchKernelGGL((bf::packed_forward_kernel_bf16<4, 4, 4>), dim3((nblk + 3) / 4), dim3(512), ring4 + bias_bytes, st, x, B, T, F, nblk, pm, c, out,
+                               wo, win_base, m->d_sat);
+        else
+            hipLaunchKernelGGL((bf::packed_forward_kernel_bf16<4, 2, 0>), dim3((nblk + 3) / 4), dim3(256), ring2 + bias_bytes, st, x, B, T, F, nblk, pm, c, out,
+                               wo, win_base, m->d_sat);
+        return "packed_forward_bf16";
+    }
+    if (family == sched::F32S) {
+        const auto pm = packed_model<fs::PackedF32sModel>(m, m->f32s);
+        if (variant == sched::VARIANT_LATENCY)
+            hipLaunchKernelGGL(fs::packed_forward_kernel_f32s_ns, dim3(nblk), dim3(256), fs::nsf_lds_bytes(L), st, x, B, T, F, nblk, pm, c, out, wo, win_base);
+        else
+            hipLaunchKernelGGL(fs::packed_forward_kernel_f32s, dim3((nblk + 3) / 4), dim3(256), fs::packed_f32s_lds_bytes(L), st, x, B, T, F, nblk, pm, c,
+                               out, wo, win_base);
+        return "packed_forward_f32s";
+    }
+    const weights::Layout& w = m->w;
+    const float *R = m->d_raw, *P = m->d_packed;
+    PackedModel pm;
+    for (int l = 0; l < L; ++l) pm.layer[l] = PackedLayer{P + w.lp[l].frag};
+    for (int l = L; l < PACKED_MAX_LAYERS; ++l) pm.layer[l] = pm.layer[0];
+    pm.bias = P + w.p_bias;
+    pm.win = win_fp32(m);
+    pm.bin = R + w.r_bin;
+    pm.pe = m->d_pe;
+    pm.wc = P + w.p_wc;
+    pm.bc = P + w.p_bc;
+    pm.L = L;
+    hipLaunchKernelGGL(packed_forward_kernel, dim3(nblk), dim3(256), 0, st, x, B * T, T, F, pm, c, out, G * T, wo, win_base);
+    return "packed_forward";
+}
+
+// layer l's Q / K / V projection as a stage reads it from the image and the packed buffer; folded: the image Wq~ | Wo Wv' (four slots,
+// the keys are the normalised rows) and its biases bq~ | Wo bv'
+const char* qkv_frags(const FragImage& im, int l, bool folded) { return im.d + (folded ? im.at->layer[l].wq_vo : im.at->layer[l].wqkv); }
+const float* qkv_bias(const savad_model* m, int l, bool folded) { return m->d_packed + (folded ? m->w.lp[l].bq_vo : m->w.lp[l].bqkv); }
+
+// the row chain of layer l on the image `im`: its own matrices, then the next layer's Q / K / V projection into `nxt`, or the
+// classifier into `out` after the last layer (bf::RowArgsBf16, which adds satcnt, and fs::RowArgs3)
+template <typename Args, typename H>
+Args row_args(const savad_model* m, const FragImage& im, bool folded, int l, int B, int T, int nblk, H* hb, char* const* nxt, float* out) {
+    const weights::Layout& w = m->w;
+    const float *R = m->d_raw, *P = m->d_packed;
+    const auto& f = im.at->layer[l];
+    const bool last = l + 1 == m->cfg.num_layers;
+    Args A;
+    A.B = B;
+    A.T = T;
+    A.nblk = nblk;
+    A.hbuf = hb;
+    A.wo_frag = im.d + f.wo;  // (not read by the folded launches)
+    A.bo = R + w.lr[l].bo;
+    A.w1_frag = im.d + f.w1;
+    A.b1 = P + w.lp[l].b1;
+    A.w2_frag = im.d + f.w2;
+    A.b2 = R + w.lr[l].b2;
+    A.wn_frag = last ? nullptr : qkv_frags(im, l + 1, folded);
+    A.wc = last ? P + w.p_wc : nullptr;
+    A.bn = last ? P + w.p_bc : qkv_bias(m, l + 1, folded);
+    A.qf = nxt[0];
+    A.kf = nxt[1];
+    A.vtf = nxt[2];
+    A.out = out;
+    A.qscale = qscale();
+    return A;
+}
+
+// bf16-operand forward, T > 32: input_qkv -> [attention -> row] x L on fragment-major buffers
+void forward_bf16(savad_model* m, const sched::ForwardPlan& bp, const Features& in, int B, int T, float* out, char* W, hipStream_t st, Prof& prof) {
     bf::hres_t* hb = (bf::hres_t*)(W + bp.h);
     char *qf = W + bp.q, *kf = W + bp.k, *vtf = W + bp.v, *ctxf = W + bp.ctx;
-    const int L = m->cfg.num_layers;
-    int F = m->cfg.feature_size;
-    if (bp.pad) {
-        float* xp = (float*)(W + bp.xpad);
-        if (x_is_bf16)
-            pad_features(st, (const __bf16*)x, (size_t)B * T, F, m->FP, xp);
-        else
-            pad_features(st, (const float*)x, (size_t)B * T, F, m->FP, xp);
-        x = xp;
-        x_is_bf16 = 0;
-        F = m->FP;
-    }
-    const long xbs = xbs_in > 0 ? xbs_in : (long)T * F;
+    const int L = m->cfg.num_layers, F = in.F;
+    const long xbs = in.xbs;
     const float c = qscale();
-    const float* R = m->d_raw;
-    const float* P = m->d_packed;
-    const char* Fr = m->d_frag;
-    Prof prof(m, st);
-    if (bp.form == sched::SINGLE) {
-        WindowOffsets none;
-        none.w = 0;
-        launch_packed_forward_bf16(m, bp.variant, st, (const float*)x, B, T, F, out, none, 0);
-        prof.mark("packed_forward_bf16");
-        prof.done();
-        HIP_TRY(hipGetLastError());
-        return SAVAD_OK;
-    }
+    const FragImage& im = m->bf16;
+    const char* win = im.d + im.at->win;
+    const float* bin = m->d_raw + m->w.r_bin;
     const bool fused = bp.form == sched::FUSED;
     auto run = [&](auto nw_tag) {
         constexpr int NW = decltype(nw_tag)::value;
@@ -865,50 +762,29 @@ int forward_bf16(savad_model* m, const sched::ForwardPlan& bp, const void* x, in
                 using XT = decltype(xt);
                 constexpr int KSC = decltype(ks_tag)::value;
                 hipLaunchKernelGGL((bf::input_qkv_kernel_bf16_p<XT, 8, KSC>), dim3(m->n_cu), dim3(512), bf::input_p_lds_bytes(F / 16), st,
-                                   (const XT*)x, xbs, B, T, F, bp.nblk, bp.nblk_pad, Fr + m->f_win, R + m->r_bin, m->d_pe,
-                                   Fr + m->lf[0].wqkv, P + m->lp[0].bqkv, hb, qf, kf, vtf, c, m->d_sat);
+                                   (const XT*)in.x, xbs, B, T, F, bp.nblk, bp.nblk_pad, win, bin, m->d_pe,
+                                   qkv_frags(im, 0, false), qkv_bias(m, 0, false), hb, qf, kf, vtf, c, m->d_sat);
             };
             if (bp.KSC == 5) {
-                if (x_is_bf16) go(__bf16{}, std::integral_constant<int, 5>{}); else go(float{}, std::integral_constant<int, 5>{});
+                if (in.is_bf16) go(__bf16{}, std::integral_constant<int, 5>{}); else go(float{}, std::integral_constant<int, 5>{});
             } else {
-                if (x_is_bf16) go(__bf16{}, std::integral_constant<int, 0>{}); else go(float{}, std::integral_constant<int, 0>{});
+                if (in.is_bf16) go(__bf16{}, std::integral_constant<int, 0>{}); else go(float{}, std::integral_constant<int, 0>{});
             }
-        } else if (x_is_bf16)
-            hipLaunchKernelGGL((bf::input_qkv_kernel_bf16<__bf16, NW>), dim3(grid_rows), wg, ring + 3 * D * 4, st, (const __bf16*)x, xbs,
-                               B, T, F, bp.nblk, Fr + m->f_win, R + m->r_bin, m->d_pe, Fr + m->lf[0].wqkv, P + m->lp[0].bqkv, hb,
+        } else if (in.is_bf16)
+            hipLaunchKernelGGL((bf::input_qkv_kernel_bf16<__bf16, NW>), dim3(grid_rows), wg, ring + 3 * D * 4, st, (const __bf16*)in.x, xbs,
+                               B, T, F, bp.nblk, win, bin, m->d_pe, qkv_frags(im, 0, false), qkv_bias(m, 0, false), hb,
                                qf, kf, vtf, c, m->d_sat);
         else
-            hipLaunchKernelGGL((bf::input_qkv_kernel_bf16<float, NW>), dim3(grid_rows), wg, ring + 3 * D * 4, st, (const float*)x, xbs, B,
-                               T, F, bp.nblk, Fr + m->f_win, R + m->r_bin, m->d_pe, Fr + m->lf[0].wqkv, P + m->lp[0].bqkv, hb, qf,
+            hipLaunchKernelGGL((bf::input_qkv_kernel_bf16<float, NW>), dim3(grid_rows), wg, ring + 3 * D * 4, st, (const float*)in.x, xbs, B,
+                               T, F, bp.nblk, win, bin, m->d_pe, qkv_frags(im, 0, false), qkv_bias(m, 0, false), hb, qf,
                                kf, vtf, c, m->d_sat);
         prof.mark("input_qkv_bf16");
         char* sets[2][3] = {{qf, kf, vtf}, {W + bp.q2, W + bp.k2, W + bp.v2}};
         for (int l = 0; l < L; ++l) {
-            const auto& r = m->lr[l];
-            const auto& p = m->lp[l];
-            const auto& f = m->lf[l];
             const bool last = l + 1 == L;
             char** cur = fused ? sets[l & 1] : sets[0];
             char** nxt = fused ? sets[(l + 1) & 1] : sets[0];
-            bf::RowArgsBf16 A;
-            A.B = B;
-            A.T = T;
-            A.nblk = bp.nblk;
-            A.hbuf = hb;
-            A.wo_frag = Fr + f.wo;
-            A.bo = R + r.bo;
-            A.w1_frag = Fr + f.w1;
-            A.b1 = P + p.b1;
-            A.w2_frag = Fr + f.w2;
-            A.b2 = R + r.b2;
-            A.wn_frag = last ? nullptr : Fr + m->lf[l + 1].wqkv;
-            A.wc = last ? P + m->p_wc : nullptr;
-            A.bn = last ? P + m->p_bc : P + m->lp[l + 1].bqkv;
-            A.qf = nxt[0];
-            A.kf = nxt[1];
-            A.vtf = nxt[2];
-            A.out = out;
-            A.qscale = c;
+            bf::RowArgsBf16 A = row_args<bf::RowArgsBf16>(m, im, false, l, B, T, bp.nblk, hb, nxt, out);
             A.satcnt = m->d_sat;
             const dim3 grid_groups(8 * (((long)B * bp.NG + 7) / 8));  // a workgroup per query-block group, whole XCD rounds
             if (fused) {
@@ -940,15 +816,11 @@ int forward_bf16(savad_model* m, const sched::ForwardPlan& bp, const void* x, in
         run(std::integral_constant<int, 8>{});
     else
         run(std::integral_constant<int, 4>{});
-    prof.done();
-    HIP_TRY(hipGetLastError());
-    return SAVAD_OK;
 }
-
 
 int prepare_f32s_launch(savad_model* m) {
     int rc;
-    if (m->lds_attrs3_set) return SAVAD_OK;
+    if (m->f32s.lds_attrs_set) return SAVAD_OK;
     if ((rc = allow_lds(fs::input_qkv_kernel_f32s_plain, fs::NRING3 * fs::SLOT_BYTES + 3 * D * 4))) return rc;
     if ((rc = allow_lds(fs::input_qkv_kernel_f32s, fs::NRING3 * fs::SLOT_BYTES + 3 * D * 4))) return rc;
     if ((rc = allow_lds(fs::attention_row_kernel_f32s<false, false>, fs::ROW_LDS_BYTES))) return rc;
@@ -957,102 +829,29 @@ int prepare_f32s_launch(savad_model* m) {
     if ((rc = allow_lds(fs::attention_row_kernel_f32s<true, true>, fs::ROW_LDS_BYTES))) return rc;
     if ((rc = allow_lds(fs::packed_forward_kernel_f32s, fs::packed_f32s_lds_bytes(fs::PACKED_F32S_MAX_LAYERS)))) return rc;
     if ((rc = allow_lds(fs::packed_forward_kernel_f32s_ns, fs::nsf_lds_bytes(fs::PACKED_F32S_MAX_LAYERS)))) return rc;
-    m->lds_attrs3_set = true;
+    m->f32s.lds_attrs_set = true;
     return SAVAD_OK;
 }
 
-// T <= 32 in precision 2: the whole forward in one launch, in the variant the plan names (sched::single_f32s_variant)
-void launch_packed_forward_f32s(savad_model* m, int variant, hipStream_t st, const float* x, int B, int T, int F, float* out, const WindowOffsets& wo,
-                                int win_base) {
-    const int L = m->cfg.num_layers;
-    const char* Fr = m->d_frag3;
-    const int G = 32 / T, nblk = (B + G - 1) / G;
-    fs::PackedF32sModel pm;
-    for (int l = 0; l < fs::PACKED_F32S_MAX_LAYERS; ++l) {
-        const auto& f = m->lf3[l < L ? l : 0];
-        pm.layer[l] = fs::PackedF32sLayer{Fr + f.wqkv, Fr + f.wo, Fr + f.w1, Fr + f.w2};
-    }
-    pm.win = Fr + m->f3_win;
-    pm.bin = m->d_raw + m->r_bin;
-    pm.pe = m->d_pe;
-    pm.bias = m->d_packed + m->p_bias;
-    pm.wc = m->d_packed + m->p_wc;
-    pm.bc = m->d_packed + m->p_bc;
-    pm.L = L;
-    const float c = qscale();
-    if (variant == sched::VARIANT_LATENCY)
-        hipLaunchKernelGGL(fs::packed_forward_kernel_f32s_ns, dim3(nblk), dim3(256), fs::nsf_lds_bytes(L), st, x, B, T, F, nblk, pm, c, out, wo, win_base);
-    else
-        hipLaunchKernelGGL(fs::packed_forward_kernel_f32s, dim3((nblk + 3) / 4), dim3(256), fs::packed_f32s_lds_bytes(L), st, x, B, T, F, nblk, pm, c,
-                           out, wo, win_base);
-}
-
-// fp32s forward (precision 2): input_qkv -> [attention + row chain] x L, every GEMM as six bf16 MFMA products of three-piece operands
-int forward_f32s(savad_model* m, const sched::ForwardPlan& bp, const float* x, int B, int T, long xbs_in, float* out, void* workspace,
-                 hipStream_t st) {
-    char* W = (char*)workspace;
+// fp32s forward (precision 2), T > 32: input_qkv -> [attention + row chain] x L, every GEMM as six bf16 MFMA products of three-piece operands
+void forward_f32s(savad_model* m, const sched::ForwardPlan& bp, const Features& in, int B, int T, float* out, char* W, hipStream_t st, Prof& prof) {
     float* hb = (float*)(W + bp.h);
     const int L = m->cfg.num_layers;
-    int F = m->cfg.feature_size;
-    if (bp.pad) {
-        float* xp = (float*)(W + bp.xpad);
-        pad_features(st, x, (size_t)B * T, F, m->FP, xp);
-        x = xp;
-        F = m->FP;
-    }
-    const long xbs = xbs_in > 0 ? xbs_in : (long)T * F;
-    const float c = qscale();
-    const float* R = m->d_raw;
-    const float* P = m->d_packed;
-    const char* Fr = m->d_frag3;
-    Prof prof(m, st);
-    if (bp.form == sched::SINGLE) {
-        WindowOffsets none;
-        none.w = 0;
-        launch_packed_forward_f32s(m, bp.variant, st, x, B, T, F, out, none, 0);
-        prof.mark("packed_forward_f32s");
-        prof.done();
-        HIP_TRY(hipGetLastError());
-        return SAVAD_OK;
-    }
+    const FragImage& im = m->f32s;
     char* sets[2][3] = {{W + bp.q, W + bp.k, W + bp.v}, {W + bp.q2, W + bp.k2, W + bp.v2}};
-    const bool packed = !bp.fold_v;  // the T <= 32 form of the launch: the plain Q/K/V images and its own out-projection
-    // (bp.fold_v: the image Wq~ | Wo Wv' -- four slots, the keys are the normalised rows -- and its biases bq~ | Wo bv')
-    auto wqkv3 = [&](int l) { return Fr + (packed ? m->lf3[l].wqkv : m->lf3[l].wq_vo); };
-    auto bqkv3 = [&](int l) { return P + (packed ? m->lp[l].bqkv : m->lp[l].bq_vo); };
-    const auto input_qkv = packed ? fs::input_qkv_kernel_f32s_plain : fs::input_qkv_kernel_f32s;
-    hipLaunchKernelGGL(input_qkv, dim3(bp.nblk_pad / 4), dim3(256), fs::NRING3 * fs::SLOT_BYTES + 3 * D * 4, st, x, xbs, B, T, F,
-                       bp.nblk, Fr + m->f3_win, R + m->r_bin, m->d_pe, wqkv3(0), bqkv3(0), hb, sets[0][0], sets[0][1], sets[0][2], c);
+    const bool folded = bp.fold_v;  // otherwise the T <= 32 form of the launch: the plain Q/K/V images and its own out-projection
+    const auto input_qkv = folded ? fs::input_qkv_kernel_f32s : fs::input_qkv_kernel_f32s_plain;
+    hipLaunchKernelGGL(input_qkv, dim3(bp.nblk_pad / 4), dim3(256), fs::NRING3 * fs::SLOT_BYTES + 3 * D * 4, st, (const float*)in.x, in.xbs, B, T, in.F,
+                       bp.nblk, im.d + im.at->win, m->d_raw + m->w.r_bin, m->d_pe, qkv_frags(im, 0, folded), qkv_bias(m, 0, folded), hb, sets[0][0],
+                       sets[0][1], sets[0][2], qscale());
     prof.mark("input_qkv_f32s");
     const int NG = bp.NG;
-    const dim3 grid(packed ? bp.nblk_pad / 4 : 8 * (((long)B * NG + 7) / 8));
+    const dim3 grid(folded ? 8 * (((long)B * NG + 7) / 8) : bp.nblk_pad / 4);
     for (int l = 0; l < L; ++l) {
-        const auto& r = m->lr[l];
-        const auto& p = m->lp[l];
-        const auto& f = m->lf3[l];
         const bool last = l + 1 == L;
         char** cur = sets[l & 1];
-        char** nxt = sets[(l + 1) & 1];
-        fs::RowArgs3 A;
-        A.B = B;
-        A.T = T;
-        A.nblk = bp.nblk;
-        A.hbuf = hb;
-        A.wo_frag = Fr + f.wo;   // (read by the T <= 32 form only)
-        A.bo = R + r.bo;
-        A.w1_frag = Fr + f.w1;
-        A.b1 = P + p.b1;
-        A.w2_frag = Fr + f.w2;
-        A.b2 = R + r.b2;
-        A.wn_frag = last ? nullptr : wqkv3(l + 1);
-        A.wc = last ? P + m->p_wc : nullptr;
-        A.bn = last ? P + m->p_bc : bqkv3(l + 1);
-        A.qf = nxt[0];
-        A.kf = nxt[1];
-        A.vtf = nxt[2];
-        A.out = out;
-        A.qscale = c;
-        if (packed) {
+        const fs::RowArgs3 A = row_args<fs::RowArgs3>(m, im, folded, l, B, T, bp.nblk, hb, sets[(l + 1) & 1], out);
+        if (!folded) {
             if (last) hipLaunchKernelGGL((fs::attention_row_kernel_f32s<true, true>), grid, dim3(256), fs::ROW_LDS_BYTES, st, cur[0], cur[1], cur[2], NG, A);
             else hipLaunchKernelGGL((fs::attention_row_kernel_f32s<false, true>), grid, dim3(256), fs::ROW_LDS_BYTES, st, cur[0], cur[1], cur[2], NG, A);
         } else {
@@ -1061,98 +860,51 @@ int forward_f32s(savad_model* m, const sched::ForwardPlan& bp, const float* x, i
         }
         prof.mark(last ? "attention_row_last_f32s" : "attention_row_f32s");
     }
-    prof.done();
-    HIP_TRY(hipGetLastError());
-    return SAVAD_OK;
 }
 
-}  // namespace
-
-namespace {
-// the single-launch T <= 32 forward (packed_forward_kernel); weights and the PE table must be ready
-void launch_packed_forward(savad_model* m, hipStream_t st, const float* x, int B, int T, int F, float* out, const WindowOffsets& wo,
-                           int win_base) {
-    const int L = m->cfg.num_layers;
-    const float* R = m->d_raw;
-    const float* P = m->d_packed;
-    const float c = qscale();
-    const int G = 32 / T, nblk = (B + G - 1) / G;
-    PackedModel pm;
-    for (int l = 0; l < L; ++l) pm.layer[l] = PackedLayer{P + m->lp[l].frag};
-    for (int l = L; l < PACKED_MAX_LAYERS; ++l) pm.layer[l] = pm.layer[0];
-    pm.bias = P + m->p_bias;
-    pm.win = win_fp32(m);
-    pm.bin = R + m->r_bin;
-    pm.pe = m->d_pe;
-    pm.wc = P + m->p_wc;
-    pm.bc = P + m->p_bc;
-    pm.L = L;
-    hipLaunchKernelGGL(packed_forward_kernel, dim3(nblk), dim3(256), 0, st, x, B * T, T, F, pm, c, out, G * T, wo, win_base);
-}
-
-// exact-fp32 forward (precision 0, and the shapes precision 2 hands over): input_qkv -> [attention -> row] x L on row-major fp32 buffers
-int forward_f32(savad_model* m, const sched::ForwardPlan& ws, const float* x, int B, int T, long xbs_in, float* out, void* workspace,
-                hipStream_t st) {
-    char* W = (char*)workspace;
+// exact-fp32 forward (precision 0, and the shapes precision 2 hands over), T > 32: input_qkv -> [attention -> row] x L on row-major fp32 buffers
+void forward_f32(savad_model* m, const sched::ForwardPlan& ws, const Features& in, int B, int T, float* out, char* W, hipStream_t st, Prof& prof) {
     auto at = [W](size_t off) { return (float*)(W + off); };
     float *hb = at(ws.h), *q = at(ws.q), *k = at(ws.k), *v = at(ws.v), *op = at(ws.opart), *ml = at(ws.ml);
-    const int L = m->cfg.num_layers;
-    int F = m->cfg.feature_size;
-    if (ws.pad) {
-        float* xp = at(ws.xpad);
-        pad_features(st, x, ws.rows, F, m->FP, xp);
-        x = xp;
-        F = m->FP;
-    }
-    const long xbs = xbs_in > 0 ? xbs_in : (long)T * F;
+    const int L = m->cfg.num_layers, F = in.F;
+    const float* x = (const float*)in.x;
+    const long xbs = in.xbs;
     const int tiles = (int)(ws.rows_pad / TILE);
     const float c = qscale();
     const float* R = m->d_raw;
     const float* P = m->d_packed;
-    Prof prof(m, st);
-
+    const weights::Layout& w = m->w;
     const int tiles_m = (int)(ws.rows_pad / 128);
     const bool msplit = ws.msplit;
-    if (ws.form == sched::SINGLE) {
-        WindowOffsets none;
-        none.w = 0;
-        launch_packed_forward(m, st, x, B, T, F, out, none, 0);
-        prof.mark("packed_forward");
-        prof.done();
-        HIP_TRY(hipGetLastError());
-        return SAVAD_OK;
-    }
     if (msplit)
         hipLaunchKernelGGL(input_qkv_kernel_m, dim3(tiles_m), dim3(256), 0, st, x, xbs, (int)ws.rows, T, F, win_fp32(m),
-                           R + m->r_bin, m->d_pe, P + m->lp[0].wqkv, P + m->lp[0].bqkv, hb, q, k, v);
+                           R + w.r_bin, m->d_pe, P + w.lp[0].wqkv, P + w.lp[0].bqkv, hb, q, k, v);
     else
         hipLaunchKernelGGL(input_qkv_kernel, dim3(tiles), dim3(256), 0, st, x, xbs, (int)ws.rows, T, F, win_fp32(m),
-                           R + m->r_bin, m->d_pe, P + m->lp[0].frag, P + m->lp[0].bqkv, hb, q, k, v);
+                           R + w.r_bin, m->d_pe, P + w.lp[0].frag, P + w.lp[0].bqkv, hb, q, k, v);
     prof.mark("input_qkv");
     const int NG = ws.NG;
     if (ws.form == sched::FUSED) {
         float* qkv[2][3] = {{q, k, v}, {at(ws.q2), at(ws.k2), at(ws.v2)}};
         const int grid = (int)(8 * (((long)B * NG + 7) / 8));
         for (int l = 0; l < L; ++l) {
-            const auto& r = m->lr[l];
-            const auto& p = m->lp[l];
+            const auto& r = w.lr[l];
+            const auto& p = w.lp[l];
             float** cur = qkv[l & 1];
             float** nxt = qkv[(l + 1) & 1];
             if (l + 1 < L) {
                 hipLaunchKernelGGL(attention_row_kernel<false>, dim3(grid), dim3(256), 0, st, cur[0], cur[1], cur[2], B, T, NG, c, hb,
-                                   R + r.wo, R + r.bo, P + p.w1, P + p.b1, R + r.w2, R + r.b2, P + m->lp[l + 1].wqkv,
-                                   P + m->lp[l + 1].bqkv, nxt[0], nxt[1], nxt[2], out);
+                                   R + r.wo, R + r.bo, P + p.w1, P + p.b1, R + r.w2, R + r.b2, P + w.lp[l + 1].wqkv,
+                                   P + w.lp[l + 1].bqkv, nxt[0], nxt[1], nxt[2], out);
                 prof.mark("attention_row");
             } else {
                 hipLaunchKernelGGL(attention_row_kernel<true>, dim3(grid), dim3(256), 0, st, cur[0], cur[1], cur[2], B, T, NG, c, hb,
-                                   R + r.wo, R + r.bo, P + p.w1, P + p.b1, R + r.w2, R + r.b2, P + m->p_wc, P + m->p_bc, nxt[0],
+                                   R + r.wo, R + r.bo, P + p.w1, P + p.b1, R + r.w2, R + r.b2, P + w.p_wc, P + w.p_bc, nxt[0],
                                    nxt[1], nxt[2], out);
                 prof.mark("attention_row_last");
             }
         }
-        prof.done();
-        HIP_TRY(hipGetLastError());
-        return SAVAD_OK;
+        return;
     }
     for (int l = 0; l < L; ++l) {
         if (ws.attn == sched::ATTN_PACKED) {
@@ -1163,8 +915,8 @@ int forward_f32(savad_model* m, const sched::ForwardPlan& ws, const float* x, in
                                ws.S, NG, c);
         }
         prof.mark("attention");
-        const auto& r = m->lr[l];
-        const auto& p = m->lp[l];
+        const auto& r = w.lr[l];
+        const auto& p = w.lp[l];
 #define SAVAD_ROW_ARGS(WN, BN) op, ml, ws.S, (int)ws.rows, (int)ws.rows_pad, c, hb, R + r.wo, R + r.bo, P + p.w1, P + p.b1, \
                                R + r.w2, R + r.b2, WN, BN, q, k, v, out
 #define SAVAD_ROWN_ARGS(NFRAG, WN, BN) op, ml, ws.S, (int)ws.rows, (int)ws.rows_pad, c, hb, P + p.frag, R + r.bo, P + p.b1, R + r.b2, \
@@ -1172,31 +924,27 @@ int forward_f32(savad_model* m, const sched::ForwardPlan& ws, const float* x, in
         if (l + 1 < L) {
             if (msplit)
                 hipLaunchKernelGGL(row_kernel_m<false>, dim3(tiles_m), dim3(256), 0, st,
-                                   SAVAD_ROW_ARGS(P + m->lp[l + 1].wqkv, P + m->lp[l + 1].bqkv));
+                                   SAVAD_ROW_ARGS(P + w.lp[l + 1].wqkv, P + w.lp[l + 1].bqkv));
             else
-                hipLaunchKernelGGL(row_kernel<false>, dim3(tiles), dim3(256), 0, st, SAVAD_ROWN_ARGS(P + m->lp[l + 1].frag, P, P + m->lp[l + 1].bqkv));
+                hipLaunchKernelGGL(row_kernel<false>, dim3(tiles), dim3(256), 0, st, SAVAD_ROWN_ARGS(P + w.lp[l + 1].frag, P, P + w.lp[l + 1].bqkv));
             prof.mark("row");
         } else {
             if (msplit)
                 hipLaunchKernelGGL(row_kernel_m<true>, dim3(tiles_m), dim3(256), 0, st,
-                                   SAVAD_ROW_ARGS(P + m->p_wc, P + m->p_bc));
+                                   SAVAD_ROW_ARGS(P + w.p_wc, P + w.p_bc));
             else
-                hipLaunchKernelGGL(row_kernel<true>, dim3(tiles), dim3(256), 0, st, SAVAD_ROWN_ARGS(P + p.frag, P + m->p_wc, P + m->p_bc));
+                hipLaunchKernelGGL(row_kernel<true>, dim3(tiles), dim3(256), 0, st, SAVAD_ROWN_ARGS(P + p.frag, P + w.p_wc, P + w.p_bc));
             prof.mark("row_last");
         }
 #undef SAVAD_ROW_ARGS
 #undef SAVAD_ROWN_ARGS
     }
-    prof.done();
-    HIP_TRY(hipGetLastError());
-    return SAVAD_OK;
 }
 
 // every forward entry point ends here: validate, plan once (savad_schedule.h), make the family's weights ready, launch what the plan
 // names.  xbs_in: elements between consecutive sequences of x (savad_forward_strided), 0 = T * F
-int forward_any(savad_handle m, const void* xv, int x_dtype, int B, int T, long xbs_in, float* out, void* workspace, size_t workspace_bytes,
+int forward_any(savad_handle m, const void* x, int x_dtype, int B, int T, long xbs_in, float* out, void* workspace, size_t workspace_bytes,
                 void* stream) {
-    const float* x = (const float*)xv;
     if (!m) return fail(SAVAD_E_INVALID, "null handle");
     if (B < 0 || T < 0) return fail(SAVAD_E_INVALID, "negative shape B=%d T=%d", B, T);
     if (B == 0 || T == 0) return SAVAD_OK;
@@ -1210,12 +958,24 @@ int forward_any(savad_handle m, const void* xv, int x_dtype, int B, int T, long 
     if (workspace_bytes < p.total) return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
     int rc;
     if ((rc = ensure_ready(m, p.family, T, st))) return rc;
-    switch (p.family) {
-        case sched::GENERIC: return forward_generic(m, p, x, B, T, out, workspace, st);
-        case sched::BF16: return forward_bf16(m, p, xv, x_dtype, B, T, xbs_in, out, workspace, st);
-        case sched::F32S: return forward_f32s(m, p, x, B, T, xbs_in, out, workspace, st);
-        default: return forward_f32(m, p, x, B, T, xbs_in, out, workspace, st);
+    char* W = (char*)workspace;
+    const Features in = forward_input(m, p, x, p.family == sched::BF16 ? x_dtype : 0, B, T, xbs_in, W, st);
+    Prof prof(m, st);
+    if (p.form == sched::SINGLE) {
+        WindowOffsets none;
+        none.w = 0;
+        prof.mark(launch_single(m, p.family, p.variant, st, (const float*)in.x, B, T, in.F, out, none, 0));
+    } else {
+        switch (p.family) {
+            case sched::GENERIC: forward_generic(m, p, (const float*)x, B, T, out, workspace, st, prof); break;
+            case sched::BF16: forward_bf16(m, p, in, B, T, out, W, st, prof); break;
+            case sched::F32S: forward_f32s(m, p, in, B, T, out, W, st, prof); break;
+            default: forward_f32(m, p, in, B, T, out, W, st, prof);
+        }
     }
+    prof.done();
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
 }
 }  // namespace
 
@@ -1225,7 +985,7 @@ SAVAD_EXPORT int savad_forward_ex(savad_handle m, const void* x, int x_dtype, in
     if (!m) return fail(SAVAD_E_INVALID, "null handle");
     if (x_dtype == 0 && m->precision != 1) return savad_forward(m, (const float*)x, B, T, out, workspace, workspace_bytes, stream);
     if (x_dtype < 0 || x_dtype > 1) return fail(SAVAD_E_INVALID, "x_dtype %d", x_dtype);
-    if (m->generic) return fail(SAVAD_E_UNSUPPORTED, "bf16 features need the d_model=128 kernels (this handle: d_model=%d, fp32)", m->cfg.d_model);
+    if (m->w.generic) return fail(SAVAD_E_UNSUPPORTED, "bf16 features need the d_model=128 kernels (this handle: d_model=%d, fp32)", m->cfg.d_model);
     if (m->precision != 1) return fail(SAVAD_E_UNSUPPORTED, "bf16 features need savad_set_precision(h, 1)");
     return forward_any(m, x, x_dtype, B, T, 0, out, workspace, workspace_bytes, stream);
 }
@@ -1233,9 +993,9 @@ SAVAD_EXPORT int savad_forward_ex(savad_handle m, const void* x, int x_dtype, in
 SAVAD_EXPORT int savad_forward_strided(savad_handle m, const void* x, int x_dtype, int B, int T, long x_batch_stride, float* out,
                                        void* workspace, size_t workspace_bytes, void* stream) {
     if (!m) return fail(SAVAD_E_INVALID, "null handle");
-    if (m->generic) return fail(SAVAD_E_UNSUPPORTED, "strided input needs the d_model=128 kernels");
+    if (m->w.generic) return fail(SAVAD_E_UNSUPPORTED, "strided input needs the d_model=128 kernels");
     if (T <= 32) return fail(SAVAD_E_UNSUPPORTED, "strided input is for sequences longer than 32 frames (windows of T <= 32 are read in place by savad_predict_probabilities)");
-    if (m->FP != m->cfg.feature_size) return fail(SAVAD_E_UNSUPPORTED, "strided input needs feature_size %% 16 == 0 (no padding copy)");
+    if (m->w.FP != m->cfg.feature_size) return fail(SAVAD_E_UNSUPPORTED, "strided input needs feature_size %% 16 == 0 (no padding copy)");
     const long F = m->cfg.feature_size;
     if (x_batch_stride <= 0 || x_batch_stride % 4 || x_batch_stride % F)
         return fail(SAVAD_E_INVALID, "x_batch_stride=%ld (a positive multiple of feature_size and of 4 elements)", x_batch_stride);
@@ -1299,19 +1059,28 @@ SAVAD_EXPORT int savad_window_offsets(int half, int jump, int32_t* offsets) {
     return w;
 }
 
+namespace {
+// the window geometry as the kernels take it; a window longer than WindowOffsets holds is refused
+int window_offsets(int half, int jump, WindowOffsets* wo) {
+    wo->w = savad_window_offsets(half, jump, nullptr);
+    if (wo->w < 0) return wo->w;
+    if (wo->w > 64) return fail(SAVAD_E_UNSUPPORTED, "window longer than 64 frames");
+    static_assert(std::is_same<decltype(wo->off[0]), int32_t&>::value, "WindowOffsets::off");
+    savad_window_offsets(half, jump, wo->off);
+    return SAVAD_OK;
+}
+}  // namespace
+
 SAVAD_EXPORT int savad_gather_windows(const float* feature, int N, int F, int half, int jump, int first, int count,
                                       float* windows, int64_t* positions, void* stream) {
     if (count == 0) return SAVAD_OK;
     if (!feature || !windows || N <= 0 || F <= 0 || first < 0 || count < 0) return fail(SAVAD_E_INVALID, "bad argument");
     WindowOffsets wo;
-    int32_t off[256];
-    if (savad_window_offsets(half, jump, nullptr) > 64) return fail(SAVAD_E_UNSUPPORTED, "window longer than 64 frames");
-    wo.w = savad_window_offsets(half, jump, off);
-    for (int i = 0; i < wo.w; ++i) wo.off[i] = off[i];
-    if ((long)half + first + count - 1 + off[wo.w - 1] >= N || half + first + off[0] < 0)
+    int rc = window_offsets(half, jump, &wo);
+    if (rc) return rc;
+    if ((long)half + first + count - 1 + wo.off[wo.w - 1] >= N || half + first + wo.off[0] < 0)
         return fail(SAVAD_E_INVALID, "window [%d,%d) reaches outside the %d feature frames", first, first + count, N);
-    const size_t total = (size_t)count * wo.w * (F % 4 ? F : F / 4);
-    const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    const int grid = grid_for((long)count * wo.w * (F % 4 ? F : F / 4), 2048);
     if (F % 4)
         hipLaunchKernelGGL(gather_windows_scalar_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feature, F, half, first,
                            count, wo, windows, positions);
@@ -1331,11 +1100,9 @@ SAVAD_EXPORT int savad_boost(const float* logp, const int64_t* positions, int co
     HIP_TRY(hipMemsetAsync(boosted_ws, 0, sizeof(float) * (size_t)N * W * 2, st));
     if (count > 0) {
         const size_t cw = (size_t)count * W;
-        const int grid = (int)((cw + 255) / 256 < 2048 ? (cw + 255) / 256 : 2048);
-        hipLaunchKernelGGL(boost_scatter_kernel, dim3(grid), dim3(256), 0, st, logp, positions, cw, W, boosted_ws);
+        hipLaunchKernelGGL(boost_scatter_kernel, dim3(grid_for((long)cw, 2048)), dim3(256), 0, st, logp, positions, cw, W, boosted_ws);
     }
-    const int grid2 = (N + 255) / 256 < 2048 ? (N + 255) / 256 : 2048;
-    hipLaunchKernelGGL(boost_softmax_kernel, dim3(grid2), dim3(256), 0, st, boosted_ws, N, W, probs, mean);
+    hipLaunchKernelGGL(boost_softmax_kernel, dim3(grid_for(N, 2048)), dim3(256), 0, st, boosted_ws, N, W, probs, mean);
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }
@@ -1373,12 +1140,10 @@ SAVAD_EXPORT int savad_predict_probabilities(savad_handle m, const float* featur
     if (rc) return rc;
     if (workspace_bytes < p.total) return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
     hipStream_t st = (hipStream_t)stream;
-    const int F = m->cfg.feature_size, W = p.W;  // (F % 4 != 0: never windowed -- m->FP != F -- the windows go through savad_gather_windows)
+    const int F = m->cfg.feature_size, W = p.W;  // (F % 4 != 0: never windowed -- m->w.FP != F -- the windows go through savad_gather_windows)
     WindowOffsets wo;
-    int32_t off[64];
-    wo.w = savad_window_offsets(half, jump, off);
-    for (int i = 0; i < wo.w; ++i) wo.off[i] = off[i];
-    if (p.n_items > 0 && (half + off[0] < 0 || (long)half + p.n_items - 1 + off[W - 1] >= N))
+    if ((rc = window_offsets(half, jump, &wo))) return rc;
+    if (p.n_items > 0 && (half + wo.off[0] < 0 || (long)half + p.n_items - 1 + wo.off[W - 1] >= N))
         return fail(SAVAD_E_INVALID, "windows reach outside the %d feature frames", N);
     char* ws = (char*)workspace;
     float* logp = (float*)(ws + p.logp);
@@ -1387,20 +1152,15 @@ SAVAD_EXPORT int savad_predict_probabilities(savad_handle m, const float* featur
         const int count = p.n_items - first < p.chunk ? p.n_items - first : p.chunk;
         float* out = logp + (size_t)first * W * 2;
         const int variant = count == p.chunk ? p.variant : p.variant_last;
-        if (p.windowed && p.family == sched::BF16) {
-            launch_packed_forward_bf16(m, variant, st, feature, count, W, F, out, wo, half + first);
-        } else if (p.windowed && p.family == sched::F32S) {
-            launch_packed_forward_f32s(m, variant, st, feature, count, W, F, out, wo, half + first);
-        } else if (p.windowed) {
-            launch_packed_forward(m, st, feature, count, W, F, out, wo, half + first);
+        if (p.windowed) {
+            launch_single(m, p.family, variant, st, feature, count, W, F, out, wo, half + first);
         } else {
             float* win = (float*)(ws + p.windows);
             if ((rc = savad_gather_windows(feature, N, F, half, jump, first, count, win, nullptr, stream))) return rc;
             if ((rc = savad_forward(m, win, count, W, out, ws + p.fwd, p.fwd_bytes, stream))) return rc;
         }
     }
-    const int grid = (N + 255) / 256 < 2048 ? (N + 255) / 256 : 2048;
-    hipLaunchKernelGGL(boost_gather_kernel, dim3(grid), dim3(256), 0, st, logp, p.n_items, N, half, wo, probs, mean);
+    hipLaunchKernelGGL(boost_gather_kernel, dim3(grid_for(N, 2048)), dim3(256), 0, st, logp, p.n_items, N, half, wo, probs, mean);
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }
@@ -1415,8 +1175,7 @@ SAVAD_EXPORT int savad_gather_strided(const float* feature, int N, int F, int T,
     if (count == 0) return SAVAD_OK;
     if (!feature || !windows || N <= 0 || F <= 0 || F % 4 || T <= 0 || hop <= 0 || first < 0 || count < 0)
         return fail(SAVAD_E_INVALID, "bad argument (F must be a multiple of 4)");
-    const size_t total = (size_t)count * T * (F / 4);
-    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    const int grid = grid_for((long)count * T * (F / 4));
     hipLaunchKernelGGL(gather_strided_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feature, N, F, T, hop, first,
                        count, windows);
     HIP_TRY(hipGetLastError());
@@ -1426,7 +1185,7 @@ SAVAD_EXPORT int savad_gather_strided(const float* feature, int N, int F, int T,
 SAVAD_EXPORT int savad_overlap_merge(const float* logp, int W, int N, int T, int hop, float* probs, void* stream) {
     if (N <= 0) return SAVAD_OK;
     if (!logp || !probs || W <= 0 || T <= 0 || hop <= 0) return fail(SAVAD_E_INVALID, "bad argument");
-    const int grid = (N + 255) / 256 < 2048 ? (N + 255) / 256 : 2048;
+    const int grid = grid_for(N, 2048);
     hipLaunchKernelGGL(overlap_merge_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logp, W, N, T, hop, probs);
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
@@ -1690,8 +1449,7 @@ SAVAD_EXPORT int savad_pcm16_to_f32(const short* pcm, long n_samples, float* aud
     if (!pcm || !audio || n_samples < 0) return fail(SAVAD_E_INVALID, "bad argument");
     if (((uintptr_t)pcm & 1) || ((uintptr_t)audio & 15)) return fail(SAVAD_E_INVALID, "pcm must be 2-byte, audio 16-byte aligned");
     const long work = (n_samples + 3) / 4;
-    const int grid = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
-    hipLaunchKernelGGL(pcm16_to_f32_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, pcm, n_samples, audio);
+    hipLaunchKernelGGL(pcm16_to_f32_kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream, pcm, n_samples, audio);
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }
@@ -1752,8 +1510,7 @@ SAVAD_EXPORT int savad_logmel_span(const float* audio, long audio_first, long au
     src.padB = B.dst;
     if (A.count + B.count > 0) {
         const long total = (long)A.count + B.count;
-        const int g1 = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        hipLaunchKernelGGL(mel::reflect_pad_segments_kernel, dim3(g1), dim3(256), 0, st, y0, n_samples, A, B);
+        hipLaunchKernelGGL(mel::reflect_pad_segments_kernel, dim3(grid_for(total)), dim3(256), 0, st, y0, n_samples, A, B);
     }
     const int tiles = (frame_count + 31) / 32;
     const int grid = tiles < g_mel.n_cu ? tiles : g_mel.n_cu;
@@ -1774,8 +1531,7 @@ SAVAD_EXPORT int savad_logmel(const float* audio, int n_samples, float* workspac
     if ((rc = ensure_mel_tables(st, &g_mel))) return rc;
     const int n_frames = 1 + n_samples / mel::HOP;
     const long total = (long)n_samples + mel::N_FFT;
-    const int g1 = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(mel::reflect_pad_kernel, dim3(g1), dim3(256), 0, st, audio, n_samples, workspace);
+    hipLaunchKernelGGL(mel::reflect_pad_kernel, dim3(grid_for(total)), dim3(256), 0, st, audio, n_samples, workspace);
     const int tiles = (n_frames + 31) / 32;
     hipLaunchKernelGGL(mel::logmel_kernel<4>, dim3(tiles), dim3(256), 0, st, workspace, n_frames, g_mel.d_dft, g_mel.d_mel,
                        features);
@@ -1885,7 +1641,6 @@ int fe_tables(const savad_frontend_config* c, FeTables* out) {
     return SAVAD_OK;
 }
 
-int grid_for(long work) { return (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096); }
 
 }  // namespace
 
@@ -2280,26 +2035,21 @@ struct PostLayout {   // byte offsets into the caller's workspace
 
 PostLayout post_layout(int N, const pd::Geometry& g) {
     PostLayout L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    L.last = take(sizeof(int) * (size_t)N);
-    L.next = take(sizeof(int) * (size_t)N);
-    L.sums_f = take(sizeof(int) * (size_t)pd::scan_sums_elems(N));
-    L.frames_end = off;
+    Arena a;
+    L.last = a.take(sizeof(int) * (size_t)N);
+    L.next = a.take(sizeof(int) * (size_t)N);
+    L.sums_f = a.take(sizeof(int) * (size_t)pd::scan_sums_elems(N));
+    L.frames_end = a.off;
     L.seg_cap = (long)N + 2;   // without a split a segment needs a frame of its own
-    L.cls = take((size_t)g.num);
-    L.state = take((size_t)g.num);
-    L.sums_s = take(sizeof(pd::Long2) * (size_t)pd::scan_sums_elems(g.num + 1));
-    L.seg_starts = take(sizeof(long) * (size_t)L.seg_cap);
-    L.seg_ends = take(sizeof(long) * (size_t)L.seg_cap);
-    L.totals = take(sizeof(long) * 2);
-    L.partial = take(sizeof(pd::MinKey) * pd::ARGMIN_GRID);
-    L.result = take(sizeof(pd::MinKey));
-    L.total = off;
+    L.cls = a.take((size_t)g.num);
+    L.state = a.take((size_t)g.num);
+    L.sums_s = a.take(sizeof(pd::Long2) * (size_t)pd::scan_sums_elems(g.num + 1));
+    L.seg_starts = a.take(sizeof(long) * (size_t)L.seg_cap);
+    L.seg_ends = a.take(sizeof(long) * (size_t)L.seg_cap);
+    L.totals = a.take(sizeof(long) * 2);
+    L.partial = a.take(sizeof(pd::MinKey) * pd::ARGMIN_GRID);
+    L.result = a.take(sizeof(pd::MinKey));
+    L.total = a.off;
     return L;
 }
 
@@ -2539,29 +2289,24 @@ struct EvalLayout {   // byte offsets into the caller's workspace: a function of
 
 EvalLayout eval_layout(long N) {
     EvalLayout L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
+    Arena a;
     const size_t n = (size_t)N;
-    L.keys_a = take(sizeof(uint32_t) * n);
-    L.keys_b = take(sizeof(uint32_t) * n);
-    L.y = take(n);
-    L.labels_a = take(n);
-    L.labels_b = take(n);
-    L.spred = take(n);
-    L.bpred = take(n);
-    L.table = take(sizeof(unsigned) * (size_t)ed::sort_table_elems(N));
+    L.keys_a = a.take(sizeof(uint32_t) * n);
+    L.keys_b = a.take(sizeof(uint32_t) * n);
+    L.y = a.take(n);
+    L.labels_a = a.take(n);
+    L.labels_b = a.take(n);
+    L.spred = a.take(n);
+    L.bpred = a.take(n);
+    L.table = a.take(sizeof(unsigned) * (size_t)ed::sort_table_elems(N));
     const size_t sums_sort = sizeof(unsigned) * (size_t)pd::scan_sums_elems(ed::sort_table_elems(N));
     const size_t sums_frames = sizeof(pd::Long2) * (size_t)pd::scan_sums_elems(N);   // (Long2 is the larger of the two frame scans' types)
-    L.sums = take(sums_sort > sums_frames ? sums_sort : sums_frames);
-    L.scan = take(sizeof(ed::HeadNeg) * n);
+    L.sums = a.take(sums_sort > sums_frames ? sums_sort : sums_frames);
+    L.scan = a.take(sizeof(ed::HeadNeg) * n);
     L.seg_cap = (N + 1) / 2;
-    L.seg = take((size_t)ed::SEG_BYTES * (size_t)L.seg_cap);
-    L.counters = take(sizeof(long) * ed::COUNTERS);
-    L.total = off;
+    L.seg = a.take((size_t)ed::SEG_BYTES * (size_t)L.seg_cap);
+    L.counters = a.take(sizeof(long) * ed::COUNTERS);
+    L.total = a.off;
     return L;
 }
 

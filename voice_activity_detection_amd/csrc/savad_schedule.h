@@ -75,7 +75,7 @@ struct ForwardPlan {
     bool input_p = false;  // the persistent weights-resident input stage
     int KSC = 0;           // ... its compile-time K-step count (5, or 0 = any)
     int attn = ATTN_NONE;
-    // single launch: bf16 5 / 6 / 7 / 8 (launch_packed_forward_bf16), fp32s VARIANT_LATENCY / VARIANT_WAVE_PER_BLOCK; 0 otherwise
+    // single launch: bf16 5 / 6 / 7 / 8 (savad.hip: launch_single), fp32s VARIANT_LATENCY / VARIANT_WAVE_PER_BLOCK; 0 otherwise
     int variant = 0;
     bool fold_v = false;  // fp32s: the launches read the Q/K/V images with the out-projection folded into V
     size_t rows = 0, rows_pad = 0;      // fp32: B * T and whole 128-row tiles
@@ -133,7 +133,7 @@ inline int choose_splits(const Knobs& m, int B, int T) {
 // T <= 32 with bf16 operands: the whole forward in one launch (savad_packed_bf16.h); a wave per packed block, NW blocks per
 // workgroup.
 inline bool single_bf16_applies(const Knobs& m, int T) {
-    // row_mode 0 (automatic) and 4: picked by the number of blocks; 5 - 7: a fixed variant (launch_packed_forward_bf16; tuning
+    // row_mode 0 (automatic) and 4: picked by the number of blocks; 5 - 7: a fixed variant (launch_single; tuning
     // knobs at T <= 32, where the persistent attention kernel that 5 selects for long sequences does not exist); 1 - 3 keep
     // the per-layer launches (the cross-check of the tests)
     return T <= 32 && m.num_layers <= BF16_MAX_LAYERS && (m.row_mode == 0 || m.row_mode >= 4);
@@ -151,7 +151,7 @@ inline int single_bf16_variant(const Knobs& m, long nblk) {
 // wave-per-block kernel (four blocks per workgroup share the weight stream through the LDS ring; a block's chain is 7 320 bf16 MFMAs)
 // beyond.  (Until the latency variant existed, short clips ran the exact-fp32 kernels of precision 0: SAVAD_F32S_PACKED_MIN_BLOCKS.)
 inline bool single_f32s_applies(const Knobs& m, int B, int T) {
-    // row_mode 0 (automatic) and 4: the single launch in the variant the number of blocks suggests (launch_packed_forward_f32s);
+    // row_mode 0 (automatic) and 4: the single launch in the variant the number of blocks suggests (launch_single);
     // 5 - 7: the wave-per-block variant, 8: the latency variant (one block per workgroup); 1 - 3 keep the per-layer launches
     // (the cross-check of the tests).  SAVAD_F32S_PACKED_MIN_BLOCKS > 0 (experiment builds): exact-fp32 kernels below that many blocks
     if (T > 32 || m.num_layers > F32S_MAX_LAYERS) return false;
@@ -365,7 +365,7 @@ inline void plan_f32s(ForwardPlan& p, const Knobs& m, int B, int T, long xbs_in)
         p.variant = single_f32s_variant(m, p.nblk);
     } else {
         p.form = FUSED;
-        // T > 32: V is projected with Wo Wv' (prepare_frags3), so that P V already is the out-projected context -- the fused launch's row
+        // T > 32: V is projected with Wo Wv' (prepare_frags), so that P V already is the out-projected context -- the fused launch's row
         // chain has no out-projection.  The T <= 32 form of the launch keeps the plain images and its out-projection.
         p.fold_v = T > 32;
     }
