@@ -264,6 +264,27 @@ def test_predict_audio_host_defaults_are_unchanged(torch_cuda, model):
     assert torch.equal(got, want)
 
 
+@pytest.mark.parametrize("dtype", [np.int16, np.float32])
+@pytest.mark.parametrize("pinned", [False, True])
+def test_predict_audio_host_16k_mono_exactly(torch_cuda, model, dtype, pinned):
+    """16 kHz mono, int16 (converted by the one-channel average) and float32 (the upload buffer is the signal), pageable and pinned, in
+    several chunks and in one: predict_audio_device's probs and mean bit for bit under fp32 (every launch is the same single-launch
+    kernel)"""
+    from voice_activity_detection_amd import VADFromScratchPredictor
+
+    torch = torch_cuda
+    n = 16000 * 3 + 77
+    raw = _raw_case(16000, 1, dtype, seconds=n / 16000)
+    assert raw.shape == (n,) and raw.dtype == dtype
+    pred = VADFromScratchPredictor(model, "cuda")
+    want, want_mean = pred.predict_audio_device(raw.astype(np.float32) / 32768.0 if dtype == np.int16 else raw)
+    assert want.shape == (301, 7)
+    src = torch.from_numpy(raw).pin_memory() if pinned else raw
+    for per in (100, 65536):
+        got, got_mean = pred.predict_audio_host(src, frames_per_chunk=per)
+        assert torch.equal(got, want) and torch.equal(got_mean, want_mean), (per, float((got - want).abs().max()))
+
+
 def _write_wav(path, pcm, channels, rate):
     with wave.open(str(path), "wb") as w:
         w.setnchannels(channels)

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from .data_models import Activity, VoiceActivity, merge_voice_activities
+from .host_feed import HostFeed, host_source
 from .model import SelfAttentiveVAD
 from .postprocessing import (convert_frames_to_samples, convert_samples_to_segments, optimal_split_voice_activity,
                              trim_voice_activity)
@@ -35,6 +36,22 @@ def window_offsets(half: int, jump: int) -> np.ndarray:
     if w < 0:
         _lib.check(w)
     return np.array(buf[:w], dtype=np.int64)
+
+
+def _require_hip(device: torch.device):
+    if device.type != "cuda":
+        raise _lib.SavadError("the MI355X predictor needs a HIP device (no CPU fallback)")
+
+
+def _indexed(device: torch.device) -> torch.device:
+    """`device` with its index spelled out ("cuda" = the current one)"""
+    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _require_shipped_front_end(self, what: str):
+    """(a method of both predictors; `_not_shipped` is the class's message)"""
+    if not self.front_end.is_shipped:
+        raise NotImplementedError(self._not_shipped.format(what=what, front_end=self.front_end))
 
 
 @dataclass
@@ -329,8 +346,7 @@ class VADFromScratchPredictor:
     def predict_probabilities_device(self, feature):
         """feature [N, F] -> (probs [N, W], mean [N]) on the device: window gather (a13), forward, boosted prediction (a14)
         in one library call (savad_predict_probabilities)."""
-        if self.device.type != "cuda":
-            raise _lib.SavadError("the MI355X predictor needs a HIP device (no CPU fallback)")
+        _require_hip(self.device)
         feat = torch.as_tensor(feature, dtype=torch.float32).to(self.device)
         if feat.dim() != 2:
             raise ValueError("feature must be [N, F]")
@@ -345,11 +361,9 @@ class VADFromScratchPredictor:
             return log_mel(audio, self.device)
         return self.front_end.extract(audio, self.device)
 
-    def _require_shipped_front_end(self, what: str):
-        if not self.front_end.is_shipped:
-            raise NotImplementedError(f"{what} runs the shipped log-mel front-end only (its spans follow the 160-sample hop, and "
-                                      f"MFCC's clamp and the temporal differences are not local): {self.front_end} is not; use "
-                                      "predict_audio_device")
+    _require_shipped_front_end = _require_shipped_front_end
+    _not_shipped = ("{what} runs the shipped log-mel front-end only (its spans follow the 160-sample hop, and MFCC's clamp and the "
+                    "temporal differences are not local): {front_end} is not; use predict_audio_device")
 
     @torch.no_grad()
     def predict_audio_device(self, audio):
@@ -360,14 +374,13 @@ class VADFromScratchPredictor:
         the same length and knobs: copy them if they must outlive it."""
         from .features import SAMPLE_RATE
 
-        if self.device.type != "cuda":
-            raise _lib.SavadError("the MI355X predictor needs a HIP device (no CPU fallback)")
+        _require_hip(self.device)
         n = int(audio.shape[0]) if hasattr(audio, "shape") and len(audio.shape) == 1 else -1
         if not self.graph or n < 1 or n > self.graph_max_seconds * SAMPLE_RATE or self.model.training:
             self.graph_stats["eager"] += 1
             return self.predict_probabilities_device(self.features(audio))
         model = self.model
-        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        dev = _indexed(self.device)
         with torch.cuda.device(dev):
             model._prepare_call(dev)   # weights pushed, knobs set: the walk over the parameters' versions costs ~8 us
             key = (n, dev.index, model._pushed_knobs, self.context_window_half_frames, self.context_window_jump_frames, self.chunk_size,
@@ -408,130 +421,66 @@ class VADFromScratchPredictor:
             plan.append((f0, f1, max(0, f0 - 2 * half) // G * G, min(N, f1 + 2 * half)))
         return plan
 
+    @staticmethod
+    def host_upload_plan(n_in: int, rate: int, half: int, W: int, frames_per_chunk: int):
+        """(n, [(f0, f1, g0, g1, first, count, have)]) for a recording of n_in frames at `rate` Hz, n samples at 16 kHz: host_chunk_plan
+        of its N = 1 + n // 160 frames, the 16 kHz samples [first, first + count) a chunk's feature frames read (span_samples), and the
+        raw frames [0, have) the 16 kHz signal up to the chunk's last sample is interpolated from (resample_span_samples; at 16 kHz
+        that signal itself).  Host-side arithmetic only."""
+        from .features import SAMPLE_RATE, resample_length, resample_span_samples, span_samples
+
+        n = resample_length(n_in, rate)
+        if n < 1:
+            raise ValueError("audio must be a non-empty array")
+        plan = []
+        for f0, f1, g0, g1 in VADFromScratchPredictor.host_chunk_plan(1 + n // 160, half, W, frames_per_chunk):
+            first, count = span_samples(n, g0, g1 - g0)
+            have = first + count if rate == SAMPLE_RATE else sum(resample_span_samples(n_in, rate, 0, first + count))
+            plan.append((f0, f1, g0, g1, first, count, have))
+        return n, plan
+
     @torch.no_grad()
     def predict_audio_host(self, audio, frames_per_chunk: int = 65536, sample_rate: int = 16000, channels: int = 1):
         """The reference's mode END TO END from host memory: `audio` = the whole recording on the host, 16-bit PCM
         (uploaded as it is, converted on the device) or float32, numpy array or CPU tensor (pinned: asynchronous uploads) ->
         (probs [N, W], mean [N]) on the device.  Output frames are produced in chunks of `frames_per_chunk`; chunk c needs the feature
         frames within 2 x half of its own (every window that reaches one of its frames, vad/predictor.py:186-258), whose samples are
-        uploaded on a copy stream while chunk c - 1 runs.  A chunk's first window keeps its place modulo the packed block (a multiple
-        of 32 // W windows), so the results are predict_audio_device's bits.
+        uploaded on a copy stream while chunk c - 1 runs (host_feed.HostFeed).  A chunk's first window keeps its place modulo the
+        packed block (a multiple of 32 // W windows), so the results are predict_audio_device's bits.
         `sample_rate`, `channels`: the recording as a file holds it -- `audio` is then the interleaved 1-D sample stream at that rate
         (features.read_audio), and a chunk uploads the raw frames its 16 kHz samples are interpolated from; on the device they are
         averaged over the channels (downmix_device) and resampled (resample_span_device) into a 16 kHz signal that grows chunk by
-        chunk: the bits of predict_audio_device(resample_to_16k_device(downmix_device(audio))).  With the defaults (16 kHz mono) the
-        code path is the one above, unchanged."""
-        from .features import log_mel_span, pcm16_to_f32, span_samples
+        chunk: the bits of predict_audio_device(resample_to_16k_device(downmix_device(audio))).  A stage the recording does not need
+        is skipped: the average for float32 mono (16-bit mono is converted by it: the average of one channel), the resampling at
+        16 kHz."""
+        from .features import SAMPLE_RATE, downmix_device, log_mel_span, resample_prepare, resample_span_device, resample_span_samples
 
-        if self.device.type != "cuda":
-            raise _lib.SavadError("the MI355X predictor needs a HIP device (no CPU fallback)")
+        _require_hip(self.device)
         self._require_shipped_front_end("predict_audio_host")
-        src = StreamingPredictor._host_source(audio)
-        if int(sample_rate) != 16000 or int(channels) != 1:
-            return self._predict_raw_host(src, int(frames_per_chunk), int(sample_rate), int(channels))
-        n = int(src.shape[0])
-        N = 1 + n // 160
-        half, jump, Wn = self.context_window_half_frames, self.context_window_jump_frames, self.context_window_frames
-        plan = [(f0, f1, g0, g1) + tuple(span_samples(n, g0, g1 - g0))
-                for f0, f1, g0, g1 in self.host_chunk_plan(N, half, Wn, frames_per_chunk)]
-        self.model.eval()
-        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
-        with torch.cuda.device(dev):
-            cur = torch.cuda.current_stream(dev)
-            if getattr(self, "_copy_stream", None) is None or self._copy_stream.device != dev:
-                self._copy_stream = torch.cuda.Stream(dev)
-            cs = self._copy_stream
-            dev_audio = torch.empty(n, dtype=src.dtype, device=dev)
-            dev_audio.record_stream(cs)
-            cs.wait_stream(cur)
-            probs = torch.empty((N, Wn), dtype=torch.float32, device=dev)
-            mean = torch.empty((N,), dtype=torch.float32, device=dev)
-            uploaded = 0
-
-            def upload(c):
-                nonlocal uploaded
-                end = plan[c][4] + plan[c][5]
-                ev = torch.cuda.Event()
-                with torch.cuda.stream(cs):
-                    if end > uploaded:
-                        dev_audio[uploaded:end].copy_(src[uploaded:end], non_blocking=True)
-                        uploaded = end
-                    ev.record(cs)
-                return ev
-
-            ev = upload(0)
-            for c, (f0, f1, g0, g1, first, count) in enumerate(plan):
-                nxt = upload(c + 1) if c + 1 < len(plan) else None
-                cur.wait_event(ev)
-                sl = dev_audio[first:first + count]
-                if sl.dtype == torch.int16:
-                    sl = pcm16_to_f32(sl)
-                feat = log_mel_span(sl, first, n, g0, g1 - g0)
-                p, mu = self.model.predict_windows(feat, half, jump, self.chunk_size)
-                probs[f0:f1].copy_(p[f0 - g0:f1 - g0])
-                mean[f0:f1].copy_(mu[f0 - g0:f1 - g0])
-                ev = nxt
-        return probs, mean
-
-    def _predict_raw_host(self, src, frames_per_chunk: int, rate: int, channels: int):
-        """predict_audio_host for a recording that is not 16 kHz mono (see there)"""
-        from .features import (SAMPLE_RATE, downmix_device, log_mel_span, resample_length, resample_prepare, resample_span_device,
-                               resample_span_samples, span_samples)
-
+        src = host_source(audio)
+        rate, channels = int(sample_rate), int(channels)
         if channels < 1 or src.numel() % channels:
             raise ValueError(f"{src.numel()} samples are not whole frames of {channels} channels")
         n_in = src.numel() // channels
-        n = resample_length(n_in, rate)            # samples of the 16 kHz signal
-        if n < 1:
-            raise ValueError("audio must be a non-empty array")
-        N = 1 + n // 160
         half, jump, Wn = self.context_window_half_frames, self.context_window_jump_frames, self.context_window_frames
-        plan = [(f0, f1, g0, g1) + tuple(span_samples(n, g0, g1 - g0))
-                for f0, f1, g0, g1 in self.host_chunk_plan(N, half, Wn, frames_per_chunk)]
+        n, plan = self.host_upload_plan(n_in, rate, half, Wn, frames_per_chunk)
+        N = 1 + n // 160
         self.model.eval()
-        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        dev = _indexed(self.device)
         with torch.cuda.device(dev):
             if rate != SAMPLE_RATE:
                 resample_prepare(rate, dev)        # (the table upload synchronises: before the first copy is in flight)
-            cur = torch.cuda.current_stream(dev)
-            if getattr(self, "_copy_stream", None) is None or self._copy_stream.device != dev:
-                self._copy_stream = torch.cuda.Stream(dev)
-            cs = self._copy_stream
-            raw = torch.empty(n_in * channels, dtype=src.dtype, device=dev)
-            raw.record_stream(cs)
-            cs.wait_stream(cur)
+            feed = HostFeed(src, dev, unit=channels, stream_owner=self)
             plain = channels == 1 and src.dtype == torch.float32          # the raw buffer already is the mono signal
-            mono = raw if plain else torch.empty(n_in, dtype=torch.float32, device=dev)
+            mono = feed.buffer if plain else torch.empty(n_in, dtype=torch.float32, device=dev)
             audio16 = mono if rate == SAMPLE_RATE else torch.empty(n, dtype=torch.float32, device=dev)
             probs = torch.empty((N, Wn), dtype=torch.float32, device=dev)
             mean = torch.empty((N,), dtype=torch.float32, device=dev)
-            uploaded = mixed = done16 = 0          # frames on the device / averaged; 16 kHz samples produced
-
-            def frames_for(c):                     # raw frames [0, end) the 16 kHz samples of chunks 0 .. c are interpolated from
-                end16 = plan[c][4] + plan[c][5]
-                if rate == SAMPLE_RATE:
-                    return end16
-                first, count = resample_span_samples(n_in, rate, 0, end16)
-                return first + count
-
-            def upload(c):
-                nonlocal uploaded
-                end = frames_for(c)
-                ev = torch.cuda.Event()
-                with torch.cuda.stream(cs):
-                    if end > uploaded:
-                        raw[uploaded * channels:end * channels].copy_(src[uploaded * channels:end * channels], non_blocking=True)
-                        uploaded = end
-                    ev.record(cs)
-                return ev
-
-            ev = upload(0)
-            for c, (f0, f1, g0, g1, first, count) in enumerate(plan):
-                nxt = upload(c + 1) if c + 1 < len(plan) else None
-                cur.wait_event(ev)
-                have = frames_for(c)
+            mixed = done16 = 0                     # frames averaged; 16 kHz samples produced
+            for c in feed.chunks([(0, p[6]) for p in plan]):   # (both stages are cumulative: a chunk needs the recording up to `have`)
+                f0, f1, g0, g1, first, count, have = plan[c]
                 if not plain and have > mixed:
-                    downmix_device(raw[mixed * channels:have * channels], channels, out=mono[mixed:have])
+                    downmix_device(feed.buffer[mixed * channels:have * channels], channels, out=mono[mixed:have])
                     mixed = have
                 end16 = first + count
                 if rate != SAMPLE_RATE and end16 > done16:
@@ -542,7 +491,6 @@ class VADFromScratchPredictor:
                 p, mu = self.model.predict_windows(feat, half, jump, self.chunk_size)
                 probs[f0:f1].copy_(p[f0 - g0:f1 - g0])
                 mean[f0:f1].copy_(mu[f0 - g0:f1 - g0])
-                ev = nxt
         return probs, mean
 
     def _capture(self, key, n: int, dev: torch.device) -> dict:
@@ -637,28 +585,37 @@ class StreamingPredictor:
     def predict_device(self, feature):
         from .distributed import sharded_rows
 
-        lib = _lib.load()
         feat = torch.as_tensor(feature, dtype=torch.float32).to(self.device).contiguous()
         N, F = feat.shape
-        T, hop = self.T, self.hop
-        W = lib.savad_stream_window_count(N, T, hop)
-        if W < 0:
-            _lib.check(W)
+        W = self._window_count(N, self.T, self.hop)
         self.model.eval()
         with torch.cuda.device(self.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-            if self._pipe is None or self._pipe.model is not self.model or self._pipe.depth != max(self.in_flight, 1):
-                from .pipeline import PipelinedVAD
-                self._pipe = PipelinedVAD(self.model, depth=max(self.in_flight, 1))
+            self._ensure_pipe()
 
             def windows_logp(lo, hi):  # this rank's contiguous span of windows -> [hi - lo, T, 2] log-probs
                 return self._windows_logp(feat, 0, N, lo, hi, stream)
 
-            logp = sharded_rows(W, windows_logp, (T, 2), torch.float32, self.device).contiguous()
-            probs = torch.empty((N,), dtype=torch.float32, device=self.device)
-            _lib.check(lib.savad_overlap_merge(ctypes.c_void_p(logp.data_ptr()), W, N, T, hop,
-                                               ctypes.c_void_p(probs.data_ptr()), stream))
+            logp = sharded_rows(W, windows_logp, (self.T, 2), torch.float32, self.device).contiguous()
+            return self._merge(logp, W, N)
+
+    @staticmethod
+    def _window_count(N: int, T: int, hop: int) -> int:
+        W = _lib.load().savad_stream_window_count(N, T, hop)
+        if W < 0:
+            _lib.check(W)
+        return W
+
+    def _ensure_pipe(self):
+        if self._pipe is None or self._pipe.model is not self.model or self._pipe.depth != max(self.in_flight, 1):
+            from .pipeline import PipelinedVAD
+            self._pipe = PipelinedVAD(self.model, depth=max(self.in_flight, 1))
+
+    def _merge(self, logp, W: int, N: int):
+        """the windows' log-probs [W, T, 2] -> per-frame probabilities [N] (savad_overlap_merge on the current stream)"""
+        probs = torch.empty((N,), dtype=torch.float32, device=logp.device)
+        _lib.check(_lib.load().savad_overlap_merge(ctypes.c_void_p(logp.data_ptr()), W, N, self.T, self.hop, ctypes.c_void_p(probs.data_ptr()),
+                                                   ctypes.c_void_p(torch.cuda.current_stream(logp.device).cuda_stream)))
         return probs
 
     def _windows_logp(self, feat, frame0, n_total, lo, hi, stream, out=None, join=True):
@@ -723,9 +680,7 @@ class StreamingPredictor:
         self.model.eval()
         with torch.cuda.device(self.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            if self._pipe is None or self._pipe.model is not self.model or self._pipe.depth != max(self.in_flight, 1):
-                from .pipeline import PipelinedVAD
-                self._pipe = PipelinedVAD(self.model, depth=max(self.in_flight, 1))
+            self._ensure_pipe()
             sl = audio[first:first + count]
             if not isinstance(sl, torch.Tensor):
                 sl = torch.from_numpy(np.ascontiguousarray(sl) if sl.dtype == np.int16 else np.ascontiguousarray(sl, dtype=np.float32))
@@ -749,27 +704,37 @@ class StreamingPredictor:
         from .distributed import all_gather_rows
 
         self._require_shipped_front_end("predict_audio_device")
-        lib = _lib.load()
-        n = int(audio.shape[0])
-        N = 1 + n // 160
+        N = 1 + int(audio.shape[0]) // 160
         world, rank = (dist.get_world_size(), dist.get_rank()) if dist.is_initialized() else (1, 0)
         local = self.audio_span_logp(audio, rank, world)
-        W = lib.savad_stream_window_count(N, self.T, self.hop)
+        W = self._window_count(N, self.T, self.hop)
         with torch.cuda.device(self.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            logp = (all_gather_rows(local, W) if world > 1 else local).contiguous()
-            probs = torch.empty((N,), dtype=torch.float32, device=self.device)
-            _lib.check(lib.savad_overlap_merge(ctypes.c_void_p(logp.data_ptr()), W, N, self.T, self.hop,
-                                               ctypes.c_void_p(probs.data_ptr()), stream))
-        return probs
+            return self._merge((all_gather_rows(local, W) if world > 1 else local).contiguous(), W, N)
+
+    _host_source = staticmethod(host_source)   # (the name scripts and callers knew it by)
 
     @staticmethod
-    def _host_source(audio):
-        """host audio (numpy array or CPU tensor, int16 PCM or float32) as a CPU tensor without a copy"""
-        src = audio if isinstance(audio, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(audio))
-        if src.device.type != "cpu" or src.dim() != 1 or src.numel() < 1 or src.dtype not in (torch.int16, torch.float32) or not src.is_contiguous():
-            raise ValueError("audio must be a non-empty contiguous 1-D int16 or float32 array on the host")
-        return src
+    def host_span_plan(n_samples: int, T: int, hop: int, per: int, ramp: bool):
+        """[(lo, hi, f0, f1, first, count)], in the order predict_audio_host takes them: windows [lo, hi) of an n_samples-long
+        recording, `per` to a span, the feature frames [f0, f1) they cover and the samples [first, first + count) those read
+        (span_samples).  Without `ramp` a short last span goes first (the upload nothing can hide is the smallest one); with it
+        the spans start at 32, 64, 128 ... windows, up to `per`.  Host-side arithmetic only."""
+        from .features import span_samples
+
+        N = 1 + n_samples // 160
+        W = StreamingPredictor._window_count(N, T, hop)
+        bounds, lo, step = [], 0, 32
+        while ramp and lo < W and step < per:
+            bounds.append((lo, min(W, lo + step)))
+            lo, step = lo + step, 2 * step
+        bounds += [(b, min(W, b + per)) for b in range(lo, W, per)]
+        if not ramp and len(bounds) > 1 and bounds[-1][1] - bounds[-1][0] < per:
+            bounds.insert(0, bounds.pop())
+        plan = []
+        for lo, hi in bounds:
+            f0, f1 = hop * lo, min(N, hop * (hi - 1) + T)
+            plan.append((lo, hi, f0, f1) + tuple(span_samples(n_samples, f0, f1 - f0)))
+        return plan
 
     @torch.no_grad()
     def predict_audio_host(self, audio, windows_per_chunk: Optional[int] = None, ramp: bool = False):
@@ -784,84 +749,34 @@ class StreamingPredictor:
         host_pipeline_parts.py), but the batches are no longer predict_device's: the same bits only where a window's result does
         not depend on its batch (fp32 / fp32s: measured equal; bf16 needs model.batch_invariant).  Returns the per-frame
         probabilities [N] on the device."""
-        from .features import log_mel_span, pcm16_to_f32, span_samples
+        from .features import log_mel_span, pcm16_to_f32
 
         self._require_shipped_front_end("predict_audio_host")
-        lib = _lib.load()
-        src = self._host_source(audio)
+        src = host_source(audio)
         n = int(src.shape[0])
         N = 1 + n // 160
-        T, hop = self.T, self.hop
-        W = lib.savad_stream_window_count(N, T, hop)
-        if W < 0:
-            _lib.check(W)
-        per = int(windows_per_chunk or self.max_batch)
-        bounds, lo = [], 0
-        if ramp:   # spans of 32, 64, 128 ... windows up to `per`: the first upload -- the one nothing hides -- is an eighth of a full span's
-            step = 32
-            while lo < W and step < per:
-                bounds.append((lo, min(W, lo + step)))
-                lo, step = lo + step, 2 * step
-        bounds += [(b, min(W, b + per)) for b in range(lo, W, per)]
-        plan = []
-        for lo, hi in bounds:
-            f0, f1 = hop * lo, min(N, hop * (hi - 1) + T)
-            first, count = span_samples(n, f0, f1 - f0)
-            plan.append((lo, hi, f0, f1, first, count))
-        if not ramp and len(plan) > 1 and plan[-1][1] - plan[-1][0] < per:
-            plan.insert(0, plan.pop())
+        W = self._window_count(N, self.T, self.hop)
+        plan = self.host_span_plan(n, self.T, self.hop, int(windows_per_chunk or self.max_batch), ramp)
         self.model.eval()
-        dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+        dev = _indexed(self.device)
         with torch.cuda.device(dev):
-            cur = torch.cuda.current_stream(dev)
-            stream = ctypes.c_void_p(cur.cuda_stream)
-            if self._pipe is None or self._pipe.model is not self.model or self._pipe.depth != max(self.in_flight, 1):
-                from .pipeline import PipelinedVAD
-                self._pipe = PipelinedVAD(self.model, depth=max(self.in_flight, 1))
-            if getattr(self, "_copy_stream", None) is None or self._copy_stream.device != dev:
-                self._copy_stream = torch.cuda.Stream(dev)
-            cs = self._copy_stream
-            dev_audio = torch.empty(n, dtype=src.dtype, device=dev)
-            dev_audio.record_stream(cs)
-            cs.wait_stream(cur)
-            logp = torch.empty((W, T, 2), dtype=torch.float32, device=dev)
-            uploaded, tail_from = 0, n   # on the device so far: samples [0, uploaded) and [tail_from, n)
-
-            def upload(c):   # everything span c reads that is not on the device yet
-                nonlocal uploaded, tail_from
-                a, b = plan[c][4], plan[c][4] + plan[c][5]
-                ev = torch.cuda.Event()
-                with torch.cuda.stream(cs):
-                    if uploaded == 0 and a > 0 and c == 0:   # the short last span, taken first
-                        dev_audio[a:b].copy_(src[a:b], non_blocking=True)
-                        tail_from = a
-                    else:
-                        a, b = max(a, uploaded), min(b, tail_from)
-                        if b > a:
-                            dev_audio[a:b].copy_(src[a:b], non_blocking=True)
-                        uploaded = max(uploaded, b)
-                    ev.record(cs)
-                return ev
-
-            ev = upload(0)
-            for c, (lo, hi, f0, f1, first, count) in enumerate(plan):
-                nxt = upload(c + 1) if c + 1 < len(plan) else None   # (pageable memory: this call stages synchronously -- while span c - 1 still runs)
-                cur.wait_event(ev)
-                sl = dev_audio[first:first + count]
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            self._ensure_pipe()
+            feed = HostFeed(src, dev, stream_owner=self)
+            logp = torch.empty((W, self.T, 2), dtype=torch.float32, device=dev)
+            for c in feed.chunks([(first, first + count) for *_, first, count in plan]):
+                lo, hi, f0, f1, first, count = plan[c]
+                sl = feed.buffer[first:first + count]
                 if sl.dtype == torch.int16:
                     sl = pcm16_to_f32(sl)
                 feat = log_mel_span(sl, first, n, f0, f1 - f0)
                 self._windows_logp(feat, f0, N, lo, hi, stream, out=logp[lo:hi], join=False)   # (spans overlap on the pipeline's streams)
-                ev = nxt
             self._pipe.join()
-            probs = torch.empty((N,), dtype=torch.float32, device=dev)
-            _lib.check(lib.savad_overlap_merge(ctypes.c_void_p(logp.data_ptr()), W, N, T, hop, ctypes.c_void_p(probs.data_ptr()), stream))
-        return probs
+            return self._merge(logp, W, N)
 
-    def _require_shipped_front_end(self, what: str):
-        if not self.front_end.is_shipped:
-            raise NotImplementedError(f"StreamingPredictor.{what} runs the shipped log-mel front-end only (spans at its 160-sample hop, "
-                                      f"features per span): {self.front_end} is not; extract the features whole and call predict_device")
+    _require_shipped_front_end = _require_shipped_front_end
+    _not_shipped = ("StreamingPredictor.{what} runs the shipped log-mel front-end only (spans at its 160-sample hop, features per span): "
+                    "{front_end} is not; extract the features whole and call predict_device")
 
     def predict(self, feature) -> np.ndarray:
         return self.predict_device(feature).cpu().numpy()
