@@ -24,9 +24,9 @@ import torch
 D = 128
 DFF = 4 * D
 TILE = 32                        # keys per attention tile (csrc/savad_kernels_bf16.h:729-743: one MFMA tile of keys)
-RESCALE_LOG2 = 16.0              # csrc/savad_kernels.h:165
-NEG_BIG = -1.0e30                # csrc/savad_kernels.h:39
-LN_EPS = 1e-5                    # csrc/savad_kernels.h:38
+RESCALE_LOG2 = 16.0              # csrc/savad_device.h
+NEG_BIG = -1.0e30                # csrc/savad_device.h
+LN_EPS = 1e-5                    # csrc/savad_device.h
 F16_MAX = 65504.0
 
 # Max-abs log-prob gaps allowed between a bf16 kernel and this model (tests/test_gpu_bf16_model.py): 2x what
@@ -103,7 +103,7 @@ def positional_encoding(T: int) -> np.ndarray:
 
 
 def _fold(W, b, gamma, beta):
-    """fold_ln_kernel (csrc/savad_kernels.h:1592-1610): W' = fp32(W * gamma) (:1600), b' = fp32(b + sum W beta in double) (:1609)"""
+    """fold_ln_kernel (csrc/savad_aux_kernels.h): W' = fp32(W * gamma), b' = fp32(b + sum W beta in double)"""
     Wf = (W.astype(np.float32) * gamma.astype(np.float32)[None, :]).astype(np.float32)
     bf = (b.astype(np.float64) + W.astype(np.float64) @ beta.astype(np.float64)).astype(np.float32)
     return Wf, bf
@@ -138,7 +138,7 @@ def _prepare(state: dict, A: _Arith):
 
 
 def _layernorm(h: torch.Tensor) -> torch.Tensor:
-    """layernorm_regs (csrc/savad_kernels.h:1235-1256): fp32 statistics, biased variance, no affine part (folded)"""
+    """layernorm_regs (csrc/savad_device.h): fp32 statistics, biased variance, no affine part (folded)"""
     mean = h.mean(-1, keepdim=True)
     d = h - mean
     return d / torch.sqrt((d * d).mean(-1, keepdim=True) + LN_EPS)

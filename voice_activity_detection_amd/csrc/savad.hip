@@ -3,7 +3,9 @@
 // kernel families (generic, fp32, bf16, fp32s), each as a single launch for the whole forward (T <= 32), or as
 //   input_qkv -> [attention(l) -> row(l)] x L      (row(L-1) ends in classifier + log-softmax)
 // with attention and row chain of a layer in one launch (fused) or in two.
+// the order of the kernel headers is the order of the kernels in the code object
 #include "savad_kernels.h"
+#include "savad_aux_kernels.h"
 #include "savad_kernels_bf16.h"
 #include "savad_attn_pw_bf16.h"
 #include "savad_packed_bf16.h"
@@ -97,15 +99,6 @@ struct savad_model {
 namespace {
 
 using namespace savad;
-
-// the kernel headers' sizes as savad_schedule.h and savad_weights.h restate them
-static_assert(sched::D == D && sched::TILE == TILE && sched::F32_MAX_LAYERS == PACKED_MAX_LAYERS, "savad_schedule.h: savad_kernels.h sizes");
-static_assert(sched::BF_BLK_BYTES == bf::BLK_BYTES && sched::BF_HBLK_FLOATS == bf::HBLK_FLOATS && sched::BF_HRES_BYTES == sizeof(bf::hres_t) &&
-                  sched::BF16_MAX_LAYERS == bf::PACKED_BF16_MAX_LAYERS && sched::PW_GRID == bf::PW_GRID, "savad_schedule.h: bf16 sizes");
-static_assert(sched::FS_BLK3_BYTES == fs::BLK3_BYTES && sched::F32S_MAX_LAYERS == fs::PACKED_F32S_MAX_LAYERS && sched::FS_HBLK_BYTES == fs::HBLK_BYTES,
-              "savad_schedule.h: fp32s sizes");
-static_assert(sched::GEN_SCORE_CAP == gen::SCORE_CAP, "savad_schedule.h: savad_generic.h sizes");
-static_assert(weights::D == D && weights::DFF == DFF && weights::LBIAS == LBIAS && weights::FRAG_LAYER == FRAG_LAYER, "savad_weights.h: savad_kernels.h sizes");
 
 // blocks of 256 threads for `work` elements, at most `cap` (the kernels stride over the rest)
 int grid_for(long work, int cap = 4096) { return (int)((work + 255) / 256 < cap ? (work + 255) / 256 : cap); }

@@ -21,7 +21,7 @@
 
 #include <vector>
 
-#include "savad_kernels.h"
+#include "savad_device.h"
 
 namespace savad {
 namespace fe {
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(256) void fe_gemm_kernel(FeGemm g) {
         float* C = g.C + m * g.ldc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int n = n0 + wn * 32 + 8 * (r >> 2) + 4 * kh + (r & 3);
+            const int n = n0 + wn * 32 + acc_row(r, kh);
             if (n >= g.N) continue;
             float v = acc[r];
             if constexpr (EPI == EPI_LOG) v = logf(v + 1e-6f);

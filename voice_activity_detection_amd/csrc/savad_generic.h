@@ -8,6 +8,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "savad_dims.h"  // gen::SCORE_CAP
+
 namespace savad {
 namespace gen {
 
@@ -173,7 +175,6 @@ inline void build_pe_host(float* pe, int T, int Dm) {
 }
 
 // workspace (floats): h | n | q | k | v | ctx (rows x d_model each), ff (rows x 4 d_model), one score tile
-constexpr size_t SCORE_CAP = (size_t)32 << 20;   // floats: 128 MiB of scores per attention pass
 struct Plan {
     size_t h, n, q, k, v, ctx, ff, scores, total;  // float offsets
     int cb, tq;                                    // sequences and query rows per score tile

@@ -1,4 +1,5 @@
-// savad_kernels.h -- gfx950 (MI355X / CDNA4) device code of the self-attentive-VAD forward pass.
+// savad_kernels.h -- gfx950 (MI355X / CDNA4) device code of the self-attentive-VAD forward pass: the fp32 kernel family.
+// (The primitives every family shares are in savad_device.h, the weight-preparation and predictor kernels in savad_aux_kernels.h.)
 //
 // Everything GEMM-shaped runs on the exact-fp32 matrix core instruction
 // v_mfma_f32_32x32x2_f32 (64 cycles, 4096 FLOP; 157.3 TF chip peak) in the TRANSPOSED form
@@ -18,93 +19,14 @@
 // No transposes, no LDS staging of operands: weights / K / V stream from L2 straight into the
 // A operand, activations stay in registers between chained GEMMs.
 //
-// Reference being restated (paths relative to /root/reference):
+// Reference being restated (paths relative to the reference project):
 //   vad/models/self_attention.py:23-28, vad/modeling/transformer.py:24-61,227-238,258-363,366-382,385-414.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "savad_device.h"
 
 namespace savad {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int D = 128;        // d_model (= d_head, n_heads = 1: vad/models/self_attention.py:18)
-constexpr int DFF = 4 * D;    // vad/models/self_attention.py:10
-constexpr int TILE = 32;      // data rows per MFMA tile / per workgroup of the row kernels
-constexpr int XLD = D + 4;    // LDS row stride (floats) of the 32x128 exchange buffer: conflict-free b128
 constexpr int PLD = 32 + 4;   // LDS row stride of one 32x32 split-K partial block
-constexpr float LN_EPS = 1e-5f;
-constexpr float NEG_BIG = -1.0e30f;
-
-#define SAVAD_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-// A data row lives in lanes m and m+32: one v_permlane32_swap hands every lane both halves' values
-// (no LDS round trip as with ds_bpermute), in the same order on both lanes (bit-identical results).
-// NB: copy the two results into scalars before __builtin_bit_cast -- bit_cast applied directly to a
-// vector-element lvalue (r[1]) reads element 0 (clang quirk; it cost a parity failure to find).
-__device__ __forceinline__ void both_halves(float v, float& lo, float& hi) {
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);  // r[0] = low half's value, r[1] = high half's
-    const unsigned a = r[0], b = r[1];
-    lo = __builtin_bit_cast(float, a);
-    hi = __builtin_bit_cast(float, b);
-}
-__device__ __forceinline__ float half_sum(float v) {
-    float lo, hi;
-    both_halves(v, lo, hi);
-    return lo + hi;
-}
-__device__ __forceinline__ float half_max(float v) {
-    float lo, hi;
-    both_halves(v, lo, hi);
-    return fmaxf(lo, hi);
-}
-
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 z;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) z[i] = 0.0f;
-    return z;
-}
-
-// bias for the wave's feature block in row layout: b[n0 + 8g + 4h + s]
-__device__ __forceinline__ void add_bias(f32x16& acc, const float* __restrict__ b, int h) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 b4 = ld4(b + 8 * g + 4 * h);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc[4 * g + s] += b4[s];
-    }
-}
-
-// element offset of flat row r = b T + t of the features: sequences xbs elements apart (xbs = T F: the contiguous [B,T,F]
-// tensor; smaller: overlapping windows read in place out of a feature matrix -- the streaming mode, savad_forward_strided)
-__device__ __forceinline__ size_t x_row_offset(size_t r, int T, int F, long xbs) {
-    return xbs == (long)T * F ? r * (size_t)F : (r / (size_t)T) * (size_t)xbs + (r % (size_t)T) * (size_t)F;
-}
-
-// row-layout 32-feature block <-> memory row (global or LDS): 4 x 16-byte pieces at 8g + 4h
-__device__ __forceinline__ void store_block(float* rowp /* &X[row][n0] */, const f32x16& v, int h) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        f32x4 t;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) t[s] = v[4 * g + s];
-        st4(rowp + 8 * g + 4 * h, t);
-    }
-}
-__device__ __forceinline__ void add_block(f32x16& v, const float* rowp, int h) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 t = ld4(rowp + 8 * g + 4 * h);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) v[4 * g + s] += t[s];
-    }
-}
 
 // Read full rows back from the LDS exchange buffer and apply LayerNorm WITHOUT the affine part
 // (gamma/beta are folded into the next Linear on the host side of the library, see fold_ln_kernel).
@@ -145,15 +67,6 @@ __device__ __forceinline__ void read_rows_layernorm(const float* xbuf, int m, in
 // kernel combines the splits and divides.
 // ---------------------------------------------------------------------------------------------
 
-// Drain this wave's vector-memory operations (global loads AND the LDS-DMA issued through inline asm).
-// It must be the BUILTIN, not an asm string: the compiler's wait-count pass cannot see into asm, would
-// still believe earlier global loads (e.g. the Q rows read before the key loop) to be pending, and
-// would then guard their first use INSIDE the loop with vmcnt(N) waits -- which the hardware counts
-// against the DMA just issued for the next tile, exposing its full latency on every iteration.
-__device__ __forceinline__ void wait_vmem_all() {
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt / lgkmcnt untouched (gfx9 encoding)
-    asm volatile("" ::: "memory");
-}
 
 // One 32-key tile of the flash loop, K and V tiles supplied by functors (LDS or global).
 // sc in/out: raw scores S^T (already masked) -> probabilities p.
@@ -162,7 +75,7 @@ __device__ __forceinline__ void wait_vmem_all() {
 // relative to the stale reference, p = 2^((s - m_run) c) <= 2^RESCALE_LOG2.  O, l and p stay mutually
 // consistent, so O / l is unchanged (fp32 accumulators: no precision cost), and the 64-register rescale of O
 // plus one exp -- needed on ~3/4 of the tiles with a per-tile reference on random data -- all but disappears.
-constexpr float RESCALE_LOG2 = 16.0f;
+// (RESCALE_LOG2: savad_device.h -- the bf16 and fp32s attention defer their rescale the same way.)
 __device__ __forceinline__ void online_softmax(f32x16& sc, float& m_run, float& l_run, f32x16 (&O)[4], float c) {
     float mx = sc[0];
 #pragma unroll
@@ -220,7 +133,7 @@ __device__ __forceinline__ void packed_attention_tile(f32x16 (&O)[4], float& m_r
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) vv[nb][r] = vp[(8 * (r >> 2) + (r & 3)) * D + 32 * nb];
+        for (int r = 0; r < 16; ++r) vv[nb][r] = vp[acc_row(r, 0) * D + 32 * nb];
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) O[nb] = zero16();
     m_run = NEG_BIG;
@@ -232,7 +145,7 @@ __device__ __forceinline__ void packed_attention_tile(f32x16 (&O)[4], float& m_r
         for (int e = 0; e < 4; ++e) sc = SAVAD_MFMA(kg[G8][e], qg[G8][e], sc);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int jk = 8 * (r >> 2) + 4 * h + (r & 3);
+        const int jk = acc_row(r, h);
         const bool ok = (jk < rowsPB) && (jk / T == tq) && (k0 + jk < (size_t)rows);
         sc[r] = ok ? sc[r] : NEG_BIG;
     }
@@ -329,54 +242,11 @@ __device__ __forceinline__ void pv_tile_lds(f32x16 (&O)[4], const f32x16& sc, co
     for (int nb = 0; nb < 4; ++nb) {
         dma(nb);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) O[nb] = SAVAD_MFMA(vp[(8 * (r >> 2) + (r & 3)) * D + 32 * nb], sc[r], O[nb]);
+        for (int r = 0; r < 16; ++r) O[nb] = SAVAD_MFMA(vp[acc_row(r, 0) * D + 32 * nb], sc[r], O[nb]);
     }
 #endif
 }
 
-// Workgroup -> (sequence, index among the sequence's `per_seq` workgroups) for the attention-type kernels.
-// Workgroups go to the 8 XCDs round-robin by blockIdx (each XCD has its own L2); the linear order (sequence major)
-// is cut into 8 equal chunks, one per XCD, so that a sequence's workgroups -- which all read the same K/V -- share an
-// L2 (a sequence straddles at most two XCDs) AND every XCD gets the same number of workgroups for any batch size.
-// (Binding whole sequences to XCDs, b = 8 j + xcd, left XCDs 0-1 with twice the work at B = 10: 76 us against 47.)
-// Launch 8 * ceil(B * per_seq / 8) workgroups.
-__device__ __forceinline__ bool xcd_balanced_map(int B, int per_seq, int& b, int& rr) {
-    const long W = (long)B * per_seq;
-    const int per_xcd = (int)((W + 7) / 8);
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const long lin = (long)xcd * per_xcd + slot;
-    if (slot >= per_xcd || lin >= W) return false;
-    b = (int)(lin / per_seq);
-    rr = (int)(lin % per_seq);
-    return true;
-}
-
-// Phase timing (experiments only, scripts/ablate.sh -DSAVAD_TIMING): wave 0 of workgroup 0 stamps
-// s_memtime at phase boundaries into g_savad_dbg.
-#ifdef SAVAD_TIMING
-__device__ long long g_savad_dbg[64];
-#define SAVAD_STAMP(i)                                                                  \
-    do {                                                                                \
-        if (blockIdx.x == 0 && threadIdx.x == 0) g_savad_dbg[i] = __builtin_readcyclecounter(); \
-    } while (0)
-#else
-#define SAVAD_STAMP(i) \
-    do {               \
-    } while (0)
-#endif
-// Fault injection for the NEGATIVE tests of the hazard checkers (tests/test_async_load_hazards.py, tests/test_gpu_cache_pressure.py;
-// never defined in the product build): bit 1 = the single-launch fp32 forward re-targets the query block's registers (a request
-// for the key block) while the query GEMM still reads them: the load lands inside the GEMM on any box, whatever the caches hold
-// (until round 6 the fault was a missing wait behind a request one LayerNorm earlier, which an L2 hit survived), bit 16 = the bf16 row chain hands ring
-// block 2 over at a barrier without its wait, the DMA issued right in front of it (every wave then reads block 0's bytes), bit 2 = the bf16
-// ring GEMMs wait for one LDS fragment too few, bit 4 = the bf16 weight ring skips its workgroup barrier, bit 8 = the ring waits that
-// leave a wave's own stores in flight allow one operation too many (the newest DMA piece may not have landed at the barrier).
-#ifndef SAVAD_FAULT_INJECT
-#define SAVAD_FAULT_INJECT 0
-#endif
-#ifndef SAVAD_ABLATE
-#define SAVAD_ABLATE 0  // experiment switch (scripts/ablate.sh): 1 = no DMA, 2 = no ring barrier, 4 = no softmax, 8 = no LDS operand reads (bf16 attention)
-#endif
 // ---- asynchronous global -> LDS DMA (global_load_lds_dwordx4): 64 lanes x 16 B from
 // base (SGPR pair, wave-uniform) + per-lane byte offset (VGPR) to LDS at M0 + lane*16.
 // A 16 KB block is 16 such instructions; each of the 4 waves issues 4 of them (instruction index
@@ -531,7 +401,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
         if (32 * jt + 32 > T) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int jk = 8 * (r >> 2) + 4 * h + (r & 3);
+                const int jk = acc_row(r, h);
                 sc[r] = (32 * jt + jk < T) ? sc[r] : NEG_BIG;
             }
         }
@@ -560,59 +430,6 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
 // 4 waves; wave w owns output features [32w,32w+32) of out-proj / QKV (N split) and hidden units
 // [128w,128w+128) of the FFN (K split, partial sums reduce-scattered through LDS once).
 // ---------------------------------------------------------------------------------------------
-// Biases live in LDS for the whole kernel (loaded once, published by the first ring barrier): a
-// global load inside the block loop would be drained by the ring's vmcnt(0) at full L2 latency,
-// once per block.  For the same reason results are stored one block LATE (after the next block's
-// barrier), so that a store's write-ack is never waited for.
-__device__ __forceinline__ void stage_bias(float* dst, const float* __restrict__ src, int count) {
-    for (int i = threadIdx.x * 4; i < count; i += 256 * 4) st4(dst + i, ld4(src + i));
-}
-// Several pieces at once (each <= 1024 floats, a multiple of 4; count 0 = none): ALL the loads first, then the LDS stores.
-// Piece by piece (stage_bias four times in a row) the compiler emits load -> s_waitcnt vmcnt(0) -> ds_write per piece: four
-// dependent round trips to the L2 at the start of every row chain, the first of which also drains whatever else the wave has
-// in flight (round 5, read off the disassembly; the loads are unconditional -- a lane past a piece's end re-reads its last
-// float4 -- so that no branch separates them).
-struct BiasPiece {
-    float* dst;
-    const float* src;
-    int count;
-};
-template <int N>
-struct BiasRegs {
-    f32x4 v[N];
-};
-template <int N>
-__device__ __forceinline__ BiasRegs<N> request_bias_pieces(const BiasPiece (&p)[N]) {
-    const int i = threadIdx.x * 4;
-    BiasRegs<N> r;
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        const int j = i < p[n].count ? i : (p[n].count >= 4 ? p[n].count - 4 : 0);
-        r.v[n] = ld4(p[n].src + j);
-    }
-    return r;
-}
-template <int N>
-__device__ __forceinline__ void commit_bias_pieces(const BiasPiece (&p)[N], const BiasRegs<N>& r) {
-    const int i = threadIdx.x * 4;
-#pragma unroll
-    for (int n = 0; n < N; ++n)
-        if (i < p[n].count) st4(p[n].dst + i, r.v[n]);
-}
-template <int N>
-__device__ __forceinline__ void stage_bias_pieces(const BiasPiece (&p)[N]) {
-    commit_bias_pieces(p, request_bias_pieces(p));
-}
-__device__ __forceinline__ f32x16 bias_block(const float* lds_bias /* &bias[n0] */, int h) {
-    f32x16 r;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 b4 = ld4(lds_bias + 8 * g + 4 * h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) r[4 * g + e] = b4[e];
-    }
-    return r;
-}
 
 // ---- N-split weight streaming: every wave owns its slices of the weight matrices (nothing to share), so
 // they go straight from L2 into the A operand -- but as whole 16-KB BLOCKS (16 x 16-byte loads = 64 VGPRs =
@@ -642,7 +459,7 @@ __device__ __forceinline__ void wmma_w2(f32x16 (&o)[4], const WBlock& wb, const 
 // (Row-major blocks make every load touch 32 lines for 32 bytes each, four instructions per line, all in flight
 // together: the L2 sees the stream four times over.)  48 blocks per layer:
 //   0..11 Wqkv' rows 32b..32b+31 | 12..15 Wo rows | 16..31 W1' rows | 32..47 W2 columns 32(b-32).. (all 128 rows)
-constexpr int FRAG_BLOCK = 4096, FRAG_LAYER = 48 * FRAG_BLOCK;  // floats
+// (FRAG_BLOCK and FRAG_LAYER, in floats: savad_dims.h)
 // The request and the wait are written out by hand: left to itself hipcc sinks the 16 loads of a block down to
 // their first use once the Q / K / V accumulators join the two weight buffers and the activation rows in the
 // register file ("global_load; s_waitcnt vmcnt(0); 4 MFMAs", 16 times per block -- the prefetch is gone).  The
@@ -717,6 +534,61 @@ __device__ __forceinline__ void combine_splits(f32x4 (&xg)[16], const float* __r
     for (int G = 0; G < 16; ++G) xg[G] *= inv;
 }
 
+// ---- steps that the N-split kernels (input_qkv_kernel, row_kernel, packed_forward_kernel) share; the M-split family's
+// counterpart of the first is qkv_tail_m below.  Two more pairs stay written out in their kernels, because every form of a shared
+// function tried for them (result by value or by reference, with and without the bias / residual, __restrict__ or not) changed
+// what the compiler makes of a kernel beyond scheduling (scripts/kernel_diff.py): the input GEMM's K-chunk loop (input_qkv_kernel
+// and packed_forward_kernel: 4 more VGPRs each, other wait counts) and the reduce-scatter behind the FFN (packed_forward_kernel:
+// 4 more VGPRs, 2 more SGPR spills).  For the same reason qkv_tail_n leaves the stores to its callers.
+
+// Q, K, V of the wave's 32 features from LayerNorm'ed rows.  Pre: the query block (fragment block w) is in flight in wa and the key
+// block (4 + w) behind it in wb; the value block is requested here.  The caller stores the results (after the last wait).
+__device__ __forceinline__ void qkv_tail_n(f32x16& qa, f32x16& ka, f32x16& va, const f32x4 (&xg)[16], WBlock& wa, WBlock& wb,
+                                           const float* __restrict__ frag, const float* lbn, int w, int h, int voff) {
+    qa = bias_block(lbn + 32 * w, h);
+    wwait<16>(wa);
+    wmma_k128(qa, wa, xg);
+    wload_frag(wa, frag, 8 + w, voff);
+    ka = bias_block(lbn + D + 32 * w, h);
+    wwait<16>(wb);
+    wmma_k128(ka, wb, xg);
+    va = bias_block(lbn + 2 * D + 32 * w, h);
+    wwait<0>(wa);
+    wmma_k128(va, wa, xg);
+}
+
+// FFN of the N-split kernels: hidden units [128w, 128w+128) in 4 chunks of 32 (wa = W1 slice, the first one already in flight; wb =
+// W2 slice); the ReLU output feeds the second GEMM as B operand straight from the accumulator registers.  o: the wave's K-split
+// partial of all 128 output features.  STAMPS: the per-wait phase stamps 40-45 (scripts/ubench/phase_timing_packed.py).
+template <bool STAMPS>
+__device__ __forceinline__ void ffn_n(f32x16 (&o)[4], WBlock& wa, WBlock& wb, const f32x4 (&xg)[16], const float* __restrict__ frag,
+                                      const float* __restrict__ next_frag, const float* lb1, int w, int h, int voff) {
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) o[nb] = zero16();
+#pragma unroll 1
+    for (int ch = 0; ch < 4; ++ch) {
+        wload_frag(wb, frag, 32 + 4 * w + ch, voff);
+        f32x16 a = bias_block(lb1 + 128 * w + 32 * ch, h);
+        if (STAMPS) SAVAD_STAMP(40);
+        wwait<16>(wa);
+        if (STAMPS) SAVAD_STAMP(41);
+        wmma_k128(a, wa, xg);
+        if (STAMPS) SAVAD_STAMP(42);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) a[r] = fmaxf(a[r], 0.0f);
+        // the next W1 slice, or block w of next_frag (the next layer's query block).  The request is UNCONDITIONAL: where there is
+        // no next layer the caller names a block it will not use (keeps the wait count uniform and the loop free of branches: a
+        // request in one arm of a branch makes the compiler copy blocks that are still in flight where the arms meet) and must
+        // WAIT for it (wwait<0>) before the registers are reused.
+        wload_frag(wa, ch + 1 < 4 ? frag : next_frag, ch + 1 < 4 ? 16 + 4 * w + ch + 1 : w, voff);
+        if (STAMPS) SAVAD_STAMP(43);
+        wwait<16>(wb);
+        if (STAMPS) SAVAD_STAMP(44);
+        wmma_w2(o, wb, a);
+        if (STAMPS) SAVAD_STAMP(45);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Kernel 1: input Linear(F, D) + sinusoidal PE / sqrt(D)  (vad/models/self_attention.py:12-16,24;
 // vad/modeling/transformer.py:392-401), then layer-0 LN + QKV (transformer.py:234-237,281-284).
@@ -778,16 +650,8 @@ __global__ __launch_bounds__(256, 1) void input_qkv_kernel(
     __syncthreads();
     f32x4 xg[16];
     read_rows_layernorm(xbuf, m, h, xg);
-    f32x16 qa = bias_block(lbn + 32 * w, h);
-    wwait<16>(wa);
-    wmma_k128(qa, wa, xg);
-    wload_frag(wa, frag0, 8 + w, voff);
-    f32x16 ka = bias_block(lbn + D + 32 * w, h);
-    wwait<16>(wb);
-    wmma_k128(ka, wb, xg);
-    f32x16 va = bias_block(lbn + 2 * D + 32 * w, h);
-    wwait<0>(wa);
-    wmma_k128(va, wa, xg);
+    f32x16 qa, ka, va;
+    qkv_tail_n(qa, ka, va, xg, wa, wb, frag0, lbn, w, h, voff);
     store_block(q + row * D + 32 * w, qa, h);
     store_block(k + row * D + 32 * w, ka, h);
     store_block(v + row * D + 32 * w, va, h);
@@ -841,26 +705,10 @@ __global__ __launch_bounds__(256, 1) void row_kernel(
     __syncthreads();
     read_rows_layernorm(xbuf, m, h, xg);
     SAVAD_STAMP(34);
-    // ---- phase 2: FFN, hidden units [128w, 128w+128) in 4 chunks of 32; ReLU output feeds the
-    //      second GEMM as B operand straight from the accumulator registers
+    // ---- phase 2: FFN.  Its last chunk requests the next layer's query block; the LAST launch re-reads a block it will not use
+    // (ffn_n says why the request is unconditional) ...
     f32x16 o[4];
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) o[nb] = zero16();
-#pragma unroll 1
-    for (int ch = 0; ch < 4; ++ch) {
-        wload_frag(wb, frag, 32 + 4 * w + ch, voff);
-        f32x16 a = bias_block(lb1 + 128 * w + 32 * ch, h);
-        wwait<16>(wa);
-        wmma_k128(a, wa, xg);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) a[r] = fmaxf(a[r], 0.0f);
-        // the next W1 slice, or the next layer's query block; the LAST launch re-reads a block it will not use (keeps the
-        // wait count uniform and the loop free of branches: a request in one arm of a branch makes the compiler copy blocks
-        // that are still in flight where the arms meet)
-        wload_frag(wa, (ch + 1 < 4 || LAST) ? frag : nfrag, ch + 1 < 4 ? 16 + 4 * w + ch + 1 : w, voff);
-        wwait<16>(wb);
-        wmma_w2(o, wb, a);
-    }
+    ffn_n<false>(o, wa, wb, xg, frag, LAST ? frag : nfrag, lb1, w, h, voff);
     // ... but it WAITS for that block: a request left in flight lands on whatever the compiler keeps in those registers by
     // then (round 4: one wrong 32-row tile in a few percent of the runs with other streams' kernels pressing on the L2)
     if (LAST) wwait<0>(wa);
@@ -891,37 +739,14 @@ __global__ __launch_bounds__(256, 1) void row_kernel(
     if (!LAST) {
         // Q (in flight in wa), K, V blocks of this wave's 32 features; results are stored after the last wait
         wload_frag(wb, nfrag, 4 + w, voff);
-        f32x16 qa = bias_block(lbn + 32 * w, h);
-        wwait<16>(wa);
-        wmma_k128(qa, wa, xg);
-        wload_frag(wa, nfrag, 8 + w, voff);
-        f32x16 ka = bias_block(lbn + D + 32 * w, h);
-        wwait<16>(wb);
-        wmma_k128(ka, wb, xg);
-        f32x16 va = bias_block(lbn + 2 * D + 32 * w, h);
-        wwait<0>(wa);
-        wmma_k128(va, wa, xg);
+        f32x16 qa, ka, va;
+        qkv_tail_n(qa, ka, va, xg, wa, wb, nfrag, lbn, w, h, voff);
         store_block(q + row * D + 32 * w, qa, h);
         store_block(k + row * D + 32 * w, ka, h);
         store_block(v + row * D + 32 * w, va, h);
     } else if (w == 0) {
-        float z0 = 0.0f, z1 = 0.0f;
-#pragma unroll
-        for (int G = 0; G < 16; ++G) {
-            const f32x4 c0 = ld4(Wn + 8 * G + 4 * h), c1 = ld4(Wn + D + 8 * G + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                z0 = __builtin_fmaf(xg[G][e], c0[e], z0);
-                z1 = __builtin_fmaf(xg[G][e], c1[e], z1);
-            }
-        }
-        z0 = half_sum(z0);
-        z1 = half_sum(z1);
-        z0 += bn[0];
-        z1 += bn[1];
-        const float mx = fmaxf(z0, z1);
-        const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
-        if (h == 0 && row < (size_t)rows) *reinterpret_cast<f32x2*>(out + row * 2) = f32x2{z0 - lse, z1 - lse};
+        const f32x2 lp = classify_rows(xg, Wn, bn, h);
+        if (h == 0 && row < (size_t)rows) *reinterpret_cast<f32x2*>(out + row * 2) = lp;
     }
     SAVAD_STAMP(38);
 }
@@ -942,12 +767,6 @@ __global__ __launch_bounds__(256, 1) void row_kernel(
 // 32 attention MFMAs per wave and layer instead of the 128 redundant ones of row_kernel's packed mode, no
 // q / k / v / h round trip through L2 and one launch instead of four.
 // ---------------------------------------------------------------------------------------------
-// window geometry of the predictor (vad/predictor.py:186-212): W relative frame offsets
-struct WindowOffsets {
-    int w;
-    int off[64];
-};
-constexpr int PACKED_MAX_LAYERS = 8;
 struct PackedLayer {
     const float* frag;  // Wqkv / W1: LayerNorm affine folded in
 };
@@ -957,7 +776,6 @@ struct PackedModel {
     const float* bias;  // [L][LBIAS]: b1' | b2 | bqkv' | bo of every layer, contiguous
     int L;
 };
-constexpr int LBIAS = DFF + D + 3 * D + D;  // b1 | b2 | bqkv | bo
 
 // Windowed mode (wo.w == T > 0): x is the predictor's feature MATRIX [N][F] and sequence s is its window
 // feature[win_base + s + wo.off[0..T-1]] (a13, vad/predictor.py:180-220) -- the gather is an address computation here
@@ -1086,7 +904,7 @@ __global__ __launch_bounds__(256, 1) void packed_forward_kernel(const float* __r
         float mx = NEG_BIG;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int jk = 8 * (r >> 2) + 4 * h + (r & 3);
+            const int jk = acc_row(r, h);
             const bool ok = (jk < tile_rows) && (jk / T == tq) && ((size_t)blockIdx.x * tile_rows + jk < (size_t)rows);
             sc[r] = ok ? sc[r] : NEG_BIG;
             mx = fmaxf(mx, sc[r]);
@@ -1118,31 +936,10 @@ __global__ __launch_bounds__(256, 1) void packed_forward_kernel(const float* __r
         __syncthreads();
         read_rows_layernorm(xb0, m, h, xg);
         SAVAD_STAMP(55);
-        // ---- FFN: hidden units [128w, 128w+128) in 4 chunks of 32 (wa = W1 slice, wb = W2 slice), as in row_kernel
+        // ---- FFN, as in row_kernel; behind the last layer the stream simply re-reads a block it will not use (waited for behind
+        // the layer loop)
         f32x16 o[4];
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) o[nb] = zero16();
-        const float* nfrag = M.layer[l + 1 < M.L ? l + 1 : l].frag;
-#pragma unroll 1
-        for (int ch = 0; ch < 4; ++ch) {
-            wload_frag(wb, frag, 32 + 4 * w + ch, voff);
-            f32x16 a = bias_block(lb1 + 128 * w + 32 * ch, h);
-            SAVAD_STAMP(40);
-            wwait<16>(wa);
-            SAVAD_STAMP(41);
-            wmma_k128(a, wa, xg);
-            SAVAD_STAMP(42);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a[r] = fmaxf(a[r], 0.0f);
-            // the next W1 slice, or the next layer's query block; behind the last layer the stream simply re-reads a
-            // block it will not use (keeps the wait count uniform; waited for behind the layer loop)
-            wload_frag(wa, ch + 1 < 4 ? frag : nfrag, ch + 1 < 4 ? 16 + 4 * w + ch + 1 : w, voff);
-            SAVAD_STAMP(43);
-            wwait<16>(wb);
-            SAVAD_STAMP(44);
-            wmma_w2(o, wb, a);
-            SAVAD_STAMP(45);
-        }
+        ffn_n<true>(o, wa, wb, xg, frag, M.layer[l + 1 < M.L ? l + 1 : l].frag, lb1, w, h, voff);
         SAVAD_STAMP(56);
         // reduce-scatter the 4 K-split partials: wave w ends up with feature block w (the score tiles' readers
         // passed two barriers since)
@@ -1169,21 +966,8 @@ __global__ __launch_bounds__(256, 1) void packed_forward_kernel(const float* __r
     __syncthreads();
     if (w == 0) {
         read_rows_layernorm(xb0, m, h, xg);
-        float z0 = 0.0f, z1 = 0.0f;
-#pragma unroll
-        for (int G = 0; G < 16; ++G) {
-            const f32x4 c0 = ld4(M.wc + 8 * G + 4 * h), c1 = ld4(M.wc + D + 8 * G + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                z0 = __builtin_fmaf(xg[G][e], c0[e], z0);
-                z1 = __builtin_fmaf(xg[G][e], c1[e], z1);
-            }
-        }
-        z0 = half_sum(z0) + M.bc[0];
-        z1 = half_sum(z1) + M.bc[1];
-        const float mx = fmaxf(z0, z1);
-        const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
-        if (h == 0 && lane_ok) *reinterpret_cast<f32x2*>(out + row * 2) = f32x2{z0 - lse, z1 - lse};
+        const f32x2 lp = classify_rows(xg, M.wc, M.bc, h);
+        if (h == 0 && lane_ok) *reinterpret_cast<f32x2*>(out + row * 2) = lp;
     }
     SAVAD_STAMP(58);
 }
@@ -1230,29 +1014,6 @@ __device__ __forceinline__ void gemm_lds_b(f32x16 (&o)[4], const float* buf, int
             for (int e = 0; e < 4; ++e) o[nb] = SAVAD_MFMA(w4[e], a[4 * g + e], o[nb]);
         }
     }
-}
-// LayerNorm (no affine) of full rows held as 4 row-layout blocks -> B-operand registers
-__device__ __forceinline__ void layernorm_regs(const f32x16 (&x)[4], f32x4 (&xg)[16]) {
-    float s = 0.0f;
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s += x[nb][r];
-    s = half_sum(s);
-    const float mean = s * (1.0f / D);
-    float ss = 0.0f;
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float d = x[nb][r] - mean;
-            xg[4 * nb + (r >> 2)][r & 3] = d;
-            ss += d * d;
-        }
-    ss = half_sum(ss);
-    const float rstd = 1.0f / sqrtf(ss * (1.0f / D) + LN_EPS);
-#pragma unroll
-    for (int G = 0; G < 16; ++G) xg[G] *= rstd;
 }
 
 // QKV tail shared by both M-split kernels: 12 ring blocks (Wqkv rows 32j .. 32j+31); block 0 must
@@ -1395,23 +1156,8 @@ __device__ __forceinline__ void row_chain_m(f32x4 (&xg)[16], f32x16 (&h1)[4], si
         qkv_tail_m(xg, Wn, lbn, q, k, v, row, ring, LA, w, n, h, store_ok, act);
         SAVAD_STAMP(8);
     } else {
-        float z0 = 0.0f, z1 = 0.0f;
-#pragma unroll
-        for (int G = 0; G < 16; ++G) {
-            const f32x4 c0 = ld4(Wn + 8 * G + 4 * h), c1 = ld4(Wn + D + 8 * G + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                z0 = __builtin_fmaf(xg[G][e], c0[e], z0);
-                z1 = __builtin_fmaf(xg[G][e], c1[e], z1);
-            }
-        }
-        z0 = half_sum(z0);
-        z1 = half_sum(z1);
-        z0 += bn[0];
-        z1 += bn[1];
-        const float mx = fmaxf(z0, z1);
-        const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
-        if (h == 0 && out_ok) *reinterpret_cast<f32x2*>(out + row * 2) = f32x2{z0 - lse, z1 - lse};
+        const f32x2 lp = classify_rows(xg, Wn, bn, h);
+        if (h == 0 && out_ok) *reinterpret_cast<f32x2*>(out + row * 2) = lp;
     }
 }
 
@@ -1533,7 +1279,7 @@ __global__ __launch_bounds__(256, 2) void attention_row_kernel(
         if (32 * jt + 32 > T) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int jk = 8 * (r >> 2) + 4 * h + (r & 3);
+                const int jk = acc_row(r, h);
                 sc[r] = (32 * jt + jk < T) ? sc[r] : NEG_BIG;
             }
         }
@@ -1569,181 +1315,6 @@ __global__ __launch_bounds__(256, 2) void attention_row_kernel(
             for (int r = 0; r < 16; ++r) xg[4 * nb + (r >> 2)][r & 3] = qvalid ? O[nb][r] * inv : 0.0f;
     }
     row_chain_m<LAST>(xg, h1, row, qvalid, qvalid, active, ring, lbo, lb1, lb2, lbn, LA, LB, Wo, W1, W2, Wn, bn, hbuf, qn, kn, vn, out, w, n, h);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Weight preparation: fold a LayerNorm's affine parameters into the Linear that consumes it:
-//   LN(x) W^T + b = xhat (W diag(gamma))^T + (b + W beta)
-// One block per output row; beta term accumulated in fp64.
-// ---------------------------------------------------------------------------------------------
-// fp32 weights in fragment order (PackedLayer::frag).  mode 0: `count` row blocks of W [32 count][128] (register i =
-// k-chunk G: W[32 b + n][8 G + 4 h + e]); mode 1: `count` column blocks of W2 [128][512] (register i = 4 nb + g:
-// W2[32 nb + n][32 b + 8 g + 4 h + e]).
-__global__ void pack_frag32_kernel(const float* __restrict__ W, int mode, int count, float* __restrict__ out) {
-    const size_t total = (size_t)count * FRAG_BLOCK;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int b = (int)(idx / FRAG_BLOCK), r = (int)(idx % FRAG_BLOCK);
-        const int i = r >> 8, lane = (r >> 2) & 63, e = r & 3, n = lane & 31, h = lane >> 5;
-        out[idx] = mode == 0 ? W[(size_t)(32 * b + n) * D + 8 * i + 4 * h + e]
-                             : W[(size_t)(32 * (i >> 2) + n) * DFF + 32 * b + 8 * (i & 3) + 4 * h + e];
-    }
-}
-
-__global__ void fold_ln_kernel(const float* __restrict__ W, const float* __restrict__ b, const float* __restrict__ gamma,
-                               const float* __restrict__ beta, float* __restrict__ Wout, float* __restrict__ bout,
-                               int K) {
-    __shared__ double red[256];
-    const int nrow = blockIdx.x;
-    double acc = 0.0;
-    for (int kk = threadIdx.x; kk < K; kk += blockDim.x) {
-        const float wv = W[(size_t)nrow * K + kk];
-        Wout[(size_t)nrow * K + kk] = wv * gamma[kk];
-        acc += (double)wv * (double)beta[kk];
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int st = blockDim.x / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bout[nrow] = (float)((double)b[nrow] + red[0]);
-}
-
-// ---------------------------------------------------------------------------------------------
-// a13: window gather (vad/predictor.py:180-220).  One thread per output float4.
-// ---------------------------------------------------------------------------------------------
-__global__ void gather_windows_kernel(const float* __restrict__ feature, int F, int half, int first, int count,
-                                      WindowOffsets wo, float* __restrict__ windows, int64_t* __restrict__ positions) {
-    const int f4 = F / 4;
-    const size_t total = (size_t)count * wo.w * f4;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % f4);
-        const size_t iw = i / f4;
-        const int wi = (int)(iw % wo.w);
-        const size_t item = iw / wo.w;
-        const size_t pos = (size_t)half + first + item + wo.off[wi];
-        st4(windows + iw * F + 4 * c, ld4(feature + pos * F + 4 * c));
-        if (c == 0 && positions) positions[iw] = (int64_t)pos;
-    }
-}
-
-// the same for a feature size that is not a multiple of 4 (the MFCC / spectrogram front-ends: 13, 39, 161 ...): one float per thread
-__global__ void gather_windows_scalar_kernel(const float* __restrict__ feature, int F, int half, int first, int count,
-                                             WindowOffsets wo, float* __restrict__ windows, int64_t* __restrict__ positions) {
-    const size_t total = (size_t)count * wo.w * F;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % F);
-        const size_t iw = i / F;
-        const int wi = (int)(iw % wo.w);
-        const size_t item = iw / wo.w;
-        const size_t pos = (size_t)half + first + item + wo.off[wi];
-        windows[i] = feature[pos * F + c];
-        if (c == 0 && positions) positions[iw] = (int64_t)pos;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// a14: boosted prediction (vad/predictor.py:238-258, :95): scatter, then softmax[...,1] and mean.
-// ---------------------------------------------------------------------------------------------
-__global__ void boost_scatter_kernel(const float* __restrict__ logp, const int64_t* __restrict__ positions,
-                                     size_t count_w, int W, float* __restrict__ boosted) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count_w; i += (size_t)gridDim.x * blockDim.x) {
-        const int wi = (int)(i % W);
-        const size_t p = (size_t)positions[i];
-        *reinterpret_cast<f32x2*>(boosted + (p * W + wi) * 2) = *reinterpret_cast<const f32x2*>(logp + i * 2);
-    }
-}
-__global__ void boost_softmax_kernel(const float* __restrict__ boosted, int N, int W, float* __restrict__ probs,
-                                     float* __restrict__ mean) {
-    for (int nrow = blockIdx.x * blockDim.x + threadIdx.x; nrow < N; nrow += gridDim.x * blockDim.x) {
-        float acc = 0.0f;
-        for (int wi = 0; wi < W; ++wi) {
-            const f32x2 z = *reinterpret_cast<const f32x2*>(boosted + ((size_t)nrow * W + wi) * 2);
-            const float mx = fmaxf(z[0], z[1]);
-            const float e0 = expf(z[0] - mx), e1 = expf(z[1] - mx);
-            const float p = e1 / (e0 + e1);
-            probs[(size_t)nrow * W + wi] = p;
-            acc += p;
-        }
-        if (mean) mean[nrow] = acc / (float)W;
-    }
-}
-
-// The same result as scatter + softmax, read the other way round: slot (n, w) of the boosted array was written by
-// window b = n - half - off[w] if that window exists, else it still holds (0, 0) -> 0.5.  Same arithmetic on the same
-// values, no memset, no scatter launch, no positions array.
-__global__ void boost_gather_kernel(const float* __restrict__ logp, int n_items, int N, int half, WindowOffsets wo,
-                                    float* __restrict__ probs, float* __restrict__ mean) {
-    const int W = wo.w;
-    for (int nrow = blockIdx.x * blockDim.x + threadIdx.x; nrow < N; nrow += gridDim.x * blockDim.x) {
-        float acc = 0.0f;
-        for (int wi = 0; wi < W; ++wi) {
-            const int b = nrow - half - wo.off[wi];
-            f32x2 z = f32x2{0.0f, 0.0f};
-            if (b >= 0 && b < n_items) z = *reinterpret_cast<const f32x2*>(logp + ((size_t)b * W + wi) * 2);
-            const float mx = fmaxf(z[0], z[1]);
-            const float e0 = expf(z[0] - mx), e1 = expf(z[1] - mx);
-            const float p = e1 / (e0 + e1);
-            probs[(size_t)nrow * W + wi] = p;
-            acc += p;
-        }
-        if (mean) mean[nrow] = acc / (float)W;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Streaming long-form mode (BASELINE configs[4]; not a reference mode -- the reference would cut
-// 7-frame windows): window w covers frames [hop*w, hop*w + T) of feature[N][F], zero-padded past N.
-// ---------------------------------------------------------------------------------------------
-__global__ void gather_strided_kernel(const float* __restrict__ feature, int N, int F, int T, int hop, int first,
-                                      int count, float* __restrict__ windows) {
-    const int f4 = F / 4;
-    const size_t total = (size_t)count * T * f4;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % f4);
-        const size_t wt = i / f4;
-        const int t = (int)(wt % T);
-        const size_t wi = wt / T;
-        const long frame = (long)hop * (long)(first + wi) + t;
-        f32x4 val = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (frame < N) val = ld4(feature + (size_t)frame * F + 4 * c);
-        st4(windows + wt * F + 4 * c, val);
-    }
-}
-// probs[n] = mean over the windows w covering frame n (hop*w <= n < hop*w + T, 0 <= w < W) of
-// softmax(logp[w][n - hop*w])[1]
-__global__ void overlap_merge_kernel(const float* __restrict__ logp, int W, int N, int T, int hop,
-                                     float* __restrict__ probs) {
-    for (int nrow = blockIdx.x * blockDim.x + threadIdx.x; nrow < N; nrow += gridDim.x * blockDim.x) {
-        int w_hi = nrow / hop;
-        if (w_hi > W - 1) w_hi = W - 1;
-        float acc = 0.0f;
-        int cnt = 0;
-        for (int wi = w_hi; wi >= 0 && nrow - hop * wi < T; --wi) {
-            const f32x2 z = *reinterpret_cast<const f32x2*>(logp + ((size_t)wi * T + (nrow - hop * wi)) * 2);
-            const float mx = fmaxf(z[0], z[1]);
-            const float e0 = expf(z[0] - mx), e1 = expf(z[1] - mx);
-            acc += e1 / (e0 + e1);
-            ++cnt;
-        }
-        probs[nrow] = cnt ? acc / (float)cnt : 0.5f;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Arbitrary feature sizes (the reference's transforms give 80 mels, 257 spectrogram bins, n_mfcc ...):
-// the MFMA kernels read K in groups of 8 (fp32) / 16 (bf16) with 16-byte loads, so rows are zero-padded
-// to FP = round_up(F, 16) when F is not a multiple of 16: the input weight once (prepare_weights), the
-// features once per forward.
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void pad_rows_kernel(const T* __restrict__ src, size_t rows, int F, int FP, float* __restrict__ dst) {
-    const size_t total = rows * (size_t)FP;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % FP);
-        const size_t r = i / FP;
-        dst[i] = c < F ? (float)src[r * F + c] : 0.0f;
-    }
 }
 
 }  // namespace savad

@@ -16,7 +16,7 @@
 //   h         : [block][nb 4][gp 2][lane 64][8 f16]  (residual stream as stored between kernels)
 //   weights   : [n-block][ks][lane 64][8 bf16], packed once by pack_weight_frags_kernel
 #pragma once
-#include "savad_kernels.h"
+#include "savad_device.h"
 #include <type_traits>
 
 namespace savad {
@@ -36,10 +36,8 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #define SAVAD_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
-constexpr int FRAG_BYTES = 1024;             // one K-step fragment of 32 rows: 64 lanes x 16 B
-constexpr int BLK_BYTES = 8 * FRAG_BYTES;    // 32 rows x 128 features in bf16
+// FRAG_BYTES, BLK_BYTES, HBLK_FLOATS: savad_dims.h
 constexpr int RING_BYTES = 4 * BLK_BYTES;    // one ring block = 128 output features x 128 k = 32 KiB
-constexpr int HBLK_FLOATS = 32 * D;          // elements of one residual block
 
 __device__ __forceinline__ bf16x8 ldfrag(const void* p) {
     return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(p));
@@ -93,6 +91,7 @@ __device__ __forceinline__ bool slot_row(int B, int T, int blk, int m, size_t& r
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 hres_t;
+static_assert(sizeof(hres_t) == HRES_BYTES, "savad_dims.h");
 __device__ __forceinline__ void load_hblock(f32x16 (&x)[4], const hres_t* hb, int lane) {
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb)
@@ -737,7 +736,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention_kernel_bf1
                     asm volatile("" ::: "memory");
                     const int lim = T - 32 * jt - 4 * h;
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) sc[r] = (8 * (r >> 2) + (r & 3) < lim) ? sc[r] : NEG_BIG;
+                    for (int r = 0; r < 16; ++r) sc[r] = (acc_row(r, 0) < lim) ? sc[r] : NEG_BIG;
                 }
             };
             attn_tile(st, qp, buf + tt * BLK_BYTES, buf + (2 + tt) * BLK_BYTES, mask, jt == 0, lane);
@@ -768,10 +767,7 @@ __global__ __launch_bounds__(256, 2) void attention_packed_kernel_bf16(const cha
     attn_state_init(st);
     bool keyok[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int jk = 8 * (r >> 2) + 4 * h + (r & 3);
-        keyok[r] = (jk < G * T) && (jk / T == m / T) && (blk * G + jk / T < B);
-    }
+    for (int r = 0; r < 16; ++r) keyok[r] = packed_key_ok(B, T, blk, m, acc_row(r, h));
     auto mask = [&](f32x16& sc) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) sc[r] = keyok[r] ? sc[r] : NEG_BIG;
@@ -894,24 +890,11 @@ __device__ __forceinline__ void row_stage_bf16(const RowArgsBf16& A, char* smem,
             qkv_block_bf16(rb, ring.slot(9 + rb), xp, lbn, A.qf, A.kf, A.vtf, blk, lane, A.qscale, live);
         }
     } else {
-        float z0 = 0.0f, z1 = 0.0f;
-#pragma unroll
-        for (int G = 0; G < 16; ++G) {
-            const f32x4 c0 = ld4(lbn + 8 * G + 4 * h), c1 = ld4(lbn + D + 8 * G + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                z0 = __builtin_fmaf(xg[G][e], c0[e], z0);
-                z1 = __builtin_fmaf(xg[G][e], c1[e], z1);
-            }
-        }
-        z0 = half_sum(z0) + lbn[2 * D];
-        z1 = half_sum(z1) + lbn[2 * D + 1];
-        const float mx = fmaxf(z0, z1);
-        const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
+        const f32x2 lp = classify_rows(xg, lbn, lbn + 2 * D, h);
         size_t row;
         int t_frame;
         const bool valid = live && (blk < A.nblk) && slot_row(A.B, A.T, blk, m, row, t_frame);
-        if (h == 0 && valid) *reinterpret_cast<f32x2*>(A.out + row * 2) = f32x2{z0 - lse, z1 - lse};
+        if (h == 0 && valid) *reinterpret_cast<f32x2*>(A.out + row * 2) = lp;
     }
 }
 
@@ -981,7 +964,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attention_row_kernel
                     asm volatile("" ::: "memory");
                     const int lim = T - 32 * jt - 4 * h;
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) sc[r] = (8 * (r >> 2) + (r & 3) < lim) ? sc[r] : NEG_BIG;
+                    for (int r = 0; r < 16; ++r) sc[r] = (acc_row(r, 0) < lim) ? sc[r] : NEG_BIG;
                 }
             };
             attn_tile(st, qp, buf + tt * BLK_BYTES, buf + (2 + tt) * BLK_BYTES, mask, jt == 0, lane);

@@ -41,7 +41,7 @@
 //
 // Reference being restated: vad/models/self_attention.py:23-28, vad/modeling/transformer.py:24-61,227-238,258-363,366-382.
 #pragma once
-#include "savad_kernels_bf16.h"
+#include "savad_kernels_bf16.h"  // the skeleton it is built on: bf16x8, ldfrag / stfrag, slot_row, AttnState, online_softmax_shifted, Ring<4>::vmcnt_imm ...
 #include <type_traits>
 
 namespace savad {
@@ -60,11 +60,9 @@ using bf::AttnState;
 using bf::attn_state_init;
 using bf::online_softmax_shifted;
 
-constexpr int TFRAG_BYTES = 3 * FRAG_BYTES;   // one triple
-constexpr int BLK3_BYTES = 8 * TFRAG_BYTES;   // 32 rows x 128 features as triples: 24 KiB
+// TFRAG_BYTES, BLK3_BYTES, HBLK_BYTES: savad_dims.h
 constexpr int SLOT_BYTES = 2 * BLK3_BYTES;    // a ring slot: 48 KiB
 constexpr int NRING3 = 3;
-constexpr int HBLK_BYTES = 32 * D * 4;        // a residual block (fp32)
 constexpr int ROW_LDS_BYTES = NRING3 * SLOT_BYTES + 9 * D * 4;
 
 struct Tri {
@@ -954,24 +952,11 @@ __device__ __forceinline__ void row_stage_f32s(const RowArgs3& A, char* smem, Tr
         }
 #undef SAVAD_ROW_QKV
     } else {
-        float z0 = 0.0f, z1 = 0.0f;
-#pragma unroll
-        for (int G = 0; G < 16; ++G) {
-            const f32x4 c0 = ld4(lbn + 8 * G + 4 * h), c1 = ld4(lbn + D + 8 * G + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                z0 = __builtin_fmaf(xg[G][e], c0[e], z0);
-                z1 = __builtin_fmaf(xg[G][e], c1[e], z1);
-            }
-        }
-        z0 = half_sum(z0) + lbn[2 * D];
-        z1 = half_sum(z1) + lbn[2 * D + 1];
-        const float mx = fmaxf(z0, z1);
-        const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
+        const f32x2 lp = classify_rows(xg, lbn, lbn + 2 * D, h);
         size_t row;
         int t_frame;
         const bool valid = live && (blk < A.nblk) && slot_row(A.B, A.T, blk, m, row, t_frame);
-        if (h == 0 && valid) *reinterpret_cast<f32x2*>(A.out + row * 2) = f32x2{z0 - lse, z1 - lse};
+        if (h == 0 && valid) *reinterpret_cast<f32x2*>(A.out + row * 2) = lp;
     }
 }
 
@@ -1018,10 +1003,7 @@ __global__ __launch_bounds__(256, 1) void attention_row_kernel_f32s(const char* 
             for (int ks = 0; ks < 8; ++ks) qp[ks] = ldtri(qf + (size_t)blk_q * BLK3_BYTES + ks * TFRAG_BYTES + lane * 16);
             bool keyok[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int jk = 8 * (r >> 2) + 4 * h + (r & 3);
-                keyok[r] = (jk < G * T) && (jk / T == m / T) && (blk_q * G + jk / T < B);
-            }
+            for (int r = 0; r < 16; ++r) keyok[r] = packed_key_ok(B, T, blk_q, m, acc_row(r, h));
             auto mask = [&](f32x16& sc) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) sc[r] = keyok[r] ? sc[r] : NEG_BIG;
@@ -1060,7 +1042,7 @@ __global__ __launch_bounds__(256, 1) void attention_row_kernel_f32s(const char* 
             if (32 * QB > T) {
                 asm volatile("" ::: "memory");
 #pragma unroll
-                for (int r = 0; r < 16; ++r) sc[r] = (8 * (r >> 2) + (r & 3) < lim) ? sc[r] : NEG_BIG;
+                for (int r = 0; r < 16; ++r) sc[r] = (acc_row(r, 0) < lim) ? sc[r] : NEG_BIG;
             }
         };
         ring.acquire<2>();   // K(0) has landed; slots 0 and 1 may still be in flight
@@ -1128,7 +1110,6 @@ __global__ __launch_bounds__(256, 1) void attention_row_kernel_f32s(const char* 
 // [N][F] and sequence s is its window feature[win_base + s + wo.off[0..T-1]] (vad/predictor.py:180-220): the gather is an address
 // computation.
 // ---------------------------------------------------------------------------------------------
-constexpr int PACKED_F32S_MAX_LAYERS = 3;  // ring (144 KiB) + 3 x 4.5 KiB of biases + the classifier fit the 160 KiB of LDS
 struct PackedF32sLayer {
     const char *wqkv, *wo, *w1, *w2;  // triples (pack_weight_frags3_kernel), LayerNorm affine folded in
 };
@@ -1180,10 +1161,7 @@ __global__ __launch_bounds__(256, 1) void packed_forward_kernel_f32s(const float
     const size_t row = valid ? (size_t)seq * T + t_frame : 0;
     bool keyok[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int jk = 8 * (r >> 2) + 4 * h + (r & 3);
-        keyok[r] = (jk < G * T) && (jk / T == m / T) && (blk * G + jk / T < B);
-    }
+    for (int r = 0; r < 16; ++r) keyok[r] = packed_key_ok(B, T, blk, m, acc_row(r, h));
     // ---- input Linear + positional encoding (vad/models/self_attention.py:12-16,24)
     f32x16 hres[4], acc[4];
 #pragma unroll
@@ -1317,21 +1295,8 @@ __global__ __launch_bounds__(256, 1) void packed_forward_kernel_f32s(const float
     }
 #undef SAVAD_PK_GEMM
     // ---- final LayerNorm (folded into the classifier) + Linear(D, 2) + log-softmax (vad/models/self_attention.py:26-28)
-    float z0 = 0.0f, z1 = 0.0f;
-#pragma unroll
-    for (int Gq = 0; Gq < 16; ++Gq) {
-        const f32x4 c0 = ld4(lwc + 8 * Gq + 4 * h), c1 = ld4(lwc + D + 8 * Gq + 4 * h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            z0 = __builtin_fmaf(xg[Gq][e], c0[e], z0);
-            z1 = __builtin_fmaf(xg[Gq][e], c1[e], z1);
-        }
-    }
-    z0 = half_sum(z0) + lwc[2 * D];
-    z1 = half_sum(z1) + lwc[2 * D + 1];
-    const float mx = fmaxf(z0, z1);
-    const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
-    if (h == 0 && valid) *reinterpret_cast<f32x2*>(out + row * 2) = f32x2{z0 - lse, z1 - lse};
+    const f32x2 lp = classify_rows(xg, lwc, lwc + 2 * D, h);
+    if (h == 0 && valid) *reinterpret_cast<f32x2*>(out + row * 2) = lp;
     wait_vmem_all();  // the two slots requested behind the last layer are never read, but must have landed before the LDS is released
 }
 
@@ -1425,7 +1390,7 @@ __global__ __launch_bounds__(256, 1) void packed_forward_kernel_f32s_ns(const fl
     bool keyok[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int jk = 8 * (r >> 2) + 4 * h + (r & 3), jq = div_t(jk);
+        const int jk = acc_row(r, h), jq = div_t(jk);
         keyok[r] = (jk < G * T) && (jq == sq) && (blk * G + jq < B);
     }
     // ---- this wave's weight stream: chunk c of layer l
@@ -1723,21 +1688,8 @@ __global__ __launch_bounds__(256, 1) void packed_forward_kernel_f32s_ns(const fl
     // ---- final LayerNorm (folded into the classifier) + Linear(D, 2) + log-softmax (vad/models/self_attention.py:26-28)
     rows_ln(xb0, own, false);
     if (w == 0) {
-        float z0 = 0.0f, z1 = 0.0f;
-#pragma unroll
-        for (int Gq = 0; Gq < 16; ++Gq) {
-            const f32x4 c0 = ld4(lwc + 8 * Gq + 4 * h), c1 = ld4(lwc + D + 8 * Gq + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                z0 = __builtin_fmaf(xg[Gq][e], c0[e], z0);
-                z1 = __builtin_fmaf(xg[Gq][e], c1[e], z1);
-            }
-        }
-        z0 = half_sum(z0) + lwc[2 * D];
-        z1 = half_sum(z1) + lwc[2 * D + 1];
-        const float mx = fmaxf(z0, z1);
-        const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
-        if (h == 0 && valid) *reinterpret_cast<f32x2*>(out + row * 2) = f32x2{z0 - lse, z1 - lse};
+        const f32x2 lp = classify_rows(xg, lwc, lwc + 2 * D, h);
+        if (h == 0 && valid) *reinterpret_cast<f32x2*>(out + row * 2) = lp;
     }
     SAVAD_STAMP(52);
 }

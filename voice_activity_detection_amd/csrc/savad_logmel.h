@@ -13,7 +13,7 @@
 // values feed the mel GEMM from the accumulator registers; log and the [N,80] store finish the
 // tile.  One workgroup = 32 frames, its 4 waves take one pass of 4 DFT row blocks (64 bins) each.
 #pragma once
-#include "savad_kernels.h"
+#include "savad_device.h"
 #include <type_traits>
 
 namespace savad {

@@ -21,7 +21,6 @@
 namespace savad {
 namespace bf {
 
-constexpr int PACKED_BF16_MAX_LAYERS = 6;  // ring (NW = 8: 128 KiB) + 6 x 4.5 KiB of biases fit the 160 KiB of LDS
 
 struct PackedBf16Layer {
     const char *wqkv, *wo, *w1, *w2;  // fragment-major bf16 (pack_weight_frags_kernel), LayerNorm affine folded in
@@ -137,10 +136,7 @@ __global__ __launch_bounds__(64 * (NW + DW), (NW + DW == 8) ? 1 : 2) void packed
     const size_t row = valid ? (size_t)seq * T + t_frame : 0;
     bool keyok[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int jk = 8 * (r >> 2) + 4 * h + (r & 3);
-        keyok[r] = (jk < G * T) && (jk / T == m / T) && (blk * G + jk / T < B);
-    }
+    for (int r = 0; r < 16; ++r) keyok[r] = packed_key_ok(B, T, blk, m, acc_row(r, h));
     // ---- input Linear + positional encoding (self_attention.py:12-16,24), as input_qkv_kernel_bf16
     f32x16 acc[4];
 #pragma unroll
@@ -302,21 +298,8 @@ __global__ __launch_bounds__(64 * (NW + DW), (NW + DW == 8) ? 1 : 2) void packed
         if (l + 1 < L) pack_row(xg, xp);
     }
     // ---- final LayerNorm (folded into the classifier) + Linear(D, 2) + log-softmax (self_attention.py:26-28)
-    float z0 = 0.0f, z1 = 0.0f;
-#pragma unroll
-    for (int Gq = 0; Gq < 16; ++Gq) {
-        const f32x4 c0 = ld4(lwc + 8 * Gq + 4 * h), c1 = ld4(lwc + D + 8 * Gq + 4 * h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            z0 = __builtin_fmaf(xg[Gq][e], c0[e], z0);
-            z1 = __builtin_fmaf(xg[Gq][e], c1[e], z1);
-        }
-    }
-    z0 = half_sum(z0) + lwc[2 * D];
-    z1 = half_sum(z1) + lwc[2 * D + 1];
-    const float mx = fmaxf(z0, z1);
-    const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
-    if (h == 0 && valid) *reinterpret_cast<f32x2*>(out + row * 2) = f32x2{z0 - lse, z1 - lse};
+    const f32x2 lp = classify_rows(xg, lwc, lwc + 2 * D, h);
+    if (h == 0 && valid) *reinterpret_cast<f32x2*>(out + row * 2) = lp;
 #ifdef SAVAD_TIMING
     SAVAD_PACC(0);
     if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -378,10 +361,7 @@ __global__ __launch_bounds__(256, 1) void packed_forward_kernel_bf16_ns(const fl
     const size_t row = valid ? (size_t)seq * T + t_frame : 0;
     bool keyok[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int jk = 8 * (r >> 2) + 4 * h + (r & 3);
-        keyok[r] = (jk < G * T) && (jk / T == m / T) && (blk * G + jk / T < B);
-    }
+    for (int r = 0; r < 16; ++r) keyok[r] = packed_key_ok(B, T, blk, m, acc_row(r, h));
     // ---- input Linear + positional encoding: this wave's 32 features.  Every global load of the prologue is requested before the
     // first use of any (the features, the input weights' fragments, bias and PE rows, then the biases and the classifier for LDS).
     // (scripts/ubench/phase_timing_packed_bf16_ns.py: the prologue is 10 k of the forward's 57-60 k cycles either way -- kernel
@@ -616,21 +596,8 @@ __global__ __launch_bounds__(256, 1) void packed_forward_kernel_bf16_ns(const fl
     // ---- final LayerNorm (folded into the classifier) + Linear(D, 2) + log-softmax
     rows_ln(xb0, own, xg, xp, false);
     if (w == 0) {
-        float z0 = 0.0f, z1 = 0.0f;
-#pragma unroll
-        for (int Gq = 0; Gq < 16; ++Gq) {
-            const f32x4 c0 = ld4(lwc + 8 * Gq + 4 * h), c1 = ld4(lwc + D + 8 * Gq + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                z0 = __builtin_fmaf(xg[Gq][e], c0[e], z0);
-                z1 = __builtin_fmaf(xg[Gq][e], c1[e], z1);
-            }
-        }
-        z0 = half_sum(z0) + lwc[2 * D];
-        z1 = half_sum(z1) + lwc[2 * D + 1];
-        const float mx = fmaxf(z0, z1);
-        const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
-        if (h == 0 && valid) *reinterpret_cast<f32x2*>(out + row * 2) = f32x2{z0 - lse, z1 - lse};
+        const f32x2 lp = classify_rows(xg, lwc, lwc + 2 * D, h);
+        if (h == 0 && valid) *reinterpret_cast<f32x2*>(out + row * 2) = lp;
     }
     SAVAD_STAMP(52);
 }

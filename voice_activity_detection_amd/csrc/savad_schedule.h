@@ -8,6 +8,7 @@
 #include <stddef.h>
 
 #include "../../include/savad.h"
+#include "savad_dims.h"
 
 // ---- experiment-build knobs (-D on the compile line; the product is built with the defaults)
 #ifndef SAVAD_INPUT_PERSISTENT
@@ -28,20 +29,6 @@
 
 namespace savad {
 namespace sched {
-
-// ---- sizes the layouts need, restated from the kernel headers (savad.hip static_asserts every one against its origin)
-constexpr int D = 128;                       // savad::D
-constexpr int TILE = 32;                     // savad::TILE
-constexpr int F32_MAX_LAYERS = 8;            // savad::PACKED_MAX_LAYERS
-constexpr int BF16_MAX_LAYERS = 6;           // bf::PACKED_BF16_MAX_LAYERS
-constexpr int F32S_MAX_LAYERS = 3;           // fs::PACKED_F32S_MAX_LAYERS
-constexpr int BF_BLK_BYTES = 8 * 1024;       // bf::BLK_BYTES
-constexpr int BF_HBLK_FLOATS = 32 * D;       // bf::HBLK_FLOATS
-constexpr int BF_HRES_BYTES = 2;             // sizeof(bf::hres_t)
-constexpr int FS_BLK3_BYTES = 8 * 3 * 1024;  // fs::BLK3_BYTES
-constexpr int FS_HBLK_BYTES = 32 * D * 4;    // fs::HBLK_BYTES
-constexpr int PW_GRID = 256;                 // bf::PW_GRID
-constexpr size_t GEN_SCORE_CAP = (size_t)32 << 20;  // gen::SCORE_CAP (floats: 128 MiB of scores per attention pass)
 
 // what a handle's settings contribute to the schedule (savad.hip: knobs_of)
 struct Knobs {
@@ -136,7 +123,7 @@ inline bool single_bf16_applies(const Knobs& m, int T) {
     // row_mode 0 (automatic) and 4: picked by the number of blocks; 5 - 7: a fixed variant (launch_single; tuning
     // knobs at T <= 32, where the persistent attention kernel that 5 selects for long sequences does not exist); 1 - 3 keep
     // the per-layer launches (the cross-check of the tests)
-    return T <= 32 && m.num_layers <= BF16_MAX_LAYERS && (m.row_mode == 0 || m.row_mode >= 4);
+    return T <= 32 && m.num_layers <= bf::PACKED_BF16_MAX_LAYERS && (m.row_mode == 0 || m.row_mode >= 4);
 }
 inline int single_bf16_variant(const Knobs& m, long nblk) {
     // variant: row_mode 5 = 8-wave workgroups, 6 = 4 waves + 4 that move the weight stream through a 4-slot ring, 7 = 4 waves +
@@ -154,7 +141,7 @@ inline bool single_f32s_applies(const Knobs& m, int B, int T) {
     // row_mode 0 (automatic) and 4: the single launch in the variant the number of blocks suggests (launch_single);
     // 5 - 7: the wave-per-block variant, 8: the latency variant (one block per workgroup); 1 - 3 keep the per-layer launches
     // (the cross-check of the tests).  SAVAD_F32S_PACKED_MIN_BLOCKS > 0 (experiment builds): exact-fp32 kernels below that many blocks
-    if (T > 32 || m.num_layers > F32S_MAX_LAYERS) return false;
+    if (T > 32 || m.num_layers > fs::PACKED_F32S_MAX_LAYERS) return false;
     const long nblk = packed_blocks(B, T);
     return m.row_mode >= 4 || (m.row_mode == 0 && nblk >= SAVAD_F32S_PACKED_MIN_BLOCKS);
 }
@@ -189,7 +176,7 @@ inline bool f32s_uses_exact_fp32(const Knobs& m, int B, int T) {
 inline bool pw_pays(bool ks_tail /* key-split tail items (0.55 of a full item) or ordinary ones (a full item's time) */, int Bq, int Tq) {
     const int QBq = (Tq + 31) / 32, NGFq = QBq >> 3, TQq = QBq & 7;
     if (NGFq == 0) return false;
-    const int wg = PW_GRID / 8;
+    const int wg = bf::PW_GRID / 8;
     auto ff1 = [](int x) { return __builtin_ctz((unsigned)x); };
     const int t0 = ff1(NGFq) < ff1(wg) ? ff1(NGFq) : ff1(wg), sh = ff1(wg) - t0, mask = (1 << t0) - 1;
     const int S = (Bq + 7) / 8;  // sequences of the fullest XCD
@@ -267,7 +254,7 @@ inline void plan_f32(ForwardPlan& w, const Knobs& m, int B, int T, long xbs_in) 
     const bool one_launch = tiles_packed <= 1024 &&
                             (tiles_dense > 512 || 92 * ((tiles_packed + 255) / 256) <= 45 + 110 * ((tiles_dense + 255) / 256));
     w.nblk = (int)tiles_packed;
-    if (T <= 32 && m.num_layers <= F32_MAX_LAYERS && (m.row_mode == 4 || (m.row_mode == 0 && one_launch)))
+    if (T <= 32 && m.num_layers <= PACKED_MAX_LAYERS && (m.row_mode == 4 || (m.row_mode == 0 && one_launch)))
         w.form = SINGLE;
     else if (w.fused)
         w.form = FUSED;
@@ -336,8 +323,8 @@ inline void plan_bf16(ForwardPlan& p, const Knobs& m, int B, int T, bool x_is_bf
         }
     }
     Bump b;
-    p.h = b.take((size_t)p.nblk_pad * BF_HBLK_FLOATS * BF_HRES_BYTES);
-    const size_t fb = (size_t)(p.nblk_pad + 1) * BF_BLK_BYTES;  // +1 block: a 2-block key stage may over-read
+    p.h = b.take((size_t)p.nblk_pad * bf::HBLK_FLOATS * bf::HRES_BYTES);
+    const size_t fb = (size_t)(p.nblk_pad + 1) * bf::BLK_BYTES;  // +1 block: a 2-block key stage may over-read
     p.q = b.take(fb);
     p.k = b.take(fb);
     p.v = b.take(fb);
@@ -370,8 +357,8 @@ inline void plan_f32s(ForwardPlan& p, const Knobs& m, int B, int T, long xbs_in)
         p.fold_v = T > 32;
     }
     Bump b;
-    p.h = b.take((size_t)p.nblk_pad * FS_HBLK_BYTES);
-    const size_t fb = (size_t)p.nblk_pad * FS_BLK3_BYTES;
+    p.h = b.take((size_t)p.nblk_pad * fs::HBLK_BYTES);
+    const size_t fb = (size_t)p.nblk_pad * fs::BLK3_BYTES;
     size_t* slots[6] = {&p.q, &p.k, &p.v, &p.q2, &p.k2, &p.v2};
     for (size_t* s : slots) *s = b.take(fb);
     p.xpad = b.off;
@@ -394,12 +381,12 @@ inline void plan_generic(ForwardPlan& p, const Knobs& m, int B, int T, long xbs_
     p.ctx = take(md);
     p.ff = take(4 * md);
     const size_t tt = (size_t)T * T;
-    if (force_query_tiles > 1 || tt > GEN_SCORE_CAP) {
+    if (force_query_tiles > 1 || tt > gen::SCORE_CAP) {
         p.cb = 1;
-        long tq = force_query_tiles > 1 ? (T + force_query_tiles - 1) / force_query_tiles : (long)(GEN_SCORE_CAP / T);
+        long tq = force_query_tiles > 1 ? (T + force_query_tiles - 1) / force_query_tiles : (long)(gen::SCORE_CAP / T);
         p.tq = (int)(tq < 1 ? 1 : (tq > T ? T : tq));
     } else {
-        size_t cb = GEN_SCORE_CAP / tt;
+        size_t cb = gen::SCORE_CAP / tt;
         cb = cb > 65535 ? 65535 : cb;  // cb is a grid.z of the score GEMMs (HIP: at most 65535); the b0 loop takes the rest
         p.cb = (int)(cb > (size_t)B ? (size_t)B : cb);
         p.tq = T;
@@ -452,7 +439,7 @@ inline PredictPlan plan_predict(const Knobs& m, int N, int half, int jump, int c
     else if (p->f32s)   // (the fp32s single launch takes any number of windows)
         p->windowed = true;
     else
-        p->windowed = !m.generic && p->W <= 32 && m.num_layers <= F32_MAX_LAYERS && m.FP == F &&
+        p->windowed = !m.generic && p->W <= 32 && m.num_layers <= PACKED_MAX_LAYERS && m.FP == F &&
                       (m.row_mode == 4 || (m.row_mode == 0 && p->n_items <= 1024 * (32 / p->W)));
     p->family = m.generic ? GENERIC : m.precision == 1 ? BF16 : p->f32s ? F32S : F32;
     // chunk-sized forwards write their log-probs at logp + first*W*2 floats and savad_forward wants 16-byte aligned

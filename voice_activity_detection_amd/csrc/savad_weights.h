@@ -10,14 +10,10 @@
 #include <string>
 #include <vector>
 
+#include "savad_dims.h"
+
 namespace savad {
 namespace weights {
-
-// ---- sizes the layouts need, restated from savad_kernels.h (savad.hip static_asserts every one against its origin)
-constexpr int D = 128;                  // savad::D
-constexpr int DFF = 4 * D;              // savad::DFF
-constexpr int LBIAS = DFF + 5 * D;      // savad::LBIAS: b1 | b2 | bqkv | bo
-constexpr int FRAG_LAYER = 48 * 4096;   // savad::FRAG_LAYER (floats)
 
 struct Param {
     std::string key;
