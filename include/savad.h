@@ -175,7 +175,8 @@ int savad_window_offsets(int half, int jump, int32_t* offsets);
 
 /* Replaces the per-window python gather loop (vad/predictor.py:182-220): for item i in
  * [first, first+count): windows[i-first][w][:] = feature[half+i+off[w]][:], positions[i-first][w] =
- * half+i+off[w].  feature [N,F] fp32, windows [count,W,F] fp32, positions [count,W] int64 (may be NULL). */
+ * half+i+off[w].  feature [N,F] fp32, windows [count,W,F] fp32, positions [count,W] int64 (may be NULL).  With F a multiple of 4
+ * the rows move in 16-byte pieces: feature and windows 16-byte aligned; any other F goes one float at a time. */
 int savad_gather_windows(const float* feature, int N, int F, int half, int jump, int first, int count, float* windows,
                          int64_t* positions, void* stream);
 
@@ -205,7 +206,9 @@ int savad_boost(const float* logp, const int64_t* positions, int count, int N, i
  * window w covers frames [hop*w, hop*w+T) of feature[N,F], zero-padded past N; the number of windows
  * is savad_stream_window_count = N <= T ? 1 : ceil((N-T)/hop) + 1.  After savad_forward on the
  * windows, savad_overlap_merge gives probs[n] = mean over the windows covering frame n of
- * softmax(logp[w][n-hop*w])[1] (mirrors the averaging of vad/predictor.py:95). */
+ * softmax(logp[w][n-hop*w])[1] (mirrors the averaging of vad/predictor.py:95).  savad_gather_strided copies the windows
+ * [first, first + count) in 16-byte pieces (F a multiple of 4; feature and windows 16-byte aligned); logp is read as 8-byte
+ * (log p0, log p1) pairs here and in savad_boost. */
 int savad_stream_window_count(int N, int T, int hop);
 int savad_gather_strided(const float* feature, int N, int F, int T, int hop, int first, int count, float* windows,
                          void* stream);

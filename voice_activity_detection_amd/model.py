@@ -325,9 +325,21 @@ class SelfAttentiveVAD(nn.Module):
         lib = self._prepare_call(device)
         ws = self._workspace_for(self._workspace_bytes(lib, B, T), device)
         stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(lib.savad_forward_ex(self._handle, ctypes.c_void_p(x.data_ptr()), x_dtype, B, T,
-                                        ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+        x_ptr, out_ptr, tmp = x.data_ptr(), out.data_ptr(), None
+        if (x_ptr | out_ptr) & 15:
+            # the 16-byte alignment of x and out is the C ABI's rule (include/savad.h), not the module's: a contiguous view that starts
+            # off a 16-byte boundary (batch[1:] of 7 x 13 MFCC windows, a slice of a larger result) is cloned / computed into a temporary
+            if x_ptr & 15:
+                x = x.clone()
+                x_ptr = x.data_ptr()
+            if out_ptr & 15:
+                tmp = torch.empty_like(out)
+                out_ptr = tmp.data_ptr()
+        _lib.check(lib.savad_forward_ex(self._handle, ctypes.c_void_p(x_ptr), x_dtype, B, T,
+                                        ctypes.c_void_p(out_ptr), ctypes.c_void_p(ws.data_ptr()),
                                         ws.numel(), ctypes.c_void_p(stream)))
+        if tmp is not None:
+            out.copy_(tmp)
 
     @torch.no_grad()
     def forward_windows(self, feature: Tensor, T: int, hop: int, first: int, count: int, out: Optional[Tensor] = None) -> Tensor:
@@ -347,6 +359,8 @@ class SelfAttentiveVAD(nn.Module):
             out = torch.empty((count, T, 2), dtype=torch.float32, device=device)
         elif tuple(out.shape) != (count, T, 2) or out.dtype != torch.float32 or out.device != device or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous float32 [{count}, {T}, 2] tensor on {device}")
+        if feature.data_ptr() % 16:   # (the in-place reads and savad_gather_strided move 16-byte pieces: a misaligned view is cloned)
+            feature = feature.clone()
         if T <= 32 or F % 16 or self.d_model != 128:
             # savad_forward_strided reads windows in place only where a kernel takes the sequence stride (T > 32, no feature padding,
             # the d_model = 128 kernels); everything else goes through one gathered copy of the windows and the plain forward
@@ -359,17 +373,17 @@ class SelfAttentiveVAD(nn.Module):
                     stream = torch.cuda.current_stream(device).cuda_stream
                     _lib.check(lib.savad_gather_strided(ctypes.c_void_p(feature.data_ptr()), N, F, T, hop, first, count,
                                                         ctypes.c_void_p(win.data_ptr()), ctypes.c_void_p(stream)))
-            if out.data_ptr() % 16 == 0:
-                return self(features=win, out=out)
-            out.copy_(self(features=win))   # (a slice of a larger result that starts off a 16-byte boundary: odd T x odd window count)
-            return out
+            return self(features=win, out=out)   # (forward takes an `out` off a 16-byte boundary: odd T x odd window count)
+        dst = out if out.data_ptr() % 16 == 0 else torch.empty_like(out)
         with torch.cuda.device(device):
             lib = self._prepare_call(device)
             ws = self._workspace_for(self._workspace_bytes(lib, count, T), device)
             stream = torch.cuda.current_stream(device).cuda_stream
             x = feature.data_ptr() + 4 * first * hop * F
-            _lib.check(lib.savad_forward_strided(self._handle, ctypes.c_void_p(x), 0, count, T, hop * F, ctypes.c_void_p(out.data_ptr()),
+            _lib.check(lib.savad_forward_strided(self._handle, ctypes.c_void_p(x), 0, count, T, hop * F, ctypes.c_void_p(dst.data_ptr()),
                                                  ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream)))
+        if dst is not out:
+            out.copy_(dst)
         return out
 
     @torch.no_grad()
@@ -383,6 +397,8 @@ class SelfAttentiveVAD(nn.Module):
         feat = feature.detach().float().contiguous()
         if feat.dim() != 2 or feat.shape[1] != self.feature_size:
             raise ValueError(f"feature must be [N, {self.feature_size}], got {tuple(feat.shape)}")
+        if feat.data_ptr() % 16:   # (savad_predict_probabilities wants the matrix 16-byte aligned; the module takes any tensor)
+            feat = feat.clone()
         N = feat.shape[0]
         lib = _lib.load()
         W = lib.savad_window_offsets(int(half), int(jump), None)
