@@ -201,6 +201,41 @@ int savad_predict_probabilities(savad_handle h, const float* feature, int N, int
 int savad_boost(const float* logp, const int64_t* positions, int count, int N, int W, float* boosted_ws, float* probs,
                 float* mean, void* stream);
 
+/* MANY CLIPS IN ONE CALL.  The reference's windows are independent sequences, so the windows of several recordings can share
+ * forwards without masks or padding -- as long as no window is cut across two recordings and every recording keeps its own
+ * 0.5 placeholders.  A CLIP TABLE names the recordings inside one concatenated feature matrix [rows, F]:
+ *   clip_first [C + 1] int32, non-decreasing, clip_first[0] = 0: clip c owns rows [clip_first[c], clip_first[c + 1]); rows =
+ *   clip_first[C].  Clip c has n_c = max(0, its rows - 2 half) windows (vad/predictor.py:169); an empty clip and a clip too
+ *   short for a window are legal.  The windows of all clips in clip order are the global ITEMS [0, sum n_c).
+ * Every entry that launches takes the table twice: clip_first_host (HOST) is validated and planned from, clip_first (DEVICE, the same values)
+ * is what the kernels read -- the library uploads nothing, allocates nothing and never synchronises; kernels go to `stream`.
+ * Refused before anything is launched: C < 1, clip_first[0] != 0 or a decreasing table (SAVAD_E_INVALID); a window longer than
+ * 64 frames, or sum n_c * W above 2^31 - 1 (SAVAD_E_UNSUPPORTED; the int32 table itself bounds rows by 2^31 - 1).
+ *   savad_gather_windows_batch   savad_gather_windows for items [first, first + count): windows[i - first][w][:] =
+ *       feature[clip_first[c] + half + local + off[w]][:] for item i = the local-th window of clip c; positions [count, W] int64
+ *       (may be NULL) hold that row of the concatenated matrix.  items_first [C + 1] int32 (DEVICE) is written by the call: the
+ *       exclusive prefix sum of n_c, which maps an item to its clip.  F a multiple of 4: 16-byte pieces, feature and windows
+ *       16-byte aligned; any other F goes one float at a time.
+ *   savad_boost_batch            the boosted prediction of every clip, read as a gather (no [rows, W, 2] scratch array, no
+ *       positions): logp [sum n_c, W, 2] in item order -> probs [rows, W], mean [rows] (may be NULL); slot (n, w) of a clip is
+ *       filled by the CLIP's window local - half - off[w] when that exists and is exactly 0.5 otherwise.  With one clip: the bits
+ *       of savad_boost.  items_first as above (written by the call).
+ *   savad_predict_probabilities_batch   savad_predict_probabilities for every clip of the table in one call: probs [rows, W] and
+ *       mean [rows] (may be NULL) hold clip c's result in its rows.  The items run `chunk` (made even; at most sum n_c) per
+ *       forward, whatever clips they belong to; the windows are always copied and each chunk is one savad_forward, in every
+ *       precision and row mode: the bits of savad_gather_windows_batch + savad_forward per chunk + savad_boost_batch.  feature and
+ *       workspace 16-byte aligned; workspace from savad_predict_batch_workspace_bytes (HOST arithmetic: it takes the host table
+ *       only) for the same table, half, jump, chunk and the handle's current settings. */
+int savad_gather_windows_batch(const float* feature, const int32_t* clip_first_host, const int32_t* clip_first, int C, int F, int half,
+                               int jump, int first, int count, int32_t* items_first, float* windows, int64_t* positions, void* stream);
+int savad_boost_batch(const float* logp, const int32_t* clip_first_host, const int32_t* clip_first, int C, int half, int jump,
+                      int32_t* items_first, float* probs, float* mean, void* stream);
+int savad_predict_batch_workspace_bytes(savad_handle h, const int32_t* clip_first_host, int C, int half, int jump, int chunk,
+                                        size_t* bytes);
+int savad_predict_probabilities_batch(savad_handle h, const float* feature, const int32_t* clip_first_host, const int32_t* clip_first,
+                                      int C, int half, int jump, int chunk, float* probs, float* mean, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+
 /* Streaming long-form mode (BASELINE.json configs[4]: sliding windows T=800, hop=400; NOT a mode of
  * the reference, whose predictor only cuts 7-frame windows -- the rule below is this build's):
  * window w covers frames [hop*w, hop*w+T) of feature[N,F], zero-padded past N; the number of windows

@@ -46,6 +46,9 @@ def main(argv=None) -> int:
     p.add_argument("--device-post", action="store_true",
                    help="threshold, trim, frame -> sample conversion, split and segment extraction on the GPU (same results; only "
                         "the segments return to the host): pays for long recordings, a short clip is launch-bound")
+    p.add_argument("--batch-chunks", action="store_true",
+                   help="run the --split-max-seconds chunks of the recording through one batched prediction (one feature matrix, one "
+                        "library call for the windows of all chunks) instead of one call per chunk: same results to fp32 rounding")
     e = sub.add_parser("evaluate", help="frame metrics over a labelled data list (vad/evaluate.py:20-29)")
     e.add_argument("eval_path", type=Path)
     e.add_argument("checkpoint_path", type=Path)
@@ -79,7 +82,8 @@ def main(argv=None) -> int:
     from .predictor import VADFromScratchPredictor, VADPredictParameters
 
     predictor = VADFromScratchPredictor.from_checkpoint(args.checkpoint_path, args.device, extended_front_end=args.extended_front_end,
-                                                        device_ingest=args.device_ingest, device_post=args.device_post)
+                                                        device_ingest=args.device_ingest, device_post=args.device_post,
+                                                        batch_chunks=args.batch_chunks)
     predictor.model.precision, predictor.model.batch_invariant, predictor.graph = args.precision, args.batch_invariant, args.graph
     voice_activity = predictor.predict_from_path(
         args.audio_path,

@@ -6,6 +6,7 @@
 // the order of the kernel headers is the order of the kernels in the code object
 #include "savad_kernels.h"
 #include "savad_aux_kernels.h"
+#include "savad_batch_kernels.h"
 #include "savad_kernels_bf16.h"
 #include "savad_attn_pw_bf16.h"
 #include "savad_packed_bf16.h"
@@ -1154,6 +1155,121 @@ SAVAD_EXPORT int savad_predict_probabilities(savad_handle m, const float* featur
         }
     }
     hipLaunchKernelGGL(boost_gather_kernel, dim3(grid_for(N, 2048)), dim3(256), 0, st, logp, p.n_items, N, half, wo, probs, mean);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+// ---- many clips in one call (savad_batch_kernels.h; savad_schedule.h: plan_predict_batch) --------------------
+namespace {
+// the HOST table validated and counted; the refusal's message when it is not a clip table
+int clip_table(const int32_t* clip_first_host, int C, int half, int jump, sched::ClipTotals* t) {
+    *t = sched::clip_totals(clip_first_host, C, half, jump);
+    return t->err ? fail(t->err, "%s", t->msg) : SAVAD_OK;
+}
+
+void launch_items_scan(const int32_t* clip_first, int C, int half, int32_t* items_first, hipStream_t st) {
+    hipLaunchKernelGGL(clip_items_scan_kernel, dim3(1), dim3(BATCH_SCAN_THREADS), 0, st, clip_first, C, half, items_first);
+}
+
+// items [first, first + count) of a table whose items_first the device already holds
+void launch_gather_batch(const float* feature, int F, const int32_t* clip_first, const int32_t* items_first, int C, int half, int first,
+                         int count, const WindowOffsets& wo, float* windows, int64_t* positions, hipStream_t st) {
+    const int tiles = (count + BATCH_GATHER_ITEMS - 1) / BATCH_GATHER_ITEMS;
+    const dim3 grid(tiles < 4096 ? tiles : 4096);
+    if (F % 4)
+        hipLaunchKernelGGL(gather_windows_batch_kernel<false>, grid, dim3(256), 0, st, feature, F, clip_first, items_first, C, half, first,
+                           count, wo, windows, positions);
+    else
+        hipLaunchKernelGGL(gather_windows_batch_kernel<true>, grid, dim3(256), 0, st, feature, F, clip_first, items_first, C, half, first,
+                           count, wo, windows, positions);
+}
+
+int plan_predict_batch(savad_model* m, const int32_t* clip_first_host, int C, int half, int jump, int chunk, sched::PredictBatchPlan* p) {
+    *p = sched::plan_predict_batch(knobs_of(m), clip_first_host, C, half, jump, chunk);
+    if (p->err) return fail(p->err, "%s", p->msg);
+    if ((double)p->chunk * p->W * D >= 2.0e9)   // the chunk-sized forward's own limit (savad_workspace_bytes)
+        return fail(SAVAD_E_UNSUPPORTED, "B*T=%ld rows exceed the 32-bit tile index range", (long)p->chunk * p->W);
+    return SAVAD_OK;
+}
+}  // namespace
+
+SAVAD_EXPORT int savad_gather_windows_batch(const float* feature, const int32_t* clip_first_host, const int32_t* clip_first, int C, int F,
+                                            int half, int jump, int first, int count, int32_t* items_first, float* windows,
+                                            int64_t* positions, void* stream) {
+    sched::ClipTotals t;
+    int rc = clip_table(clip_first_host, C, half, jump, &t);
+    if (rc) return rc;
+    if (F <= 0 || first < 0 || count < 0) return fail(SAVAD_E_INVALID, "F=%d first=%d count=%d", F, first, count);
+    if ((long)first + count > t.n_items)
+        return fail(SAVAD_E_INVALID, "items [%d,%ld) reach outside the %d windows of the clips", first, (long)first + count, t.n_items);
+    if (count == 0) return SAVAD_OK;
+    if (!feature || !clip_first || !items_first || !windows) return fail(SAVAD_E_INVALID, "null pointer");
+    if (F % 4 == 0 && (((uintptr_t)feature | (uintptr_t)windows) & 15))
+        return fail(SAVAD_E_INVALID, "feature and windows must be 16-byte aligned when F is a multiple of 4");
+    WindowOffsets wo;
+    if ((rc = window_offsets(half, jump, &wo))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    launch_items_scan(clip_first, C, half, items_first, st);
+    launch_gather_batch(feature, F, clip_first, items_first, C, half, first, count, wo, windows, positions, st);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_boost_batch(const float* logp, const int32_t* clip_first_host, const int32_t* clip_first, int C, int half, int jump,
+                                   int32_t* items_first, float* probs, float* mean, void* stream) {
+    sched::ClipTotals t;
+    int rc = clip_table(clip_first_host, C, half, jump, &t);
+    if (rc) return rc;
+    if (t.rows == 0) return SAVAD_OK;
+    if (!clip_first || !items_first || !probs || (t.n_items > 0 && !logp)) return fail(SAVAD_E_INVALID, "null pointer");
+    WindowOffsets wo;
+    if ((rc = window_offsets(half, jump, &wo))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    launch_items_scan(clip_first, C, half, items_first, st);
+    hipLaunchKernelGGL(boost_gather_batch_kernel, dim3(grid_for(t.rows, 2048)), dim3(256), 0, st, logp, clip_first, (const int32_t*)items_first,
+                       C, t.rows, half, wo, probs, mean);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_predict_batch_workspace_bytes(savad_handle m, const int32_t* clip_first_host, int C, int half, int jump, int chunk,
+                                                     size_t* bytes) {
+    if (!m || !bytes) return fail(SAVAD_E_INVALID, "null argument");
+    sched::PredictBatchPlan p;
+    int rc = plan_predict_batch(m, clip_first_host, C, half, jump, chunk, &p);
+    if (rc) return rc;
+    *bytes = p.total;
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_predict_probabilities_batch(savad_handle m, const float* feature, const int32_t* clip_first_host,
+                                                   const int32_t* clip_first, int C, int half, int jump, int chunk, float* probs, float* mean,
+                                                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (!m) return fail(SAVAD_E_INVALID, "null handle");
+    sched::PredictBatchPlan p;
+    int rc = plan_predict_batch(m, clip_first_host, C, half, jump, chunk, &p);
+    if (rc) return rc;
+    if (p.rows == 0) return SAVAD_OK;
+    if (!feature || !clip_first || !probs || !workspace) return fail(SAVAD_E_INVALID, "null tensor pointer");
+    if (((uintptr_t)feature | (uintptr_t)workspace) & 15) return fail(SAVAD_E_INVALID, "feature and workspace must be 16-byte aligned");
+    if (workspace_bytes < p.total) return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
+    hipStream_t st = (hipStream_t)stream;
+    const int F = m->cfg.feature_size, W = p.W;
+    WindowOffsets wo;
+    if ((rc = window_offsets(half, jump, &wo))) return rc;
+    char* ws = (char*)workspace;
+    int32_t* items_first = (int32_t*)(ws + p.items_first);
+    float* logp = (float*)(ws + p.logp);
+    float* win = (float*)(ws + p.windows);
+    launch_items_scan(clip_first, C, half, items_first, st);
+    for (int first = 0; first < p.n_items; first += p.chunk) {
+        const int count = p.n_items - first < p.chunk ? p.n_items - first : p.chunk;
+        launch_gather_batch(feature, F, clip_first, items_first, C, half, first, count, wo, win, nullptr, st);
+        HIP_TRY(hipGetLastError());
+        if ((rc = savad_forward(m, win, count, W, logp + (size_t)first * W * 2, ws + p.fwd, p.fwd_bytes, stream))) return rc;
+    }
+    hipLaunchKernelGGL(boost_gather_batch_kernel, dim3(grid_for(p.rows, 2048)), dim3(256), 0, st, logp, clip_first, (const int32_t*)items_first, C,
+                       p.rows, half, wo, probs, mean);
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }

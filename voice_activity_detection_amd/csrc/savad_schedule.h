@@ -472,5 +472,84 @@ inline PredictPlan plan_predict(const Knobs& m, int N, int half, int jump, int c
     return pp;
 }
 
+// The schedule of savad_predict_probabilities_batch: C clips in one concatenated feature matrix, clip c = rows [clip_first[c],
+// clip_first[c + 1]) with n_c = max(0, rows - 2 half) windows of its own (savad_batch_kernels.h).
+struct PredictBatchPlan {
+    int err = SAVAD_OK;
+    const char* msg = nullptr;
+    int W = 0, C = 0, rows = 0, n_items = 0, chunk = 0;  // rows = the matrix's, n_items = the sum of n_c: global items [0, n_items), `chunk` per forward
+    size_t items_first = 0, logp = 0, windows = 0, fwd = 0, total = 0;  // byte offsets into the workspace
+    size_t fwd_bytes = 0;                                               // the ForwardPlan total of a chunk-sized forward
+};
+
+constexpr long BATCH_INDEX_LIMIT = 2147483647L;  // rows of the matrix (an int32 table holds no more) and n_items * W: 32-bit indices
+
+// what the HOST copy of a clip table says: validated (C >= 1, clip_first[0] = 0, non-decreasing, the window geometry, the index
+// limits) and counted
+struct ClipTotals {
+    int err = SAVAD_OK;
+    const char* msg = nullptr;
+    int W = 0, rows = 0, n_items = 0;
+};
+inline ClipTotals clip_totals(const int32_t* clip_first, int C, int half, int jump) {
+    ClipTotals t;
+    auto refuse = [&](int err, const char* msg) {
+        t.err = err;
+        t.msg = msg;
+        return t;
+    };
+    if (!clip_first || C < 1) return refuse(SAVAD_E_INVALID, "clip table: at least one clip");
+    if (half < 0 || jump <= 0) return refuse(SAVAD_E_INVALID, "half must not be negative, jump must be positive");
+    const long Wl = window_count(half, jump);
+    if (Wl > 64) return refuse(SAVAD_E_UNSUPPORTED, "window longer than 64 frames");
+    t.W = (int)Wl;
+    if (clip_first[0] != 0) return refuse(SAVAD_E_INVALID, "clip table: clip_first[0] must be 0");
+    long items = 0;
+    for (int c = 0; c < C; ++c) {
+        const long n = (long)clip_first[c + 1] - clip_first[c];
+        if (n < 0) return refuse(SAVAD_E_INVALID, "clip table: clip_first must not decrease");
+        items += n - 2L * half > 0 ? n - 2L * half : 0;
+    }
+    t.rows = clip_first[C];  // (an int32 table cannot name more than BATCH_INDEX_LIMIT rows)
+    if (items * t.W > BATCH_INDEX_LIMIT) return refuse(SAVAD_E_UNSUPPORTED, "windows x frames of all clips exceed the 32-bit index range");
+    t.n_items = (int)items;
+    return t;
+}
+
+// The plan of the one call from the HOST copy of the table: validates it, counts the items and lays the
+// workspace out: items_first [C + 1] int32 | logp [n_items, W, 2] | windows [chunk, W, F] | the chunk-sized forward's workspace.  The
+// windows are always copied and every chunk is a savad_forward of its own, in every precision and row mode (the packed kernels
+// read windows in place at ONE row pitch; a chunk of a ragged matrix has none).  The chunk rule is plan_predict's: even, at most n_items.
+inline PredictBatchPlan plan_predict_batch(const Knobs& m, const int32_t* clip_first, int C, int half, int jump, int chunk) {
+    PredictBatchPlan p;
+    const ClipTotals t = clip_totals(clip_first, C, half, jump);
+    p.err = t.err;
+    p.msg = t.msg;
+    if (!p.err && chunk <= 0) {
+        p.err = SAVAD_E_INVALID;
+        p.msg = "chunk must be positive";
+    }
+    if (p.err) return p;
+    p.W = t.W;
+    p.C = C;
+    p.rows = t.rows;
+    p.n_items = t.n_items;
+    const long even = (long)chunk + (chunk & 1);
+    p.chunk = even <= p.n_items ? (int)even : (p.n_items > 0 ? p.n_items : 1);
+    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
+    size_t off = 0;
+    p.items_first = off;
+    off += up(sizeof(int32_t) * ((size_t)C + 1));
+    p.logp = off;
+    off += up(sizeof(float) * (size_t)(p.n_items > 0 ? p.n_items : 1) * p.W * 2);
+    p.windows = off;
+    off += up(sizeof(float) * (size_t)p.chunk * p.W * m.feature_size);
+    p.fwd = off;
+    p.fwd_bytes = plan_forward(m, p.chunk, p.W, false, 0).total;
+    off += up(p.fwd_bytes);
+    p.total = off;
+    return p;
+}
+
 }  // namespace sched
 }  // namespace savad

@@ -327,9 +327,10 @@ def load_audio_device(path, device="cuda") -> torch.Tensor:
     return resample_to_16k_device(downmix_device(torch.from_numpy(raw).to(dev), channels), rate)
 
 
-def log_mel(audio, device="cuda") -> torch.Tensor:
+def log_mel(audio, device="cuda", out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """audio: 1-D float32 samples @16 kHz (numpy or tensor; int16 PCM is uploaded as it is and converted on the device) -> device
-    tensor [N, 80] float32, N = 1 + len // 160.
+    tensor [N, 80] float32, N = 1 + len // 160.  `out`: a contiguous float32 [N, 80] tensor on the device to write into (a clip's
+    slice of a concatenated matrix: predict_many) instead of a new one.
     (Host side kept thin on purpose: for a 10 s clip the two kernels take ~25 us, the Python around them used to
     take longer.)"""
     lib = _lib.load()
@@ -348,9 +349,12 @@ def log_mel(audio, device="cuda") -> torch.Tensor:
     idx = y.device.index if y.device.index is not None else torch.cuda.current_device()
     if idx != torch.cuda.current_device():
         with torch.cuda.device(idx):
-            return log_mel(y, y.device)
+            return log_mel(y, y.device, out)
     buf = torch.empty(ws_floats, dtype=torch.float32, device=y.device)
-    out = torch.empty((frames, 80), dtype=torch.float32, device=y.device)
+    if out is None:
+        out = torch.empty((frames, 80), dtype=torch.float32, device=y.device)
+    elif tuple(out.shape) != (frames, 80) or out.dtype != torch.float32 or out.device != y.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 [{frames}, 80] tensor on {y.device}")
     _lib.check(lib.savad_logmel(ctypes.c_void_p(y.data_ptr()), n, ctypes.c_void_p(buf.data_ptr()),
                                 ctypes.c_void_p(out.data_ptr()),
                                 ctypes.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)))

@@ -11,7 +11,6 @@ with numpy on the host.
 from __future__ import annotations
 
 import ctypes
-import math
 import os
 from collections import OrderedDict
 from dataclasses import dataclass
@@ -36,6 +35,13 @@ def window_offsets(half: int, jump: int) -> np.ndarray:
     if w < 0:
         _lib.check(w)
     return np.array(buf[:w], dtype=np.int64)
+
+
+def split_by_clip_pairs(result, table) -> list:
+    """(probs [sum N, W], mean [sum N]) -> [(probs of clip c, mean of clip c)]: views"""
+    from .clips import split_by_clip
+
+    return list(zip(split_by_clip(result[0], table), split_by_clip(result[1], table)))
 
 
 def _require_hip(device: torch.device):
@@ -85,7 +91,7 @@ class VADFromScratchPredictor:
 
     def __init__(self, model: SelfAttentiveVAD, device: torch.device, context: ContextResolution = ContextResolution(),
                  chunk_size: int = 16384, graph: bool = False, graph_max_seconds: float = 120.0, graph_cache: int = 8,
-                 front_end=None, device_ingest: bool = False, device_post: bool = False):
+                 front_end=None, device_ingest: bool = False, device_post: bool = False, batch_chunks: bool = False):
         """`graph=True` (not in the reference's signature): clip-sized inputs -- up to `graph_max_seconds` of audio -- run as a
         replayed HIP graph of the whole chain log-mel -> window gather -> forward -> boost, captured on first use per (length, model
         knobs) and re-captured when the weights change; at most `graph_cache` graphs are kept (least recently used goes).  For a 10 s
@@ -101,12 +107,17 @@ class VADFromScratchPredictor:
         fetches only the segments -- the host functions' results, bit for bit -- where the geometry allows it (a hop of a whole
         number of samples, at most 128 probabilities per frame); any other chunk takes the host code.  `post_stats` counts the
         chunks either way.  Pays for long recordings (the host builds float64 arrays of one element per sample); a short clip
-        is launch-bound."""
+        is launch-bound.
+        `batch_chunks=True`: predict() sends the `split_max_seconds` chunks of a recording through ONE batched prediction
+        (predict_many: every chunk's features into one matrix, one library call for the windows of all chunks) instead of one
+        call per chunk; the probabilities agree with the looped path to fp32 rounding (the forwards see other batches).  Off by
+        default."""
         from .features import SHIPPED_FRONT_END
 
         self.front_end = SHIPPED_FRONT_END if front_end is None else front_end
         self.device_ingest = bool(device_ingest)
         self.device_post = bool(device_post)
+        self.batch_chunks = bool(batch_chunks)
         self.post_stats = {"device": 0, "host": 0}   # chunks post-processed on the GPU / on the host
         self.graph, self.graph_max_seconds, self.graph_cache = bool(graph), float(graph_max_seconds), int(graph_cache)
         self._graphs: "OrderedDict[tuple, dict]" = OrderedDict()
@@ -170,7 +181,7 @@ class VADFromScratchPredictor:
 
     @classmethod
     def from_checkpoint(cls, checkpoint_path, device, trust_checkpoint: bool = False, extended_front_end: bool = False,
-                        device_ingest: bool = False, device_post: bool = False):
+                        device_ingest: bool = False, device_post: bool = False, batch_chunks: bool = False):
         """vad/predictor.py:264-280: a training checkpoint holds {"config": ..., "state_dict": ...} plus what
         ModelCheckpointer adds (epoch, global_step, monitor_metric, a `metrics` dict of numpy scalars, optimizer /
         scheduler / grad-scaler state: vad/training/checkpointers/model_checkpointer.py:97-110); the model size, the
@@ -179,7 +190,7 @@ class VADFromScratchPredictor:
         `extended_front_end=True` builds every feature_extractor config features.FrontEnd takes (the four transforms at any
         geometry within its limits, temporal differences); the default refuses all but the shipped one.  The shipped
         features are pinned by goldens and trained-weights AUC, the others by a restatement of librosa 0.8.0: opting in
-        acknowledges that.  `device_ingest`, `device_post`: as in the constructor."""
+        acknowledges that.  `device_ingest`, `device_post`, `batch_chunks`: as in the constructor."""
         ckpt = cls._load_checkpoint(checkpoint_path, trust_checkpoint)
         cfg = ckpt["config"]
 
@@ -210,7 +221,8 @@ class VADFromScratchPredictor:
             model.load_state_dict(ckpt["state_dict"])
             ctx = ContextResolution(get(cfg, "context_resolution", "context_window_half_frames"),
                                     get(cfg, "context_resolution", "context_window_jump_frames"))
-            predictor = cls(model.to(device).eval(), device, ctx, front_end=front, device_ingest=device_ingest, device_post=device_post)
+            predictor = cls(model.to(device).eval(), device, ctx, front_end=front, device_ingest=device_ingest, device_post=device_post,
+                            batch_chunks=batch_chunks)
             predictor.hop_ms, predictor.window_ms = front.hop_ms, front.window_ms  # vad/predictor.py:103-104
             return predictor
         tr = get(fe, "transform")
@@ -228,7 +240,7 @@ class VADFromScratchPredictor:
         model.load_state_dict(ckpt["state_dict"])
         ctx = ContextResolution(get(cfg, "context_resolution", "context_window_half_frames"),
                                 get(cfg, "context_resolution", "context_window_jump_frames"))
-        predictor = cls(model.to(device).eval(), device, ctx, device_ingest=device_ingest, device_post=device_post)
+        predictor = cls(model.to(device).eval(), device, ctx, device_ingest=device_ingest, device_post=device_post, batch_chunks=batch_chunks)
         predictor.hop_ms, predictor.window_ms = got["hop_ms"], got["window_ms"]  # vad/predictor.py:103-104
         return predictor
 
@@ -246,32 +258,101 @@ class VADFromScratchPredictor:
         """vad/predictor.py:77-157.  audio: float32 mono @16 kHz, a numpy array or a 1-D float32 tensor on the predictor's device
         (sliced and fed to the front-end where it is: no host round trip).  features_fn(chunk_audio) -> [N, F] overrides
         the GPU front-end (used by the parity tests to feed the reference's feature matrix)."""
+        from .clips import chunk_bounds
         from .features import SAMPLE_RATE
 
+        if self.batch_chunks:
+            return self.predict_many([audio], parameters, features_fn)[0]
         if not (isinstance(audio, torch.Tensor) and audio.device.type == "cuda" and audio.dtype == torch.float32 and audio.dim() == 1):
             audio = np.asarray(audio, dtype=np.float32)
-        duration_s = len(audio) / SAMPLE_RATE
-        num_chunks = math.ceil(duration_s / parameters.split_max_seconds) if parameters.split_max_seconds is not None else 1
-        adjusted = duration_s / num_chunks
+        adjusted, bounds = chunk_bounds(len(audio), SAMPLE_RATE, parameters.split_max_seconds)
         chunks = []
-        for ci in range(num_chunks):
-            start_sample = int(ci * adjusted * SAMPLE_RATE)
-            end_sample = int((ci + 1) * adjusted * SAMPLE_RATE)
+        for start_sample, end_sample in bounds:
             chunk = audio[start_sample:end_sample]
             if features_fn is not None:
                 probs_dev, mean_dev = self.predict_probabilities_device(features_fn(chunk))
             else:
                 probs_dev, mean_dev = self.predict_audio_device(chunk)   # (a replayed HIP graph for clip-sized chunks when graph=True)
-            if self.device_post and self._device_post_applies(probs_dev, parameters):
-                activities, probs = self._post_device(probs_dev, parameters)
-                self.post_stats["device"] += 1
-            else:
-                activities, probs = self._post_host(probs_dev, parameters)
-                self.post_stats["host"] += 1
+            activities, probs = self._post(probs_dev, parameters)
             chunks.append(VoiceActivity(duration=timedelta(seconds=adjusted), activities=activities,
                                         probs_sample_rate=parameters.probs_sample_rate if parameters.return_probs else None,
                                         probs=probs))
         return merge_voice_activities(chunks)
+
+    def _post(self, probs_dev, parameters: VADPredictParameters):
+        """a chunk's probabilities -> (activities, probs): on the GPU where `device_post` asks for it and the geometry allows it"""
+        if self.device_post and self._device_post_applies(probs_dev, parameters):
+            self.post_stats["device"] += 1
+            return self._post_device(probs_dev, parameters)
+        self.post_stats["host"] += 1
+        return self._post_host(probs_dev, parameters)
+
+    def predict_many(self, audios, parameters: VADPredictParameters, features_fn=None) -> "list[VoiceActivity]":
+        """predict() for a LIST of recordings (each as predict takes it) -> their VoiceActivity, in order, through one batched
+        prediction: every recording is cut into its `split_max_seconds` chunks (clips.chunk_bounds: predict's own), every chunk's
+        front-end writes its rows of ONE feature matrix (per-chunk launches), the windows of all chunks of all recordings run in one
+        library call (predict_probabilities_many), and each chunk's slice is post-processed as predict does it."""
+        from .clips import chunk_bounds, clip_table, split_by_clip
+        from .features import SAMPLE_RATE, log_mel
+
+        _require_hip(self.device)
+        dev = _indexed(self.device)
+        pieces, plan = [], []   # every chunk of every recording; per recording: (seconds per chunk, its chunks' indices)
+        for audio in audios:
+            if not (isinstance(audio, torch.Tensor) and audio.device.type == "cuda" and audio.dtype == torch.float32 and audio.dim() == 1):
+                audio = np.asarray(audio, dtype=np.float32)
+            adjusted, bounds = chunk_bounds(len(audio), SAMPLE_RATE, parameters.split_max_seconds)
+            plan.append((adjusted, range(len(pieces), len(pieces) + len(bounds))))
+            pieces += [audio[a:b] for a, b in bounds]
+        if not pieces:
+            return []
+        if features_fn is None and self.front_end.is_shipped:
+            for piece in pieces:
+                if len(piece) < 1:
+                    raise ValueError("audio must be a non-empty 1-D array")
+            table = clip_table(1 + len(piece) // 160 for piece in pieces)
+            feature = torch.empty((int(table[-1]), self.front_end.feature_size), dtype=torch.float32, device=dev)
+            for piece, rows in zip(pieces, split_by_clip(feature, table)):
+                log_mel(piece, dev, out=rows)
+            results = split_by_clip_pairs(self._predict_matrix(feature, table), table)
+        else:
+            results = self.predict_probabilities_many([features_fn(piece) if features_fn is not None else self.features(piece)
+                                                       for piece in pieces])
+        out = []
+        for adjusted, indices in plan:
+            chunks = []
+            for i in indices:
+                activities, probs = self._post(results[i][0], parameters)
+                chunks.append(VoiceActivity(duration=timedelta(seconds=adjusted), activities=activities,
+                                            probs_sample_rate=parameters.probs_sample_rate if parameters.return_probs else None,
+                                            probs=probs))
+            out.append(merge_voice_activities(chunks))
+        return out
+
+    @torch.no_grad()
+    def _predict_matrix(self, feature, table):
+        """(probs [sum N, W], mean [sum N]) of a concatenated device matrix and its clip table"""
+        self.model.eval()
+        return self.model.predict_windows_batch(feature, table, self.context_window_half_frames, self.context_window_jump_frames,
+                                                self.chunk_size)
+
+    @torch.no_grad()
+    def predict_probabilities_many(self, features) -> "list[tuple]":
+        """predict_probabilities_device for a LIST of [N_c, F] feature matrices (numpy or tensor; an empty one is legal) in one
+        library call -> [(probs [N_c, W], mean [N_c])] on the device: views of one result, clip by clip."""
+        from .clips import clip_table
+
+        _require_hip(self.device)
+        dev = _indexed(self.device)
+        feats = [torch.as_tensor(f, dtype=torch.float32).to(dev) for f in features]
+        if not feats:
+            return []
+        for f in feats:
+            if f.dim() != 2 or f.shape[1] != self.model.feature_size:
+                raise ValueError(f"every feature matrix must be [N, {self.model.feature_size}], got {tuple(f.shape)}")
+        table = clip_table(f.shape[0] for f in feats)
+        feature = feats[0].contiguous() if len(feats) == 1 else torch.cat(feats, dim=0)
+        return split_by_clip_pairs(self._predict_matrix(feature, table), table)
 
     def _post_host(self, probs_dev, parameters: VADPredictParameters):
         """probs [N, W] on the device -> (activities, probs list or None) on the host: vad/predictor.py:95-141"""
