@@ -201,6 +201,13 @@ __device__ __forceinline__ void store_hblock32(float* hb, const f32x16 (&x)[4], 
 #ifndef SAVAD_PIECE_FENCE
 #define SAVAD_PIECE_FENCE 0x6   // __builtin_amdgcn_sched_barrier mask around a DMA piece: only VALU / SALU may move across it
 #endif
+// a wave-uniform pointer the compiler cannot see to be one (computed from a run-time stream index): into scalar registers, where a DMA
+// piece wants its source (the builtin returns int: the halves are widened as unsigned, never sign-extended)
+__device__ __forceinline__ const char* scalar_ptr(const char* p) {
+    const size_t a = (size_t)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    return (const char*)((size_t)lo | ((size_t)hi << 32));
+}
 struct DmaJob {
     const char* src;  // wave-uniform: this wave's 12 KiB of the slot in global memory
     unsigned ldsb;    // ... and their place in LDS (byte address)
@@ -824,6 +831,9 @@ __device__ __forceinline__ const char* row_seg(const RowArgs3& A, int t, int sgm
     return A.wn_frag + (size_t)(2 * (t - 16) + sgm) * BLK3_BYTES;
 }
 
+// slots of the chain's weight stream
+__host__ __device__ constexpr int row_slots(bool last, bool folded) { return (folded ? 0 : 2) + (last ? 16 : folded ? 20 : 22); }
+
 // the row chain's biases (LAST: the classifier's folded weights and bias in the Q/K/V slot) -> LDS behind the ring; called at the head
 // of the kernel, so that their round trip to memory is long over when the chain starts; published by any workgroup barrier
 template <bool LAST, bool FOLDED>
@@ -859,7 +869,7 @@ __device__ __forceinline__ void row_stage_f32s(const RowArgs3& A, char* smem, Tr
     float* lbn = lb2 + D;
     const int lane = ring.lane, m = lane & 31, h = lane >> 5;
     constexpr int OFF = FOLDED ? 0 : 2;   // slots in front of the FFN's: Wo
-    constexpr int NSLOT = OFF + (LAST ? 16 : FOLDED ? 20 : 22);
+    constexpr int NSLOT = row_slots(LAST, FOLDED);
     auto job = [&](int t) { return ring.job(base + t, row_seg(A, t, 0, FOLDED), row_seg(A, t, 1, FOLDED)); };
     const DmaJob none{nullptr, 0u};
     // acquire slot T_, then acc0 / acc1 += slot . operand with the DMA of slot T_ + 2 between the MFMAs
@@ -1022,14 +1032,16 @@ __global__ __launch_bounds__(256, 1) void attention_row_kernel_f32s(const char* 
         base = QB;
         // stream index u: slot u = [V(u)^T | K(u+1)] for the key tiles 0 .. QB-1 (K(0) in a slot of its own in front: u = -1, at ring
         // position 2), then the row chain's slots; behind the last key tile K is a re-read of that tile (never used)
-        auto job = [&](int u) {
+        // (seg: what a segment's address goes through on its way into the job)
+        auto job_at = [&](int u, auto seg) {
             if (u < QB) {
                 const size_t kb = (size_t)b * QB;
                 const int uv = u < 0 ? 0 : u, uk = u + 1 < QB ? u + 1 : QB - 1;
-                return ring.job(u + 3, vtf + (kb + uv) * BLK3_BYTES, kf + (kb + uk) * BLK3_BYTES);
+                return ring.job(u + 3, seg(vtf + (kb + uv) * BLK3_BYTES), seg(kf + (kb + uk) * BLK3_BYTES));
             }
-            return ring.job(u, row_seg(A, u - QB, 0, true), row_seg(A, u - QB, 1, true));
+            return ring.job(u, seg(row_seg(A, u - QB, 0, true)), seg(row_seg(A, u - QB, 1, true)));
         };
+        auto job = [&](int u) { return job_at(u, [](const char* p) { return p; }); };
         ring.issue_all(job(-1));   // K(0) first: the prologue's scores wait for it
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) qp[ks] = ldtri(qf + (size_t)blk_q * BLK3_BYTES + ks * TFRAG_BYTES + lane * 16);
@@ -1064,12 +1076,19 @@ __global__ __launch_bounds__(256, 1) void attention_row_kernel_f32s(const char* 
             request_hblock32(hr, A.hbuf + (size_t)blk_q * (32 * D), lane);
             attn_step3<false, true>(st, qp, sc, ring.slot(QB - 1), no_mask, ring, job(QB + 1));
             SAVAD_STAMP(3);
-        } else {  // a wave without a query block still moves its share of the stream and meets the others at every barrier
+        } else {
+            // A wave without a query block computes nothing: it moves its share of the stream -- the key tiles' slots and the row
+            // chain's, slot u + 2 behind the barrier of step u -- meets the others at every barrier (one per slot: row_stage_f32s) and
+            // is done.  (It used to run the whole chain on zeros: 1,920 MFMAs and every LDS read of every weight slot for nothing.)
+            constexpr int NSLOT = row_slots(LAST, true);
 #pragma unroll 1
-            for (int jt = 0; jt < QB; ++jt) {
+            for (int u = 0; u + 2 < QB + NSLOT; ++u) {
                 ring.acquire<1>();
-                ring.issue_all(job(jt + 2));
+                ring.issue_all(job_at(u + 2, [](const char* p) { return scalar_ptr(p); }));   // (a run-time index into the chain's slots)
             }
+            ring.acquire<1>();
+            ring.acquire<0>();
+            return;
         }
     }
     // normalised context (invalid slots and waves without a block: exact zeros).  PACKED: -> B-operand triples of the out-projection, in
