@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 HOP = 160
-PAIR = [0, 1, 1, 2, 3, 4, 4, 5, 6, 7]   # entry t of a group's mel table -> register pair, mel block (savad.hip: build_fft_tables)
+PAIR = [0, 1, 1, 2, 3, 4, 4, 5, 6, 7]   # entry t of a group's mel table -> register pair, mel block (savad_audio_host.h: mel::fft_tables)
 BLOCK = [0, 0, 1, 1, 1, 1, 2, 2, 2, 2]
 LANE = np.arange(64)
 J, H = LANE & 31, LANE >> 5

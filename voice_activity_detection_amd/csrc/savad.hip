@@ -31,6 +31,9 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <tuple>
+#include <utility>
+#include <variant>
 #include <vector>
 
 #include "../../include/savad.h"
@@ -103,16 +106,6 @@ using namespace savad;
 
 // blocks of 256 threads for `work` elements, at most `cap` (the kernels stride over the rest)
 int grid_for(long work, int cap = 4096) { return (int)((work + 255) / 256 < cap ? (work + 255) / 256 : cap); }
-
-// consecutive 256-byte-aligned regions of a caller's workspace (post_layout, eval_layout)
-struct Arena {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    }
-};
 
 sched::Knobs knobs_of(const savad_model* m) {
     sched::Knobs k;
@@ -1300,231 +1293,88 @@ SAVAD_EXPORT int savad_overlap_merge(const float* logp, int W, int N, int T, int
     return SAVAD_OK;
 }
 
-// ---- log-mel front-end (savad_logmel.h) ---------------------------------------------------------
+// ---- device tables of the audio paths (host builders and layouts: savad_audio_host.h) -----------------------------------------
+// A table is built on the host and uploaded on first use by the device that needs it -- synchronously, so never inside a
+// graph capture: savad_frontend_prepare and savad_resample_prepare are the explicit steps before one -- and stays for the
+// life of the process.  One mutex guards everything in this section.
 namespace {
 
-struct MelTables {
-    float* d_dft = nullptr;  // DFT-as-GEMM kernel (algorithm 1)
-    float* d_mel = nullptr;
-    float* d_t1 = nullptr;  // factored kernel (algorithm 0)
-    float* d_t3 = nullptr;
-    float* d_tm = nullptr;
-    int n_cu = 0;
-};
-std::mutex g_mel_mutex;
-std::map<int, MelTables> g_mel_by_device;  // built once per device, never freed (process lifetime, 1.1 MB)
-int g_logmel_algorithm = 0;
+std::mutex g_audio_mutex;
+std::vector<int> g_audio_n_cu;   // by device ordinal; 0 = the device is not set up yet
 
-double hz_to_mel(double f) {  // Slaney scale (librosa htk=False)
-    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
-    return f >= min_log_hz ? min_log_mel + log(f / min_log_hz) / logstep : f / f_sp;
-}
-double mel_to_hz(double mm) {
-    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
-    return mm >= min_log_mel ? min_log_hz * exp(logstep * (mm - min_log_mel)) : f_sp * mm;
-}
+bool aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
+float* at(float* base, size_t bytes) { return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + bytes); }
 
-// Slaney mel filterbank (librosa.filters.mel, norm="slaney", float32): M[mel][bin], 80 x 257
-std::vector<float> mel_filterbank() {
-    using namespace mel;
-    const int NB = N_FFT / 2 + 1;
-    std::vector<double> mel_f(N_MELS + 2);
-    const double m_lo = hz_to_mel(0.0), m_hi = hz_to_mel(8000.0);
-    for (int i = 0; i < N_MELS + 2; ++i) mel_f[i] = mel_to_hz(m_lo + (m_hi - m_lo) * i / (N_MELS + 1));
-    std::vector<float> M((size_t)N_MELS * NB, 0.0f);
-    for (int i = 0; i < N_MELS; ++i) {
-        const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
-        for (int b = 0; b < NB; ++b) {
-            const double fr = 8000.0 * b / (NB - 1);
-            const double lower = (fr - mel_f[i]) / (mel_f[i + 1] - mel_f[i]);
-            const double upper = (mel_f[i + 2] - fr) / (mel_f[i + 2] - mel_f[i + 1]);
-            const double wgt = fmax(0.0, fmin(lower, upper));
-            M[(size_t)i * NB + b] = (float)wgt * (float)enorm;
+int audio_device(int dev, int* n_cu);   // (defined after the last entry point of the audio paths)
+
+// tables with elements T... under a Key, per device
+template <class Key, class... T>
+struct DeviceTables {
+    using Host = std::tuple<std::vector<T>...>;
+    using Ptrs = std::tuple<T*...>;
+    static inline std::map<std::pair<int, Key>, Ptrs> resident;
+
+    // the key's tables on the current device; on a miss build(Host&) fills the host arrays (or returns its refusal).
+    // The caller holds g_audio_mutex.
+    template <class Build>
+    static int get(const Key& key, Build&& build, Ptrs* out, int* n_cu) {
+        int rc, dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        if ((rc = audio_device(dev, n_cu))) return rc;
+        auto it = resident.find({dev, key});
+        if (it == resident.end()) {
+            Host h;
+            Ptrs p;
+            if ((rc = build(h)) || (rc = upload(h, p, std::index_sequence_for<T...>{}))) return rc;
+            it = resident.emplace(std::make_pair(dev, key), p).first;
         }
-    }
-    return M;
-}
-
-// A operands of logmel_fft_kernel (layouts: savad_logmel.h).  Pure host code; false when a filter weight falls outside
-// the kernel's fixed (register pair -> mel block) pattern, which would be a bug in the bin ordering.
-bool build_fft_tables(std::vector<float>& t1, std::vector<float>& t3, std::vector<float>& tm) {
-    using namespace mel;
-    const double PI = 3.14159265358979323846;
-    const int NB = N_FFT / 2 + 1;
-    t1.assign(FFT_T1_FLOATS, 0.0f);
-    t3.assign(FFT_T3_FLOATS, 0.0f);
-    tm.assign(FFT_TM_FLOATS, 0.0f);
-    // step 1: row i = lane & 31 of the output tile is (k1 = 4 (i >> 3) + (i & 3), re | im = (i >> 2) & 1); k-step s of
-    // lane half h is n1 = 3 + 2 s + h; the slot of im(k1 = 0) carries re(k1 = 16)
-    for (int w = 0; w < 4; ++w)
-        for (int s = 0; s < 13; ++s)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e) {
-                    const int i = lane & 31, h = lane >> 5, n1 = 3 + 2 * s + h, n2 = 4 * w + e, n = 16 * n1 + n2;
-                    int k1 = 4 * (i >> 3) + (i & 3);
-                    bool im = (i >> 2) & 1;
-                    if (k1 == 0 && im) {
-                        k1 = 16;
-                        im = false;
-                    }
-                    float win = 0.0f;
-                    if (n >= LPAD && n < LPAD + WIN) win = (float)(0.5 - 0.5 * cos(2.0 * PI * (n - LPAD) / WIN));  // periodic Hann(400), float32 as librosa's
-                    const double ph = 2.0 * PI * (double)(n1 * k1 % 32) / 32.0;
-                    t1[(((size_t)w * 13 + s) * 64 + lane) * 4 + e] = (float)(win * (im ? -sin(ph) : cos(ph)));
-                }
-    // bins of a group, lowest first.  kind 0: bin K = 32 k2 from Y[0] (real, low lane half); kind 1: K = 16 + 32 k2 from
-    // Y[16] (real, high lane half); kind 2: K = k1 + 32 k2 from the complex Y[k1].  label = the bin below 257 with the same power.
-    struct Bin {
-        int kind, K, label;
-    };
-    std::vector<std::vector<Bin>> groups(16);
-    for (int grp = 0; grp < 16; ++grp) {
-        std::vector<Bin>& g = groups[grp];
-        if (grp == 0) {
-            for (int k2 = 1; k2 < 8; ++k2) g.push_back({0, 32 * k2, 32 * k2});
-            for (int k2 = 0; k2 < 8; ++k2) g.push_back({1, 16 + 32 * k2, 16 + 32 * k2});
-        } else {
-            for (int k2 = 0; k2 < 16; ++k2) {
-                const int K = grp + 32 * k2;
-                g.push_back({2, K, K <= 256 ? K : 512 - K});
-            }
-        }
-        for (size_t a = 1; a < g.size(); ++a)  // insertion sort by label
-            for (size_t b = a; b > 0 && g[b].label < g[b - 1].label; --b) std::swap(g[b], g[b - 1]);
-    }
-    // step 3: row i of the output tile is (register pair p = 2 (i >> 3) + ((i & 3) >> 1), lane half hD = (i >> 2) & 1,
-    // re | im = i & 1) = bin number 2 p + hD of the group; k-step n2 of lane half h multiplies re (h = 0) / im (h = 1) of Y
-    for (int grp = 0; grp < 16; ++grp)
-        for (int n2 = 0; n2 < 16; ++n2)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int i = lane & 31, h = lane >> 5;
-                const int p = 2 * (i >> 3) + ((i & 3) >> 1), hD = (i >> 2) & 1, ro = i & 1, idx = 2 * p + hD;
-                float v = 0.0f;
-                if (idx < (int)groups[grp].size()) {
-                    const Bin& b = groups[grp][idx];
-                    const double th = 2.0 * PI * (double)((long)n2 * b.K % N_FFT) / N_FFT, c = cos(th), sn = sin(th);
-                    // X = sum (Yre + i Yim)(c - i sn):  re = Yre c + Yim sn,  im = Yim c - Yre sn
-                    if (b.kind == 2)
-                        v = (float)(h == 0 ? (ro == 0 ? c : -sn) : (ro == 0 ? sn : c));
-                    else if (b.kind == h)
-                        v = (float)(ro == 0 ? c : -sn);
-                }
-                t3[(((size_t)grp * 4 + (n2 >> 2)) * 64 + lane) * 4 + (n2 & 3)] = v;
-            }
-    // mel: entry t of a group = (pair, mel block) in the kernel's fixed order
-    static const int PAIR[10] = {0, 1, 1, 2, 3, 4, 4, 5, 6, 7}, BLOCK[10] = {0, 0, 1, 1, 1, 1, 2, 2, 2, 2};
-    const std::vector<float> M = mel_filterbank();
-    std::vector<char> covered((size_t)N_MELS * NB, 0);
-    for (int grp = 0; grp < 16; ++grp)
-        for (int t = 0; t < 10; ++t)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int j = lane & 31, h = lane >> 5, idx = 2 * PAIR[t] + h, ml = 32 * BLOCK[t] + j;
-                if (idx < (int)groups[grp].size() && ml < N_MELS) {
-                    const int label = groups[grp][idx].label;
-                    tm[(((size_t)grp * 3 + (t >> 2)) * 64 + lane) * 4 + (t & 3)] = M[(size_t)ml * NB + label];
-                    covered[(size_t)ml * NB + label] = 1;
-                }
-            }
-    for (size_t q = 0; q < M.size(); ++q)
-        if (M[q] != 0.0f && !covered[q]) return false;
-    return true;
-}
-
-int ensure_mel_tables(hipStream_t st, MelTables* out) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_mel_mutex);
-    auto it = g_mel_by_device.find(dev);
-    if (it != g_mel_by_device.end()) {
         *out = it->second;
         return SAVAD_OK;
     }
-    MelTables g_mel;
-    using namespace mel;
-    const double PI = 3.14159265358979323846;
-    // window-folded DFT rows in fragment order [row block 16][G 50][lane 64][4]:
-    // row 0 = re(bin 0), row 1 = re(bin 256) (both imaginary parts are identically 0), row 2b / 2b+1 = re / im of bin b
-    std::vector<float> dft((size_t)DFT_FRAG_FLOATS);
-    for (int rb = 0; rb < 16; ++rb)
-        for (int G = 0; G < KG; ++G)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e) {
-                    const int n = lane & 31, hh = lane >> 5, row = 32 * rb + n, kk = 8 * G + 4 * hh + e;
-                    const double win = 0.5 - 0.5 * cos(2.0 * PI * kk / WIN);  // periodic Hann(400)
-                    const int kp = kk + LPAD;                                  // position inside the 512-sample frame
-                    int bin = row >> 1;
-                    bool im = row & 1;
-                    if (row == 1) {
-                        bin = 256;
-                        im = false;
-                    }
-                    const double ph = 2.0 * PI * (double)((long)bin * kp % N_FFT) / N_FFT;
-                    dft[(((size_t)rb * KG + G) * 64 + lane) * 4 + e] = (float)((float)win * (im ? -sin(ph) : cos(ph)));
-                }
-    const int NB = N_FFT / 2 + 1;
-    const std::vector<float> M = mel_filterbank();
-    // mel fragments [pass 4][mel block 3][row block 4][g pair 2][lane 64][4]; element e -> g = 2gp + (e>>1), bin
-    // 64 pass + 16 rbl + 4 g + 2 h + (e&1).  Bins 0 and 256 have zero weight in every filter (fmin 0, fmax 8 kHz).
-    std::vector<float> melf((size_t)MEL_FRAG_FLOATS, 0.0f);
-    for (int pass = 0; pass < 4; ++pass)
-        for (int mb = 0; mb < 3; ++mb)
-            for (int rbl = 0; rbl < 4; ++rbl)
-                for (int gp = 0; gp < 2; ++gp)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 4; ++e) {
-                            const int n = lane & 31, hh = lane >> 5, g = 2 * gp + (e >> 1);
-                            const int bin = 64 * pass + 16 * rbl + 4 * g + 2 * hh + (e & 1);
-                            const int ml_ = 32 * mb + n;
-                            float v = 0.0f;
-                            if (ml_ < N_MELS && bin >= 1 && bin < 256) v = M[(size_t)ml_ * NB + bin];
-                            melf[(((((size_t)pass * 3 + mb) * 4 + rbl) * 2 + gp) * 64 + lane) * 4 + e] = v;
-                        }
-    std::vector<float> t1, t3, tm;
-    if (!build_fft_tables(t1, t3, tm)) return fail(SAVAD_E_STATE, "log-mel tables: a filter weight falls outside the kernel's pair -> mel block pattern");
-    HIP_TRY(hipDeviceGetAttribute(&g_mel.n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mel::logmel_fft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, mel::FFT_LDS_BYTES));
-    float* base = nullptr;  // one allocation: every table starts 256-byte aligned
-    auto up = [](size_t n) { return (n + 63) / 64 * 64; };
-    const size_t total = up(dft.size()) + up(melf.size()) + up(t1.size()) + up(t3.size()) + up(tm.size());
-    HIP_TRY(hipMalloc(&base, total * sizeof(float)));
-    size_t off = 0;
-    auto put = [&](const std::vector<float>& v, float** d) -> hipError_t {
-        *d = base + off;
-        off += up(v.size());
-        return hipMemcpyAsync(*d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice, st);
-    };
-    HIP_TRY(put(dft, &g_mel.d_dft));
-    HIP_TRY(put(melf, &g_mel.d_mel));
-    HIP_TRY(put(t1, &g_mel.d_t1));
-    HIP_TRY(put(t3, &g_mel.d_t3));
-    HIP_TRY(put(tm, &g_mel.d_tm));
-    HIP_TRY(hipStreamSynchronize(st));
-    g_mel_by_device[dev] = g_mel;
-    *out = g_mel;
-    return SAVAD_OK;
+
+    // one allocation, every array starting 256-byte aligned; given back if a copy fails
+    template <size_t... I>
+    static int upload(const Host& h, Ptrs& p, std::index_sequence<I...>) {
+        Arena a;
+        const size_t off[] = {a.take(std::get<I>(h).size() * sizeof(T))...};
+        char* base = nullptr;
+        HIP_TRY(hipMalloc(&base, a.off));
+        hipError_t e = hipSuccess;
+        auto copy = [&](const auto& v, size_t at) { return v.empty() ? hipSuccess : hipMemcpy(base + at, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice); };
+        ((e = e != hipSuccess ? e : copy(std::get<I>(h), off[I])), ...);
+        if (e != hipSuccess) {
+            hipFree(base);
+            return fail(SAVAD_E_HIP, "table upload: %s", hipGetErrorString(e));
+        }
+        ((std::get<I>(p) = reinterpret_cast<T*>(base + off[I])), ...);
+        return SAVAD_OK;
+    }
+};
+
+// ---- log-mel front-end (savad_logmel.h) ---------------------------------------------------------
+int g_logmel_algorithm = 0;
+
+int fft_tables_checked(std::vector<float>& t1, std::vector<float>& t3, std::vector<float>& tm) {
+    return mel::fft_tables(t1, t3, tm) ? SAVAD_OK : fail(SAVAD_E_STATE, "log-mel tables: a filter weight falls outside the kernel's pair -> mel block pattern");
 }
 
-// samples [first, first + count) of the signal that frames [frame_first, frame_first + frame_count) read, reflections
-// at the signal's ends included; first is rounded down to a multiple of 4 (16-byte alignment of the direct reads)
-void span_samples(long n, int frame_first, int frame_count, long* first, long* count) {
-    const long lo = (long)mel::HOP * frame_first - 208, hi = (long)mel::HOP * (frame_first + frame_count - 1) + 208;  // [lo, hi)
-    long a = lo < 0 ? 0 : lo, b = hi > n ? n : hi;
-    if (lo < 0 && -lo + 1 > b) b = -lo + 1;
-    if (hi > n && 2 * (n - 1) - (hi - 1) < a) a = 2 * (n - 1) - (hi - 1);
-    if (a < 0) a = 0;
-    if (b > n) b = n;
-    a &= ~3L;
-    *first = a;
-    *count = b - a;
+// DFT and mel fragments of the DFT-as-GEMM kernel (algorithm 1) | t1, t3, tm of the factored kernel (algorithm 0): 1.1 MB per device
+using MelTables = DeviceTables<std::monostate, float, float, float, float, float>;
+int mel_tables(MelTables::Ptrs* t, int* n_cu) {
+    std::lock_guard<std::mutex> lock(g_audio_mutex);
+    return MelTables::get({}, [](MelTables::Host& h) {
+        auto& [dft, melf, t1, t3, tm] = h;
+        dft = mel::dft_fragments();
+        melf = mel::mel_fragments();
+        return fft_tables_checked(t1, t3, tm);
+    }, t, n_cu);
 }
 
 }  // namespace
 
 SAVAD_EXPORT int savad_logmel_frames(int n_samples) { return n_samples < 0 ? fail(SAVAD_E_INVALID, "n_samples") : 1 + n_samples / mel::HOP; }
-SAVAD_EXPORT size_t savad_logmel_workspace_bytes(int n_samples) { return ((size_t)n_samples + mel::N_FFT + 64) * sizeof(float); }
-SAVAD_EXPORT size_t savad_logmel_span_workspace_bytes(int frame_count) {
-    return ((size_t)mel::HOP * (frame_count > 0 ? frame_count : 0) + mel::N_FFT + 64 + 2048) * sizeof(float);
-}
+SAVAD_EXPORT size_t savad_logmel_workspace_bytes(int n_samples) { return mel::workspace_whole(n_samples).total; }
+SAVAD_EXPORT size_t savad_logmel_span_workspace_bytes(int frame_count) { return mel::workspace_span(frame_count).total; }
 SAVAD_EXPORT int savad_logmel_set_algorithm(int algorithm) {
     if (algorithm < 0 || algorithm > 1) return fail(SAVAD_E_INVALID, "log-mel algorithm %d (0 = factored DFT, 1 = DFT as one GEMM)", algorithm);
     g_logmel_algorithm = algorithm;
@@ -1536,7 +1386,7 @@ SAVAD_EXPORT int savad_logmel_table_floats(int which) {
 SAVAD_EXPORT int savad_logmel_tables_host(float* t1, float* t3, float* tm) {
     if (!t1 || !t3 || !tm) return fail(SAVAD_E_INVALID, "null argument");
     std::vector<float> a, b, c;
-    if (!build_fft_tables(a, b, c)) return fail(SAVAD_E_STATE, "log-mel tables: a filter weight falls outside the kernel's pair -> mel block pattern");
+    if (int rc = fft_tables_checked(a, b, c)) return rc;
     memcpy(t1, a.data(), a.size() * sizeof(float));
     memcpy(t3, b.data(), b.size() * sizeof(float));
     memcpy(tm, c.data(), c.size() * sizeof(float));
@@ -1566,7 +1416,7 @@ SAVAD_EXPORT int savad_pcm16_to_f32(const short* pcm, long n_samples, float* aud
 SAVAD_EXPORT int savad_logmel_span_samples(long n_samples, int frame_first, int frame_count, long* first, long* count) {
     if (!first || !count || n_samples < 1 || frame_first < 0 || frame_count < 1 || frame_first + (long)frame_count > 1 + n_samples / mel::HOP)
         return fail(SAVAD_E_INVALID, "bad frame span [%d, +%d) of %ld samples", frame_first, frame_count, n_samples);
-    span_samples(n_samples, frame_first, frame_count, first, count);
+    mel::span_samples(n_samples, frame_first, frame_count, first, count);
     return SAVAD_OK;
 }
 
@@ -1577,22 +1427,23 @@ SAVAD_EXPORT int savad_logmel_span(const float* audio, long audio_first, long au
         return fail(SAVAD_E_INVALID, "bad argument");
     if (frame_first < 0 || frame_count < 1 || frame_first + (long)frame_count > 1 + n_samples / mel::HOP)
         return fail(SAVAD_E_INVALID, "frames [%d, +%d) outside the %ld frames of %ld samples", frame_first, frame_count, 1 + n_samples / mel::HOP, n_samples);
-    if (((uintptr_t)workspace | (uintptr_t)features) & 15) return fail(SAVAD_E_INVALID, "workspace and features must be 16-byte aligned");
+    if (!aligned16(workspace, features)) return fail(SAVAD_E_INVALID, "workspace and features must be 16-byte aligned");
     long need_first, need_count;
-    span_samples(n_samples, frame_first, frame_count, &need_first, &need_count);
+    mel::span_samples(n_samples, frame_first, frame_count, &need_first, &need_count);
     if (audio_first > need_first + 3 || audio_first + audio_count < need_first + need_count)  // (+3: need_first was rounded down)
         return fail(SAVAD_E_INVALID, "frames [%d, +%d) read samples [%ld, +%ld); the audio slice holds [%ld, +%ld)", frame_first, frame_count,
                     need_first, need_count, audio_first, audio_count);
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    MelTables g_mel;
-    if ((rc = ensure_mel_tables(st, &g_mel))) return rc;
+    int rc, n_cu;
+    MelTables::Ptrs tb;
+    if ((rc = mel_tables(&tb, &n_cu))) return rc;
     const float* y0 = audio - audio_first;  // y0[i] = sample i (only indices inside the slice are ever read)
     // the frames read padded indices [j_first, j_last + 4), in 16-byte chunks (savad_logmel.h: sample stage)
     const long j_first = (long)mel::HOP * frame_first + 48, j_last = (long)mel::HOP * (frame_first + frame_count - 1) + 460;
     constexpr long NEVER = 1L << 40;
+    const mel::Workspace w = mel::workspace_span(frame_count);   // (the whole-signal workspace places its pieces the same)
     mel::FftSrc src{};
-    mel::PadSeg A{workspace, 0, 0}, B{workspace + 256, 0, 0};
+    mel::PadSeg A{at(workspace, w.pad_a), 0, 0}, B{at(workspace, w.pad_b), 0, 0};
     src.y0 = y0;
     src.jA_end = -NEVER;
     src.jB0 = NEVER;
@@ -1621,10 +1472,11 @@ SAVAD_EXPORT int savad_logmel_span(const float* audio, long audio_first, long au
         const long total = (long)A.count + B.count;
         hipLaunchKernelGGL(mel::reflect_pad_segments_kernel, dim3(grid_for(total)), dim3(256), 0, st, y0, n_samples, A, B);
     }
+    const auto [d_dft, d_mel, d_t1, d_t3, d_tm] = tb;
     const int tiles = (frame_count + 31) / 32;
-    const int grid = tiles < g_mel.n_cu ? tiles : g_mel.n_cu;
-    hipLaunchKernelGGL(mel::logmel_fft_kernel, dim3(grid), dim3(256), mel::FFT_LDS_BYTES, st, src, frame_first, frame_count, tiles, g_mel.d_t1,
-                       g_mel.d_t3, g_mel.d_tm, features);
+    const int grid = tiles < n_cu ? tiles : n_cu;
+    hipLaunchKernelGGL(mel::logmel_fft_kernel, dim3(grid), dim3(256), mel::FFT_LDS_BYTES, st, src, frame_first, frame_count, tiles, d_t1, d_t3, d_tm,
+                       features);
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }
@@ -1633,32 +1485,22 @@ SAVAD_EXPORT int savad_logmel(const float* audio, int n_samples, float* workspac
     if (!audio || !workspace || !features || n_samples < 1) return fail(SAVAD_E_INVALID, "bad argument");
     if (g_logmel_algorithm == 0)
         return savad_logmel_span(audio, 0, n_samples, n_samples, 0, 1 + n_samples / mel::HOP, workspace, features, stream);
-    if (((uintptr_t)workspace | (uintptr_t)features) & 15) return fail(SAVAD_E_INVALID, "workspace and features must be 16-byte aligned");
+    if (!aligned16(workspace, features)) return fail(SAVAD_E_INVALID, "workspace and features must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    MelTables g_mel;
-    if ((rc = ensure_mel_tables(st, &g_mel))) return rc;
+    int rc, n_cu;
+    MelTables::Ptrs tb;
+    if ((rc = mel_tables(&tb, &n_cu))) return rc;
     const int n_frames = 1 + n_samples / mel::HOP;
     const long total = (long)n_samples + mel::N_FFT;
     hipLaunchKernelGGL(mel::reflect_pad_kernel, dim3(grid_for(total)), dim3(256), 0, st, audio, n_samples, workspace);
     const int tiles = (n_frames + 31) / 32;
-    hipLaunchKernelGGL(mel::logmel_kernel<4>, dim3(tiles), dim3(256), 0, st, workspace, n_frames, g_mel.d_dft, g_mel.d_mel,
-                       features);
+    hipLaunchKernelGGL(mel::logmel_kernel<4>, dim3(tiles), dim3(256), 0, st, workspace, n_frames, std::get<0>(tb), std::get<1>(tb), features);
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }
 
 // ---- feature front-end for any transform config (savad_frontend.h) ----------------------------------------------
 namespace {
-
-struct FeTables {
-    float* d_dft = nullptr;  // stft_kernel's A fragments
-    float* d_mel = nullptr;  // [n_mels][nb]
-    float* d_dct = nullptr;  // [n_mfcc][n_mels]
-    float* d_sg = nullptr;   // [2][9][9]
-};
-std::mutex g_fe_mutex;
-std::map<std::vector<int>, FeTables> g_fe_tables;  // (device, transform, n_fft, win, n_mels, n_mfcc) -> tables; process lifetime
 
 int fe_check(const savad_frontend_config* c) {
     if (!c) return fail(SAVAD_E_INVALID, "null config");
@@ -1673,83 +1515,37 @@ int fe_check(const savad_frontend_config* c) {
     return SAVAD_OK;
 }
 
-// frames and features of a call; errors name the limit that was not met
+// frames and features of a call (fe::shape); errors name the limit that was not met
 int fe_shape(const savad_frontend_config* c, long n, int* frames, int* feats) {
     int rc;
     if ((rc = fe_check(c))) return rc;
-    const bool centred = c->transform != SAVAD_FE_SPECTROGRAM;
-    const long need = centred ? c->n_fft / 2 + 1 : c->n_fft;
-    if (n < need || n > 2000000000L)
-        return fail(SAVAD_E_INVALID, "%ld samples: the limit is n_samples >= %ld (%s)", n, need, centred ? "n_fft / 2 + 1, reflect padding" : "n_fft, center=False");
-    // frames of the n_fft-sample window over the signal (padded by n_fft / 2 per side when centred): 1 + n / hop for an even n_fft
-    const long N = 1 + (n + (centred ? 2 * (c->n_fft / 2) : 0) - c->n_fft) / c->hop;
-    if (c->deltas && N < savad::fe::DELTA_W)
-        return fail(SAVAD_E_INVALID, "%ld frames: temporal differences need at least %d (librosa.feature.delta, width 9)", N, savad::fe::DELTA_W);
-    const int F = c->transform == SAVAD_FE_SPECTROGRAM ? c->n_fft / 2 + 1 : c->transform == SAVAD_FE_MFCC ? c->n_mfcc : c->n_mels;
-    *frames = (int)N;
-    *feats = c->deltas ? 3 * F : F;
+    const fe::Shape s = fe::shape(*c, n);
+    if (n < s.need || n > 2000000000L)
+        return fail(SAVAD_E_INVALID, "%ld samples: the limit is n_samples >= %ld (%s)", n, s.need,
+                    c->transform != SAVAD_FE_SPECTROGRAM ? "n_fft / 2 + 1, reflect padding" : "n_fft, center=False");
+    if (c->deltas && s.frames < fe::DELTA_W)
+        return fail(SAVAD_E_INVALID, "%ld frames: temporal differences need at least %d (librosa.feature.delta, width 9)", s.frames, fe::DELTA_W);
+    *frames = (int)s.frames;
+    *feats = s.feats;
     return SAVAD_OK;
 }
 
-// workspace (floats, each piece 256-byte aligned): MFCC maximum | padded / copied signal | power [N][nbs] | dB mel [N][n_mels]
-struct FeWs {
-    size_t sig, spec, db, total;
-};
-FeWs fe_workspace(const savad_frontend_config* c, long n, int N) {
-    const savad::fe::Geo g = savad::fe::geometry(c->n_fft, c->hop, c->win);
-    auto up = [](size_t v) { return (v + 63) / 64 * 64; };
-    FeWs w;
-    w.sig = 64;
-    w.spec = w.sig + up((size_t)n + c->n_fft + savad::fe::SLACK);
-    w.db = w.spec + (c->transform == SAVAD_FE_SPECTROGRAM ? 0 : up((size_t)N * g.nbs));
-    w.total = w.db + (c->transform == SAVAD_FE_MFCC ? up((size_t)N * c->n_mels) : 0);
-    return w;
-}
-
-std::vector<float> fe_host_table(const savad_frontend_config* c, int which) {
-    namespace fe = savad::fe;
-    const fe::Geo g = fe::geometry(c->n_fft, c->hop, c->win);
-    if (which == 0) return fe::dft_plain(g, c->transform == SAVAD_FE_SPECTROGRAM);
-    if (which == 1) return c->transform == SAVAD_FE_SPECTROGRAM ? std::vector<float>() : fe::mel_filterbank(c->n_fft, c->n_mels);
-    if (which == 2) return c->transform == SAVAD_FE_MFCC ? fe::dct_ortho(c->n_mels, c->n_mfcc) : std::vector<float>();
-    return fe::savgol_rows();
-}
-
-// tables of this config on the current device, built (host, float64) and uploaded on first use: synchronous, so never
-// inside a graph capture -- savad_frontend_prepare is the explicit step before one
-int fe_tables(const savad_frontend_config* c, FeTables* out) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
+// stft_kernel's A fragments | mel [n_mels][nb] | DCT [n_mfcc][n_mels] | Savitzky-Golay [2][9][9], under what of the config
+// they depend on: (spectrogram or not, n_fft, win, n_mels, n_mfcc)
+using FeTables = DeviceTables<std::tuple<int, int, int, int, int>, float, float, float, float>;
+int fe_tables(const savad_frontend_config* c, FeTables::Ptrs* t) {
     const bool sp = c->transform == SAVAD_FE_SPECTROGRAM, mf = c->transform == SAVAD_FE_MFCC;
-    const std::vector<int> key{dev, sp ? 0 : 1, c->n_fft, c->win, sp ? 0 : c->n_mels, mf ? c->n_mfcc : 0};
-    std::lock_guard<std::mutex> lock(g_fe_mutex);
-    auto it = g_fe_tables.find(key);
-    if (it != g_fe_tables.end()) {
-        *out = it->second;
-        return SAVAD_OK;
-    }
-    const savad::fe::Geo g = savad::fe::geometry(c->n_fft, c->hop, c->win);
-    const std::vector<float> dft = savad::fe::dft_fragments(g, fe_host_table(c, 0)), mel = fe_host_table(c, 1), dct = fe_host_table(c, 2),
-                             sg = fe_host_table(c, 3);
-    auto up = [](size_t v) { return (v + 63) / 64 * 64; };
-    float* base = nullptr;
-    HIP_TRY(hipMalloc(&base, (up(dft.size()) + up(mel.size()) + up(dct.size()) + up(sg.size())) * sizeof(float)));
-    size_t off = 0;
-    FeTables t;
-    auto put = [&](const std::vector<float>& v, float** d) -> hipError_t {
-        *d = base + off;
-        off += up(v.size());
-        return v.empty() ? hipSuccess : hipMemcpy(*d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice);
-    };
-    HIP_TRY(put(dft, &t.d_dft));
-    HIP_TRY(put(mel, &t.d_mel));
-    HIP_TRY(put(dct, &t.d_dct));
-    HIP_TRY(put(sg, &t.d_sg));
-    g_fe_tables[key] = t;
-    *out = t;
-    return SAVAD_OK;
+    int n_cu;
+    std::lock_guard<std::mutex> lock(g_audio_mutex);
+    return FeTables::get({sp ? 0 : 1, c->n_fft, c->win, sp ? 0 : c->n_mels, mf ? c->n_mfcc : 0}, [c](FeTables::Host& h) {
+        auto& [dft, melw, dct, sg] = h;
+        dft = fe::dft_fragments(fe::geometry(*c), fe::host_table(*c, 0));
+        melw = fe::host_table(*c, 1);
+        dct = fe::host_table(*c, 2);
+        sg = fe::host_table(*c, 3);
+        return (int)SAVAD_OK;
+    }, t, &n_cu);
 }
-
 
 }  // namespace
 
@@ -1761,12 +1557,12 @@ SAVAD_EXPORT int savad_frontend_workspace_bytes(const savad_frontend_config* con
     int N, F, rc;
     if (!bytes) return fail(SAVAD_E_INVALID, "null argument");
     if ((rc = fe_shape(config, n_samples, &N, &F))) return rc;
-    *bytes = fe_workspace(config, n_samples, N).total * sizeof(float);
+    *bytes = fe::workspace(*config, n_samples, N).total;
     return SAVAD_OK;
 }
 SAVAD_EXPORT int savad_frontend_prepare(const savad_frontend_config* config) {
     int rc;
-    FeTables t;
+    FeTables::Ptrs t;
     if ((rc = fe_check(config))) return rc;
     return fe_tables(config, &t);
 }
@@ -1774,13 +1570,13 @@ SAVAD_EXPORT int savad_frontend_table_floats(const savad_frontend_config* config
     int rc;
     if ((rc = fe_check(config))) return rc;
     if (which < 0 || which > 3) return fail(SAVAD_E_INVALID, "table %d (0 = DFT, 1 = mel, 2 = DCT, 3 = Savitzky-Golay)", which);
-    return (int)fe_host_table(config, which).size();
+    return (int)fe::host_table(*config, which).size();
 }
 SAVAD_EXPORT int savad_frontend_tables_host(const savad_frontend_config* config, int which, float* out) {
     int rc;
     if ((rc = fe_check(config))) return rc;
     if (!out || which < 0 || which > 3) return fail(SAVAD_E_INVALID, "table %d / null output", which);
-    const std::vector<float> t = fe_host_table(config, which);
+    const std::vector<float> t = fe::host_table(*config, which);
     if (!t.empty()) memcpy(out, t.data(), t.size() * sizeof(float));
     return SAVAD_OK;
 }
@@ -1791,17 +1587,18 @@ SAVAD_EXPORT int savad_frontend(const savad_frontend_config* config, const float
     int N, Fo, rc;
     if ((rc = fe_shape(config, n_samples, &N, &Fo))) return rc;
     if (!audio || !workspace || !features) return fail(SAVAD_E_INVALID, "null argument");
-    if (((uintptr_t)workspace | (uintptr_t)features) & 15) return fail(SAVAD_E_INVALID, "workspace and features must be 16-byte aligned");
-    FeTables tb;
+    if (!aligned16(workspace, features)) return fail(SAVAD_E_INVALID, "workspace and features must be 16-byte aligned");
+    FeTables::Ptrs tb;
     if ((rc = fe_tables(config, &tb))) return rc;
+    const auto [d_dft, d_mel, d_dct, d_sg] = tb;
     hipStream_t st = (hipStream_t)stream;
     const savad_frontend_config& c = *config;
-    const Geo g = geometry(c.n_fft, c.hop, c.win);
-    const FeWs w = fe_workspace(config, n_samples, N);
-    const bool sp = c.transform == SAVAD_FE_SPECTROGRAM;
+    const Geo g = geometry(c);
+    const fe::Workspace w = fe::workspace(c, n_samples, N);
+    const bool sp = c.transform == SAVAD_FE_SPECTROGRAM, mf = c.transform == SAVAD_FE_MFCC;
     const int F = c.deltas ? Fo / 3 : Fo;
-    int* gmax = reinterpret_cast<int*>(workspace);
-    float* sig = workspace + w.sig;
+    int* gmax = reinterpret_cast<int*>(at(workspace, w.gmax));
+    float *sig = at(workspace, w.sig), *spec = at(workspace, w.spec), *db = at(workspace, w.db);
     const float* src;
     if (!sp) {  // centred: the reflect-padded signal, always materialised (aligned whatever the audio pointer)
         const long total = n_samples + c.n_fft + SLACK;
@@ -1817,27 +1614,11 @@ SAVAD_EXPORT int savad_frontend(const savad_frontend_config* config, const float
             src = sig;
         }
     }
-    StftArgs a;
-    a.src = src + g.k0;
-    a.tab = tb.d_dft;
-    a.out = sp ? features : workspace + w.spec;
-    a.gmax = c.transform == SAVAD_FE_MFCC ? gmax : nullptr;
-    a.n_frames = N;
-    a.hop = g.hop;
-    a.kg = g.kg;
-    a.rblocks = g.rblocks;
-    a.nb = g.nb;
-    a.n_fft = g.n_fft;
-    a.ld = sp ? Fo : g.nbs;
-    a.magnitude = sp;
+    const StftArgs a{src + g.k0, d_dft, sp ? features : spec, mf ? gmax : nullptr, N, g.hop, g.kg, g.rblocks, g.nb, g.n_fft, sp ? Fo : g.nbs, sp};
     const int wgs = (N + 32 * FT - 1) / (32 * FT);
-    if (g.hop % 4 == 0)
-        hipLaunchKernelGGL(stft_kernel<true>, dim3(wgs), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL(stft_kernel<false>, dim3(wgs), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((g.hop % 4 == 0 ? stft_kernel<true> : stft_kernel<false>), dim3(wgs), dim3(256), 0, st, a);
     if (!sp) {
-        const bool mf = c.transform == SAVAD_FE_MFCC;
-        FeGemm m{workspace + w.spec, (long)g.nbs, tb.d_mel, mf ? workspace + w.db : features, mf ? (long)c.n_mels : (long)Fo, N, c.n_mels, g.nb, gmax};
+        FeGemm m{spec, (long)g.nbs, d_mel, mf ? db : features, mf ? (long)c.n_mels : (long)Fo, N, c.n_mels, g.nb, gmax};
         const dim3 gm((c.n_mels + GT - 1) / GT, (N + GT - 1) / GT);
         if (c.transform == SAVAD_FE_MEL)
             hipLaunchKernelGGL((fe_gemm_kernel<EPI_NONE, false>), gm, dim3(256), 0, st, m);
@@ -1845,11 +1626,11 @@ SAVAD_EXPORT int savad_frontend(const savad_frontend_config* config, const float
             hipLaunchKernelGGL((fe_gemm_kernel<EPI_LOG, false>), gm, dim3(256), 0, st, m);
         else {
             hipLaunchKernelGGL((fe_gemm_kernel<EPI_DB, false>), gm, dim3(256), 0, st, m);
-            FeGemm d{workspace + w.db, (long)c.n_mels, tb.d_dct, features, (long)Fo, N, c.n_mfcc, c.n_mels, gmax};
+            FeGemm d{db, (long)c.n_mels, d_dct, features, (long)Fo, N, c.n_mfcc, c.n_mels, gmax};
             hipLaunchKernelGGL((fe_gemm_kernel<EPI_NONE, true>), dim3((c.n_mfcc + GT - 1) / GT, (N + GT - 1) / GT), dim3(256), 0, st, d);
         }
     }
-    if (c.deltas) hipLaunchKernelGGL(delta_kernel, dim3(grid_for((long)N * F)), dim3(256), 0, st, features, N, F, (long)Fo, tb.d_sg);
+    if (c.deltas) hipLaunchKernelGGL(delta_kernel, dim3(grid_for((long)N * F)), dim3(256), 0, st, features, N, F, (long)Fo, d_sg);
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }
@@ -1857,89 +1638,76 @@ SAVAD_EXPORT int savad_frontend(const savad_frontend_config* config, const float
 // ---- audio ingest: channel average and resampling to 16 kHz on the device (savad_ingest.h) ----------------------------------
 namespace {
 
-struct RsHost {   // per source rate, host side: the plan, the scaled table with its differences, the time segments
-    savad::ingest::Plan plan;
-    std::vector<double> win, delta;
-    std::vector<savad::ingest::Seg> segs;
+struct RsHost {   // per source rate, host side: the plan and the time segments
+    ingest::Plan plan;
+    std::vector<ingest::Seg> segs;
     long long k_end = 0;
 };
-struct RsDev {
-    double2* d_tab = nullptr;
-    savad::ingest::Seg* d_segs = nullptr;
-    int n_cu = 0;
-};
-std::mutex g_rs_mutex;
 std::vector<double> g_rs_window;            // the caller's "kaiser_fast" half window (savad_resample_set_window)
 std::map<int, RsHost> g_rs_host;            // rate -> host tables; process lifetime
-std::map<std::pair<int, int>, RsDev> g_rs_dev;   // (device, rate) -> uploaded tables; process lifetime
 int g_rs_table_mode = 0;                    // 0 = table in LDS, 1 = through the cache
+using RsTables = DeviceTables<int, double2, ingest::Seg>;   // rate -> (win, delta) pairs | time segments
 
 int rs_check_rate(int rate) {
-    if (rate < savad::ingest::RATE_MIN || rate > savad::ingest::RATE_MAX)
-        return fail(SAVAD_E_UNSUPPORTED, "source rate %d Hz outside the limit %d <= rate <= %d", rate, savad::ingest::RATE_MIN, savad::ingest::RATE_MAX);
+    if (rate < ingest::RATE_MIN || rate > ingest::RATE_MAX)
+        return fail(SAVAD_E_UNSUPPORTED, "source rate %d Hz outside the limit %d <= rate <= %d", rate, ingest::RATE_MIN, ingest::RATE_MAX);
     return SAVAD_OK;
 }
 
-// plan and time segments need no table: the host-only helpers (length, span samples, segments) work without a window
-int rs_host(int rate, bool need_table, const RsHost** out) {
+// A rate's plan and time segments need no window: the host-only helpers (length, span samples, segments) work without one.
+// The caller holds g_audio_mutex.
+int rs_host(int rate, const RsHost** out) {
     namespace in = savad::ingest;
     int rc;
     if ((rc = rs_check_rate(rate))) return rc;
-    std::lock_guard<std::mutex> lock(g_rs_mutex);
-    RsHost& h = g_rs_host[rate];
-    if (h.segs.empty()) {
+    auto it = g_rs_host.find(rate);
+    if (it == g_rs_host.end()) {
+        RsHost h;
         h.plan = in::plan_for(rate);
         h.segs = in::time_segments(h.plan.inc, &h.k_end);
-        if (h.segs.empty()) {
-            g_rs_host.erase(rate);
-            return fail(SAVAD_E_UNSUPPORTED, "source rate %d Hz: its time register needs more than %d segments", rate, in::MAX_SEGS);
-        }
-        if (in::lds_bytes(h.plan, true) > (size_t)in::LDS_BYTES_MAX) {
-            g_rs_host.erase(rate);
+        if (h.segs.empty()) return fail(SAVAD_E_UNSUPPORTED, "source rate %d Hz: its time register needs more than %d segments", rate, in::MAX_SEGS);
+        if (in::lds_bytes(h.plan, true) > (size_t)in::LDS_BYTES_MAX)
             return fail(SAVAD_E_UNSUPPORTED, "source rate %d Hz: a block's input span does not fit the LDS next to the table", rate);
-        }
+        it = g_rs_host.emplace(rate, std::move(h)).first;
     }
-    if (need_table && h.win.empty()) {
-        if (g_rs_window.empty()) return fail(SAVAD_E_STATE, "the kaiser_fast half window was never set (savad_resample_set_window)");
-        h.win = g_rs_window;
-        if (h.plan.ratio < 1.0)
-            for (double& v : h.win) v = v * h.plan.ratio;   // resampy: interp_win *= sample_ratio when downsampling
-        h.delta.assign(in::NWIN, 0.0);
-        for (int i = 0; i + 1 < in::NWIN; ++i) h.delta[i] = h.win[i + 1] - h.win[i];   // np.diff; delta[last] = 0
-    }
-    *out = &h;
+    *out = &it->second;
     return SAVAD_OK;
 }
 
-int rs_dev(int rate, const RsHost** host, RsDev* out) {
-    namespace in = savad::ingest;
-    int rc, dev = 0;
-    if ((rc = rs_host(rate, true, host))) return rc;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_rs_mutex);
-    auto it = g_rs_dev.find({dev, rate});
-    if (it != g_rs_dev.end()) {
-        *out = it->second;
-        return SAVAD_OK;
-    }
-    const RsHost& h = **host;
-    std::vector<double2> tab(in::NWIN);
-    for (int i = 0; i < in::NWIN; ++i) tab[i] = double2{h.win[i], h.delta[i]};
-    RsDev d;
-    HIP_TRY(hipDeviceGetAttribute(&d.n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    HIP_TRY(hipMalloc(&d.d_tab, tab.size() * sizeof(double2)));
-    HIP_TRY(hipMalloc(&d.d_segs, h.segs.size() * sizeof(in::Seg)));
-    HIP_TRY(hipMemcpy(d.d_tab, tab.data(), tab.size() * sizeof(double2), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.d_segs, h.segs.data(), h.segs.size() * sizeof(in::Seg), hipMemcpyHostToDevice));
-    if ((rc = allow_lds(in::resample_kernel<true>, (int)in::lds_bytes(h.plan, true)))) return rc;
-    if ((rc = allow_lds(in::resample_kernel<false>, (int)in::lds_bytes(h.plan, false)))) return rc;
-    g_rs_dev[{dev, rate}] = d;
-    *out = d;
+// the caller's window as the rate's kernel reads it (ingest::scaled_window), while g_audio_mutex is held
+int rs_window(const RsHost& h, std::vector<double>& win, std::vector<double>& delta) {
+    if (g_rs_window.empty()) return fail(SAVAD_E_STATE, "the kaiser_fast half window was never set (savad_resample_set_window)");
+    ingest::scaled_window(h.plan, g_rs_window, win, delta);
     return SAVAD_OK;
+}
+
+// the rate's tables on the current device (the caller holds g_audio_mutex)
+int rs_tables(int rate, const RsHost& h, RsTables::Ptrs* t, int* n_cu) {
+    return RsTables::get(rate, [&h](RsTables::Host& up) {
+        auto& [tab, segs] = up;
+        std::vector<double> win, delta;
+        if (int rc = rs_window(h, win, delta)) return rc;
+        for (int i = 0; i < ingest::NWIN; ++i) tab.push_back(double2{win[i], delta[i]});
+        segs = h.segs;
+        return (int)SAVAD_OK;
+    }, t, n_cu);
 }
 
 long rs_n_out(const savad::ingest::Plan& p, long n) { return (long)((double)n * p.ratio); }          // int(n * ratio)
 long rs_n_fix(const savad::ingest::Plan& p, long n) { return (long)ceil((double)n * p.ratio); }     // ceil(n * ratio)
+
+// savad_resample_span_samples for a rate other than 16 kHz
+int rs_span_samples(const RsHost& h, long n_samples, long out_first, long out_count, long* first, long* count) {
+    const long n_fix = rs_n_fix(h.plan, n_samples), n_out = rs_n_out(h.plan, n_samples);
+    if (out_first + out_count > n_fix) return fail(SAVAD_E_INVALID, "output span [%ld, +%ld) of %ld", out_first, out_count, n_fix);
+    if (n_out > h.k_end) return fail(SAVAD_E_UNSUPPORTED, "%ld samples: beyond the time-register table", n_samples);
+    const long o1 = out_first + out_count < n_out ? out_first + out_count : n_out;
+    long long a = 0, c = 0;   // nothing but fix_length's zeros (or an empty span): no input is read
+    if (o1 > out_first) savad::ingest::span_inputs(h.plan, h.segs, n_samples, out_first, o1, &a, &c);
+    *first = (long)a;
+    *count = (long)c;
+    return SAVAD_OK;
+}
 
 }  // namespace
 
@@ -1953,7 +1721,7 @@ SAVAD_EXPORT long savad_resample_length(long n_samples, int rate) {
 
 SAVAD_EXPORT int savad_resample_set_window(const double* half_window) {
     if (!half_window) return fail(SAVAD_E_INVALID, "null window");
-    std::lock_guard<std::mutex> lock(g_rs_mutex);
+    std::lock_guard<std::mutex> lock(g_audio_mutex);
     if (!g_rs_window.empty()) {
         if (memcmp(g_rs_window.data(), half_window, sizeof(double) * savad::ingest::NWIN) == 0) return SAVAD_OK;
         return fail(SAVAD_E_STATE, "a different half window is already set (tables built from it may be on a device)");
@@ -1965,8 +1733,11 @@ SAVAD_EXPORT int savad_resample_set_window(const double* half_window) {
 SAVAD_EXPORT int savad_resample_prepare(int rate) {
     if (rate == savad::ingest::TARGET) return SAVAD_OK;
     const RsHost* h;
-    RsDev d;
-    return rs_dev(rate, &h, &d);
+    RsTables::Ptrs t;
+    int rc, n_cu;
+    std::lock_guard<std::mutex> lock(g_audio_mutex);
+    if ((rc = rs_host(rate, &h))) return rc;
+    return rs_tables(rate, *h, &t, &n_cu);
 }
 
 SAVAD_EXPORT int savad_resample_set_table_mode(int mode) {
@@ -1977,18 +1748,21 @@ SAVAD_EXPORT int savad_resample_set_table_mode(int mode) {
 
 SAVAD_EXPORT int savad_resample_table_host(int rate, double* window, double* delta) {
     const RsHost* h;
+    std::vector<double> win, dlt;
     int rc;
     if (!window) return fail(SAVAD_E_INVALID, "null output");
-    if ((rc = rs_host(rate, true, &h))) return rc;
-    memcpy(window, h->win.data(), sizeof(double) * savad::ingest::NWIN);
-    if (delta) memcpy(delta, h->delta.data(), sizeof(double) * savad::ingest::NWIN);
+    std::lock_guard<std::mutex> lock(g_audio_mutex);
+    if ((rc = rs_host(rate, &h)) || (rc = rs_window(*h, win, dlt))) return rc;
+    memcpy(window, win.data(), sizeof(double) * savad::ingest::NWIN);
+    if (delta) memcpy(delta, dlt.data(), sizeof(double) * savad::ingest::NWIN);
     return SAVAD_OK;
 }
 
 SAVAD_EXPORT int savad_resample_segments_host(int rate, int max, long* first, double* time, double* step, long* covered) {
     const RsHost* h;
     int rc;
-    if ((rc = rs_host(rate, false, &h))) return rc;
+    std::lock_guard<std::mutex> lock(g_audio_mutex);
+    if ((rc = rs_host(rate, &h))) return rc;
     const int n = (int)h->segs.size();
     if (covered) *covered = (long)h->k_end;
     if (max > 0 && (!first || !time || !step)) return fail(SAVAD_E_INVALID, "null output");
@@ -2010,21 +1784,9 @@ SAVAD_EXPORT int savad_resample_span_samples(long n_samples, int rate, long out_
     }
     const RsHost* h;
     int rc;
-    if ((rc = rs_host(rate, false, &h))) return rc;
-    const long n_fix = rs_n_fix(h->plan, n_samples), n_out = rs_n_out(h->plan, n_samples);
-    if (out_first + out_count > n_fix) return fail(SAVAD_E_INVALID, "output span [%ld, +%ld) of %ld", out_first, out_count, n_fix);
-    if (n_out > h->k_end) return fail(SAVAD_E_UNSUPPORTED, "%ld samples: beyond the time-register table", n_samples);
-    const long o1 = out_first + out_count < n_out ? out_first + out_count : n_out;
-    if (o1 <= out_first) {   // nothing but fix_length's zeros (or an empty span): no input is read
-        *first = 0;
-        *count = 0;
-        return SAVAD_OK;
-    }
-    long long a, c;
-    savad::ingest::span_inputs(h->plan, h->segs, n_samples, out_first, o1, &a, &c);
-    *first = (long)a;
-    *count = (long)c;
-    return SAVAD_OK;
+    std::lock_guard<std::mutex> lock(g_audio_mutex);
+    if ((rc = rs_host(rate, &h))) return rc;
+    return rs_span_samples(*h, n_samples, out_first, out_count, first, count);
 }
 
 SAVAD_EXPORT int savad_resample_span(const float* audio, long audio_first, long audio_count, long n_samples, int rate, long out_first,
@@ -2036,39 +1798,38 @@ SAVAD_EXPORT int savad_resample_span(const float* audio, long audio_first, long 
     if (out_count == 0) return SAVAD_OK;
     if (!out || (audio_count > 0 && !audio)) return fail(SAVAD_E_INVALID, "null pointer");
     long need_first, need_count;
-    int rc;
-    if ((rc = savad_resample_span_samples(n_samples, rate, out_first, out_count, &need_first, &need_count))) return rc;
+    int rc, n_cu;
     if (rate == in::TARGET) {   // a 16 kHz source is a plain copy
+        if ((rc = savad_resample_span_samples(n_samples, rate, out_first, out_count, &need_first, &need_count))) return rc;
         if (out_first < audio_first || out_first + out_count > audio_first + audio_count)
             return fail(SAVAD_E_INVALID, "the slice [%ld, +%ld) does not hold samples [%ld, +%ld)", audio_first, audio_count, out_first, out_count);
         HIP_TRY(hipMemcpyAsync(out, audio + (out_first - audio_first), sizeof(float) * (size_t)out_count, hipMemcpyDeviceToDevice, st));
         return SAVAD_OK;
     }
     const RsHost* h;
-    if ((rc = rs_host(rate, false, &h))) return rc;
-    if (need_count > 0) {   // (the slice may start after the aligned *first, as long as it holds every sample that is read)
-        long lo = (long)in::time_at(h->segs, out_first) - h->plan.taps + 1;
-        if (lo < 0) lo = 0;
-        if (audio_first > lo || audio_first + audio_count < need_first + need_count)
-            return fail(SAVAD_E_INVALID, "the slice [%ld, +%ld) does not hold the samples outputs [%ld, +%ld) read: [%ld, +%ld) (savad_resample_span_samples)",
-                        audio_first, audio_count, out_first, out_count, need_first, need_count);
+    RsTables::Ptrs tb;
+    {
+        std::lock_guard<std::mutex> lock(g_audio_mutex);
+        if ((rc = rs_host(rate, &h)) || (rc = rs_span_samples(*h, n_samples, out_first, out_count, &need_first, &need_count))) return rc;
+        if (need_count > 0) {   // (the slice may start after the aligned *first, as long as it holds every sample that is read)
+            long lo = (long)in::time_at(h->segs, out_first) - h->plan.taps + 1;
+            if (lo < 0) lo = 0;
+            if (audio_first > lo || audio_first + audio_count < need_first + need_count)
+                return fail(SAVAD_E_INVALID, "the slice [%ld, +%ld) does not hold the samples outputs [%ld, +%ld) read: [%ld, +%ld) (savad_resample_span_samples)",
+                            audio_first, audio_count, out_first, out_count, need_first, need_count);
+        }
+        if ((rc = rs_tables(rate, *h, &tb, &n_cu))) return rc;
     }
-    RsDev d;
-    if ((rc = rs_dev(rate, &h, &d))) return rc;
+    const auto [d_tab, d_segs] = tb;
     const bool in_lds = g_rs_table_mode == 0;
     const long blocks = (out_count + in::BLOCK - 1) / in::BLOCK;
-    const long cap = in_lds ? d.n_cu : 2L * d.n_cu;   // resident workgroups: one per CU around the table, two without it
+    const long cap = in_lds ? n_cu : 2L * n_cu;   // resident workgroups: one per CU around the table, two without it
     const int grid = (int)(blocks < cap ? blocks : cap);
     const size_t lds = in::lds_bytes(h->plan, in_lds);
     const long long n_out = rs_n_out(h->plan, n_samples);
-    if (in_lds)
-        hipLaunchKernelGGL(in::resample_kernel<true>, dim3(grid), dim3(in::BLOCK), lds, st, audio, (long long)audio_first, (long long)audio_count,
-                           (long long)n_samples, (long long)out_first, (long long)out_count, n_out, d.d_tab, d.d_segs, (int)h->segs.size(),
-                           h->plan.scale, h->plan.step, h->plan.taps, h->plan.span, out);
-    else
-        hipLaunchKernelGGL(in::resample_kernel<false>, dim3(grid), dim3(in::BLOCK), lds, st, audio, (long long)audio_first, (long long)audio_count,
-                           (long long)n_samples, (long long)out_first, (long long)out_count, n_out, d.d_tab, d.d_segs, (int)h->segs.size(),
-                           h->plan.scale, h->plan.step, h->plan.taps, h->plan.span, out);
+    hipLaunchKernelGGL((in_lds ? in::resample_kernel<true> : in::resample_kernel<false>), dim3(grid), dim3(in::BLOCK), lds, st, audio,
+                       (long long)audio_first, (long long)audio_count, (long long)n_samples, (long long)out_first, (long long)out_count, n_out,
+                       d_tab, d_segs, (int)h->segs.size(), h->plan.scale, h->plan.step, h->plan.taps, h->plan.span, out);
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }
@@ -2104,6 +1865,24 @@ SAVAD_EXPORT int savad_ingest_downmix(const void* raw, int dtype, int channels, 
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }
+
+// What depends on the device alone, once per device: its compute units, and each LDS limit at its kernel's maximum.  (Down here: a
+// kernel template's place in the code object follows its first mention in this file, and the launches above keep the kernels' order.)
+namespace {
+int audio_device(int dev, int* n_cu) {
+    if ((size_t)dev >= g_audio_n_cu.size()) g_audio_n_cu.resize(dev + 1, 0);
+    if (!g_audio_n_cu[dev]) {
+        int rc, n = 0;
+        HIP_TRY(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+        if ((rc = allow_lds(mel::logmel_fft_kernel, mel::FFT_LDS_BYTES))) return rc;
+        if ((rc = allow_lds(ingest::resample_kernel<true>, ingest::LDS_BYTES_MAX))) return rc;   // rs_host refuses a rate that needs more
+        if ((rc = allow_lds(ingest::resample_kernel<false>, ingest::LDS_BYTES_MAX - ingest::NWIN * 16))) return rc;
+        g_audio_n_cu[dev] = n;
+    }
+    *n_cu = g_audio_n_cu[dev];
+    return SAVAD_OK;
+}
+}  // namespace
 
 // ---- post-processing (host arrays; savad_post.h) ------------------------------------------------
 SAVAD_EXPORT int savad_trim_voice_activity(const uint8_t* pred, int n, int min_vally, int min_hill, int hang_before,

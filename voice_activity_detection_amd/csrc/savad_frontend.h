@@ -17,171 +17,16 @@
 //                 an [N][3F] matrix whose first F columns the transform wrote.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <math.h>
 
-#include <vector>
-
+#include "savad_audio_host.h"   // geometry, tables and workspace layout: pure host code
 #include "savad_device.h"
 
 namespace savad {
 namespace fe {
 
-enum { SPECTROGRAM = 0, MEL = 1, LOGMEL = 2, MFCC = 3 };
 enum { EPI_NONE = 0, EPI_LOG = 1, EPI_DB = 2 };
 
-constexpr int RB = 4;         // DFT row blocks (32 rows each) per wave pass
 constexpr int FT = 2;         // 32-frame tiles per workgroup
-constexpr int SLACK = 64;     // floats of readable (finite) slack after a padded signal: the K range may end past the frame
-constexpr int DELTA_W = 9;    // librosa.feature.delta(width=9)
-
-// geometry of one configuration (host and device agree on it; every field derives from the config)
-struct Geo {
-    int n_fft, hop, win, lpad;  // lpad = (n_fft - win) / 2: librosa pad_center / torch.stft's window placement
-    int k0, kr, kg;             // K range: frame samples [k0, k0 + kr), k0 = lpad rounded down to 4, kr = 8 kg
-    int rows, rblocks;          // DFT rows (2 ceil(n_fft / 2)) and row blocks padded to a multiple of RB
-    int nb, nbs;                // bins (n_fft / 2 + 1) and the power workspace's row stride (multiple of 4)
-};
-
-inline Geo geometry(int n_fft, int hop, int win) {
-    Geo g;
-    g.n_fft = n_fft;
-    g.hop = hop;
-    g.win = win;
-    g.lpad = (n_fft - win) / 2;
-    g.k0 = g.lpad & ~3;
-    g.kg = (g.lpad + win - g.k0 + 7) / 8;
-    g.kr = 8 * g.kg;
-    g.rows = 2 * ((n_fft + 1) / 2);
-    g.rblocks = (g.rows + 32 * RB - 1) / (32 * RB) * RB;
-    g.nb = n_fft / 2 + 1;
-    g.nbs = (g.nb + 3) & ~3;
-    return g;
-}
-
-// ---- host tables (float64 arithmetic, stored as fp32) ------------------------------------------------------------------
-
-// Plain DFT matrix [rblocks * 32][kr]: row 0 = re(bin 0), row 1 = re(bin n_fft / 2) for an even n_fft (both imaginary parts
-// vanish; a zero row for an odd one), rows 2b / 2b + 1 = re / im of bin b; column c = frame sample k0 + c.  Window: periodic
-// Hann (librosa's "hann", scipy get_window(fftbins=True)) for the centred transforms, periodic Hamming (torch.hamming_window)
-// for the spectrogram, placed at lpad inside the n_fft-sample frame.
-inline std::vector<float> dft_plain(const Geo& g, bool hamming) {
-    const double PI = 3.14159265358979323846;
-    const int R = g.rblocks * 32;
-    std::vector<float> t((size_t)R * g.kr, 0.0f);
-    for (int r = 0; r < R && r < g.rows; ++r) {
-        int bin = r >> 1;
-        bool im = r & 1;
-        if (r == 1) {
-            if (g.n_fft & 1) continue;
-            bin = g.n_fft / 2;
-            im = false;
-        }
-        for (int c = 0; c < g.kr; ++c) {
-            const int kp = g.k0 + c, j = kp - g.lpad;
-            if (j < 0 || j >= g.win) continue;
-            const double w = hamming ? 0.54 - 0.46 * cos(2.0 * PI * j / g.win) : 0.5 - 0.5 * cos(2.0 * PI * j / g.win);
-            const double ph = 2.0 * PI * (double)((long)bin * kp % g.n_fft) / g.n_fft;
-            t[(size_t)r * g.kr + c] = (float)(w * (im ? -sin(ph) : cos(ph)));
-        }
-    }
-    return t;
-}
-
-// The same in the A-operand fragment order of stft_kernel: [row block][k-group][lane 64][4], element e of lane (i, h) =
-// row 32 rb + i, column 8 G + 4 h + e
-inline std::vector<float> dft_fragments(const Geo& g, const std::vector<float>& plain) {
-    std::vector<float> t((size_t)g.rblocks * g.kg * 256);
-    for (int rb = 0; rb < g.rblocks; ++rb)
-        for (int G = 0; G < g.kg; ++G)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e)
-                    t[(((size_t)rb * g.kg + G) * 64 + lane) * 4 + e] = plain[(size_t)(32 * rb + (lane & 31)) * g.kr + 8 * G + 4 * (lane >> 5) + e];
-    return t;
-}
-
-inline double hz_to_mel_slaney(double f) {
-    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
-    return f >= min_log_hz ? min_log_mel + log(f / min_log_hz) / logstep : f / f_sp;
-}
-inline double mel_to_hz_slaney(double mm) {
-    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
-    return mm >= min_log_mel ? min_log_hz * exp(logstep * (mm - min_log_mel)) : f_sp * mm;
-}
-
-// librosa.filters.mel(sr=16000, n_fft, n_mels, fmin=0, fmax=8000, htk=False, norm="slaney"): [n_mels][nb]
-inline std::vector<float> mel_filterbank(int n_fft, int n_mels) {
-    const int nb = n_fft / 2 + 1;
-    std::vector<double> mel_f(n_mels + 2);
-    const double m_lo = hz_to_mel_slaney(0.0), m_hi = hz_to_mel_slaney(8000.0);
-    for (int i = 0; i < n_mels + 2; ++i) mel_f[i] = mel_to_hz_slaney(m_lo + (m_hi - m_lo) * i / (n_mels + 1));
-    std::vector<float> M((size_t)n_mels * nb, 0.0f);
-    for (int i = 0; i < n_mels; ++i) {
-        const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
-        for (int b = 0; b < nb; ++b) {
-            const double fr = nb > 1 ? 8000.0 * b / (nb - 1) : 0.0;  // fft_frequencies = linspace(0, sr / 2, nb)
-            const double lower = (fr - mel_f[i]) / (mel_f[i + 1] - mel_f[i]);
-            const double upper = (mel_f[i + 2] - fr) / (mel_f[i + 2] - mel_f[i + 1]);
-            M[(size_t)i * nb + b] = (float)(fmax(0.0, fmin(lower, upper)) * enorm);
-        }
-    }
-    return M;
-}
-
-// DCT-II, norm="ortho": [n_mfcc][n_mels]
-inline std::vector<float> dct_ortho(int n_mels, int n_mfcc) {
-    const double PI = 3.14159265358979323846;
-    std::vector<float> D((size_t)n_mfcc * n_mels);
-    for (int k = 0; k < n_mfcc; ++k)
-        for (int n = 0; n < n_mels; ++n)
-            D[(size_t)k * n_mels + n] = (float)(sqrt((k == 0 ? 1.0 : 2.0) / n_mels) * cos(PI * k * (2 * n + 1) / (2.0 * n_mels)));
-    return D;
-}
-
-// Savitzky-Golay rows [order - 1][u][j]: the order-th derivative at position u (0..8) of the degree-`order` least-squares
-// polynomial through 9 points at positions 0..8 = sum_j row[j] x[j].  u = 4 is the interior filter (scipy savgol_coeffs),
-// u = 0..3 / 5..8 the edge rows of mode="interp".
-inline std::vector<float> savgol_rows() {
-    std::vector<float> out(2 * DELTA_W * DELTA_W);
-    for (int order = 1; order <= 2; ++order) {
-        const int P = order + 1;  // polynomial coefficients
-        // normal equations: (V^T V) a = V^T x, V[j][k] = j^k; row(u) = d(u)^T (V^T V)^-1 V^T
-        double A[3][3] = {{0}}, inv[3][3] = {{0}};
-        for (int r = 0; r < P; ++r)
-            for (int c = 0; c < P; ++c)
-                for (int j = 0; j < DELTA_W; ++j) A[r][c] += pow((double)j, r + c);
-        for (int r = 0; r < P; ++r) inv[r][r] = 1.0;
-        for (int c = 0; c < P; ++c) {  // Gauss-Jordan (symmetric positive definite: no pivoting needed)
-            const double p = A[c][c];
-            for (int k = 0; k < P; ++k) {
-                A[c][k] /= p;
-                inv[c][k] /= p;
-            }
-            for (int r = 0; r < P; ++r)
-                if (r != c) {
-                    const double f = A[r][c];
-                    for (int k = 0; k < P; ++k) {
-                        A[r][k] -= f * A[c][k];
-                        inv[r][k] -= f * inv[c][k];
-                    }
-                }
-        }
-        for (int u = 0; u < DELTA_W; ++u) {
-            double d[3] = {0, 0, 0};  // d/du^order of u^k
-            for (int k = order; k < P; ++k) {
-                double f = 1.0;
-                for (int q = 0; q < order; ++q) f *= (k - q);
-                d[k] = f * pow((double)u, k - order);
-            }
-            for (int j = 0; j < DELTA_W; ++j) {
-                double v = 0.0;
-                for (int r = 0; r < P; ++r)
-                    for (int c = 0; c < P; ++c) v += d[r] * inv[r][c] * pow((double)j, c);
-                out[((size_t)(order - 1) * DELTA_W + u) * DELTA_W + j] = (float)v;
-            }
-        }
-    }
-    return out;
-}
 
 // ---- device ------------------------------------------------------------------------------------------------------------
 

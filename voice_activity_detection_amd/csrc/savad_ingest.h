@@ -25,115 +25,12 @@
 // binary search.  No per-sample array of times exists anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdint.h>
 
-#include <vector>
+#include "savad_audio_host.h"   // constants, Seg, Plan, time_segments: pure host code
 
 namespace savad {
 namespace ingest {
-
-constexpr int NWIN = 8193;        // resampy "kaiser_fast": 16 zero crossings x 512 entries + 1
-constexpr int NUM_TABLE = 512;    // entries per zero crossing (precision 9)
-constexpr int TARGET = 16000;
-constexpr int BLOCK = 1024;       // outputs per workgroup pass: 16 waves, 4 per SIMD, around one table in LDS
-constexpr int MAX_SEGS = 256;     // time-register segments (44.1 kHz needs 49 for 2^45 input samples)
-constexpr int RATE_MIN = 1000, RATE_MAX = 100000;
-constexpr int LDS_BYTES_MAX = 160 * 1024;
-constexpr double T_END = 35184372088832.0;  // 2^45 input samples: where the segment walk stops
-
-struct Seg {
-    long long k0;  // first output sample of the segment
-    double t0;     // its time register
-    double s;      // exact step between consecutive time registers inside the segment
-};
-
-struct Plan {
-    double ratio, scale, inc;  // 16000 / rate; min(1, ratio); 1 / ratio  (resampy: sample_ratio, scale, time_increment)
-    int step;                  // int(scale * 512): table stride of one tap
-    int taps;                  // upper bound of a wing's length: 8193 / step
-    int span;                  // LDS floats of a block's input span
-};
-
-inline Plan plan_for(int rate) {
-    Plan p;
-    p.ratio = (double)TARGET / (double)rate;
-    p.scale = p.ratio < 1.0 ? p.ratio : 1.0;
-    p.inc = 1.0 / p.ratio;
-    p.step = (int)(p.scale * NUM_TABLE);
-    p.taps = NWIN / p.step;
-    // n(last lane) - n(first lane) <= ceil((BLOCK - 1) * inc) + 1 (the register's rounding stays far below one sample)
-    p.span = (int)ceil((BLOCK - 1) * p.inc) + 2 + 2 * p.taps + 2;
-    return p;
-}
-
-inline size_t lds_bytes(const Plan& p, bool table_in_lds) {
-    return (table_in_lds ? (size_t)NWIN * 16 : 0) + (size_t)p.span * sizeof(float);
-}
-
-// (k_0, t_0, s) segments of the time register for increment c, up to T_END; *k_end = the first output NOT covered.
-// Empty when more than MAX_SEGS segments would be needed (a tie binade that holds many steps).
-inline std::vector<Seg> time_segments(double c, long long* k_end) {
-    std::vector<Seg> v;
-    volatile double t = 0.0;  // (volatile: every addition below is the float64 addition resampy makes, never folded)
-    long long k = 0;
-    while (t < T_END) {
-        if ((int)v.size() >= MAX_SEGS) {
-            v.clear();
-            break;
-        }
-        const double tc = t;
-        volatile double t1 = tc + c;
-        if (tc <= 0.0) {
-            v.push_back(Seg{k, tc, c});
-            k += 1;
-            t = t1;
-            continue;
-        }
-        const int e = ilogb(tc);
-        const double u = ldexp(1.0, e - 52), hi = ldexp(1.0, e + 1);
-        const double q = c / (0.5 * u);  // exact (a power of two): c in half ulps of t
-        const bool tie = q == floor(q) && fmod(q, 2.0) == 1.0;
-        const double s = t1 - tc;  // exact
-        if (t1 >= hi || tie || s <= 0.0) {
-            if (s <= 0.0) break;  // (increment below half an ulp: beyond T_END for every supported rate)
-            v.push_back(Seg{k, tc, s});
-            k += 1;
-            t = t1;
-            continue;
-        }
-        const long long T = (long long)(tc / u), S = (long long)(s / u), H = 1LL << 53;
-        const long long m = (H - 1 - T) / S;  // t_0 + j s stays below 2^(e+1) for j = 0 .. m
-        v.push_back(Seg{k, tc, s});
-        k += m + 1;
-        volatile double tm = tc + (double)m * s;  // exact
-        t = tm + c;                               // the crossing: a true addition
-    }
-    *k_end = k;
-    return v;
-}
-
-inline double time_at(const std::vector<Seg>& segs, long long k) {
-    size_t lo = 0, hi = segs.size();
-    while (hi - lo > 1) {
-        const size_t mid = (lo + hi) / 2;
-        if (segs[mid].k0 <= k) lo = mid; else hi = mid;
-    }
-    return segs[lo].t0 + (double)(k - segs[lo].k0) * segs[lo].s;
-}
-
-// the input samples outputs [o0, o1) read (o1 <= int(n_in * ratio), o0 < o1): a wing holds at most `taps` taps, the left one
-// x[n], x[n-1] ..., the right one x[n+1], x[n+2] ...  *first is rounded down to a multiple of 4.
-inline void span_inputs(const Plan& p, const std::vector<Seg>& segs, long long n_in, long long o0, long long o1, long long* first, long long* count) {
-    const long long n_lo = (long long)time_at(segs, o0), n_hi = (long long)time_at(segs, o1 - 1);
-    long long a = n_lo - p.taps + 1, b = n_hi + p.taps + 1;
-    if (a < 0) a = 0;
-    a = a / 4 * 4;
-    if (b > n_in) b = n_in;
-    if (b < a) b = a;
-    *first = a;
-    *count = b - a;
-}
 
 __device__ inline double seg_time(const Seg* __restrict__ segs, int nseg, long long k) {
 #pragma clang fp contract(off)

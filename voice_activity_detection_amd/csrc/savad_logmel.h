@@ -13,6 +13,7 @@
 // values feed the mel GEMM from the accumulator registers; log and the [N,80] store finish the
 // tile.  One workgroup = 32 frames, its 4 waves take one pass of 4 DFT row blocks (64 bins) each.
 #pragma once
+#include "savad_audio_host.h"   // N_FFT, HOP, ... and the table sizes: defined once, next to the builders
 #include "savad_device.h"
 #include <type_traits>
 
@@ -27,11 +28,6 @@ __device__ __forceinline__ void static_for(F&& f) {
         static_for<B + 1, E>(f);
     }
 }
-
-constexpr int N_FFT = 512, HOP = 160, WIN = 400, N_MELS = 80, LPAD = (N_FFT - WIN) / 2;  // LPAD = 56
-constexpr int KG = WIN / 8;                    // 50 k-groups of 8 samples
-constexpr int DFT_FRAG_FLOATS = 16 * KG * 256;  // [row block 16][G 50][lane 64][4]
-constexpr int MEL_FRAG_FLOATS = 4 * 3 * 4 * 2 * 256;  // [pass 4][mel block 3][row block 4][g pair 2][lane 64][4]
 
 // y_pad[j] = y[reflect(j - 256)], j in [0, n + 512)   (numpy.pad(mode="reflect"))
 __global__ void reflect_pad_kernel(const float* __restrict__ y, int n, float* __restrict__ ypad) {
@@ -212,9 +208,7 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) void logmel_kernel(cons
 //
 // One persistent workgroup per CU (all A operands of a wave -- 164 registers -- are loaded once), samples are read
 // straight from the caller's audio (reflect padding is materialised for the edge frames only).
-constexpr int FFT_T1_FLOATS = 4 * 13 * 256;   // [wave 4][k-step 13][lane 64][n2 & 3]
-constexpr int FFT_T3_FLOATS = 16 * 4 * 256;   // [group 16][n2 >> 2][lane 64][n2 & 3]
-constexpr int FFT_TM_FLOATS = 16 * 3 * 256;   // [group 16][t >> 2][lane 64][t & 3], t = 0..9 (10, 11 unused)
+// (operand tables t1, t3, tm: mel::fft_tables and FFT_T*_FLOATS in savad_audio_host.h)
 constexpr int FFT_YLD = 132;                  // LDS floats per (reader wave, frame): [re|im][n2 16][k1 & 3] + 4 (conflict-free b128)
 constexpr int FFT_Y_FLOATS = 4 * 32 * FFT_YLD;
 constexpr int FFT_PART_FLOATS = 4 * 3 * 4 * 256;

@@ -187,7 +187,7 @@ def load_wav_mono16k(path) -> np.ndarray:
     return resample_to_16k(pcm, rate)
 
 
-_HOP, _N_FFT = 160, 512  # savad_logmel.h: HOP, N_FFT (frames = 1 + n // hop; workspace = padded signal + slack)
+_HOP = 160  # savad_audio_host.h: mel::HOP (frames = 1 + n // hop)
 
 
 def pcm16_to_f32(pcm: torch.Tensor) -> torch.Tensor:
@@ -345,12 +345,11 @@ def log_mel(audio, device="cuda", out: Optional[torch.Tensor] = None) -> torch.T
         raise _lib.SavadError("the log-mel front-end runs only on a HIP device (no CPU fallback)")
     n = y.numel()
     frames = 1 + n // _HOP
-    ws_floats = n + _N_FFT + 64  # savad_logmel_workspace_bytes(n) / 4
     idx = y.device.index if y.device.index is not None else torch.cuda.current_device()
     if idx != torch.cuda.current_device():
         with torch.cuda.device(idx):
             return log_mel(y, y.device, out)
-    buf = torch.empty(ws_floats, dtype=torch.float32, device=y.device)
+    buf = torch.empty(lib.savad_logmel_workspace_bytes(n) // 4, dtype=torch.float32, device=y.device)
     if out is None:
         out = torch.empty((frames, 80), dtype=torch.float32, device=y.device)
     elif tuple(out.shape) != (frames, 80) or out.dtype != torch.float32 or out.device != y.device or not out.is_contiguous():
