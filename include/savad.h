@@ -469,6 +469,72 @@ long savad_eval_counts_host(const float* probs, int N, int W, const uint8_t* lab
                             long* counters, uint8_t* seg, long seg_cap);
 int savad_eval_set_block(int elems);
 
+/* LIVE SESSIONS: audio fed as it arrives, many streams per tick (csrc/savad_live_plan.h, csrc/savad_live.h).  The rows a stream's
+ * ticks and its finish emit, concatenated, are savad_logmel + savad_predict_probabilities of the finished recording, row for row,
+ * however the recording was cut into pushes.  Shipped front-end only (16 kHz mono).  After n samples of an open stream
+ *   K(n) = 0 for n < 257, else (n - 208) / 160 + 1 frames are ready (a frame reads samples 160 f - 208 .. 160 f + 207),
+ *   E(n) = max(0, K(n) - 2 half) rows are final (row f needs the window centred at f + half);
+ * finish computes the frames up to N = 1 + n / 160 with the right-hand reflection and emits rows E .. N - 1.  Latency: 2 half
+ * frames + 208 samples (393 ms at half = 19).
+ * A TICK is: savad_live_plan (HOST arithmetic) writes the tick's tables -- entries (one per stream in the tick), log-mel tiles,
+ * window items, row offsets -- into the caller's host buffer; the caller copies that buffer to the device as it is (the library
+ * uploads nothing, allocates nothing, never synchronises); savad_live_step launches the tick on `stream`: append, log-mel over the
+ * tile table, window gather over the item table, savad_forward per `chunk` items, log-prob history + boost -- a fixed number of
+ * launches whatever the number of streams -- and moves the slots on.  Every entry point that launches takes the table twice:
+ * table_host is validated and counted from, table_dev (the same bytes) is what the kernels read.
+ *   config      streams = slots of the state; max_push_samples = the largest push; half, jump = the window geometry; chunk = items
+ *               per forward (rounded down to whole packed blocks).
+ *   slots       HOST, streams x savad_live_slot, caller-owned, zeroed = all closed.  savad_live_open opens one.
+ *   state       DEVICE, savad_live_state_bytes, 16-byte aligned, caller-owned; needs no initialisation.
+ *   pushes      HOST; data = the DEVICE address the samples will have when the tick runs (float32: 4-byte aligned; int16 PCM,
+ *               converted as savad_pcm16_to_f32 does: 2-byte aligned); n_samples = 0 is legal; finish != 0 ends the stream after
+ *               the push (the slot is closed by the step and may be opened again: nothing of its state is read by the successor).
+ *   rows        HOST, 2 x n_pushes int64 (may be NULL): first row index in the recording and row count of each push.
+ *   probs/mean  DEVICE, [counts.rows, W] and [counts.rows] (mean may be NULL), the pushes' rows in push order.
+ *   workspace   DEVICE, savad_live_workspace_bytes (the handle's current settings), 16-byte aligned; the device table likewise.
+ * Refused before anything is launched: a window longer than 64 frames (SAVAD_E_UNSUPPORTED); a push above max_push_samples, a
+ * closed slot (in the pushes, or in a table that no longer describes the slots), a finish below 257 samples, a slot twice in one
+ * tick, null tables (SAVAD_E_INVALID).
+ * Stage entries (tests hold each to bits): savad_live_append, savad_live_logmel, savad_live_gather (items [first, first + count) ->
+ * windows [count, W, F]), savad_live_boost (logp [counts.items, W, 2] in item order), savad_live_commit (HOST: the slots move on);
+ * savad_live_step = these in order around the forwards. */
+typedef struct savad_live_config {
+    int32_t streams, max_push_samples, half, jump, chunk;
+} savad_live_config;
+typedef struct savad_live_slot {
+    int64_t n_samples; /* pushed so far */
+    int64_t base;      /* library bookkeeping: first sample the state still holds */
+    int32_t open;
+    int32_t phase;     /* library bookkeeping */
+} savad_live_slot;
+typedef struct savad_live_push {
+    int32_t slot, n_samples, dtype /* SAVAD_PCM_FLOAT32 or SAVAD_PCM_INT16 */, finish;
+    const void* data;
+} savad_live_push;
+typedef struct savad_live_counts {
+    int32_t entries, tiles, items, rows;
+    int32_t table_bytes; /* bytes of the table the plan wrote */
+    int32_t W;
+} savad_live_counts;
+long savad_live_ready_frames(long n_samples);
+long savad_live_final_rows(long n_samples, int half);
+int savad_live_state_bytes(const savad_live_config* config, size_t* bytes);
+int savad_live_table_bytes(const savad_live_config* config, int max_pushes, size_t* bytes);
+int savad_live_max_rows(const savad_live_config* config, int* rows_per_stream);
+int savad_live_workspace_bytes(savad_handle h, const savad_live_config* config, int max_pushes, size_t* bytes);
+int savad_live_open(const savad_live_config* config, savad_live_slot* slots, int slot);
+int savad_live_plan(const savad_live_config* config, const savad_live_slot* slots, const savad_live_push* pushes, int n_pushes,
+                    const void* state, void* table_host, size_t table_bytes, savad_live_counts* counts, int64_t* rows);
+int savad_live_append(const savad_live_config* config, const void* table_host, const void* table_dev, void* stream);
+int savad_live_logmel(const savad_live_config* config, const void* table_host, const void* table_dev, void* stream);
+int savad_live_gather(const savad_live_config* config, const void* table_host, const void* table_dev, int first, int count,
+                      float* windows, void* stream);
+int savad_live_boost(const savad_live_config* config, const void* table_host, const void* table_dev, const float* logp, float* probs,
+                     float* mean, void* stream);
+int savad_live_commit(const savad_live_config* config, const void* table_host, savad_live_slot* slots);
+int savad_live_step(savad_handle h, const savad_live_config* config, savad_live_slot* slots, const void* table_host,
+                    const void* table_dev, float* probs, float* mean, void* workspace, size_t workspace_bytes, void* stream);
+
 const char* savad_last_error(void);
 const char* savad_version(void);
 

@@ -4,7 +4,7 @@ voithru/voice-activity-detection: ``SelfAttentiveVAD.forward`` as driven by
 from .seeded import seeded_features, seeded_state_dict, state_dict_spec  # noqa: F401
 
 __all__ = ["SelfAttentiveVAD", "PipelinedVAD", "VADFromScratchPredictor", "ContextResolution", "StreamingPredictor", "seeded_state_dict",
-           "seeded_features", "state_dict_spec"]
+           "seeded_features", "state_dict_spec", "LiveVAD", "LiveSession", "LiveTick"]
 
 
 def __getattr__(name):  # torch / libsavad are imported lazily (seeded.py is numpy-only)
@@ -17,6 +17,9 @@ def __getattr__(name):  # torch / libsavad are imported lazily (seeded.py is num
     if name in ("VADFromScratchPredictor", "ContextResolution", "window_offsets", "StreamingPredictor", "VADPredictParameters"):
         from . import predictor
         return getattr(predictor, name)
+    if name in ("LiveVAD", "LiveSession", "LiveTick"):
+        from . import live
+        return getattr(live, name)
     if name in ("VoiceActivity", "Activity"):
         from . import data_models
         return getattr(data_models, name)

@@ -25,6 +25,22 @@ class savad_frontend_config(ctypes.Structure):
                 ("n_mfcc", c_int32), ("deltas", c_int32)]
 
 
+class savad_live_config(ctypes.Structure):
+    _fields_ = [("streams", c_int32), ("max_push_samples", c_int32), ("half", c_int32), ("jump", c_int32), ("chunk", c_int32)]
+
+
+class savad_live_slot(ctypes.Structure):
+    _fields_ = [("n_samples", c_int64), ("base", c_int64), ("open", c_int32), ("phase", c_int32)]
+
+
+class savad_live_push(ctypes.Structure):
+    _fields_ = [("slot", c_int32), ("n_samples", c_int32), ("dtype", c_int32), ("finish", c_int32), ("data", c_void_p)]
+
+
+class savad_live_counts(ctypes.Structure):
+    _fields_ = [("entries", c_int32), ("tiles", c_int32), ("items", c_int32), ("rows", c_int32), ("table_bytes", c_int32), ("W", c_int32)]
+
+
 # every symbol include/savad.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "savad_create": (c_int, [POINTER(savad_config), POINTER(c_void_p)]),
@@ -106,6 +122,20 @@ SYMBOLS = {
     "savad_eval_sort": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "savad_eval_counts_host": (c_long, [c_void_p, c_int, c_int, c_void_p, c_long, c_float, c_int, c_void_p, c_void_p, c_long]),
     "savad_eval_set_block": (c_int, [c_int]),
+    "savad_live_ready_frames": (c_long, [c_long]),
+    "savad_live_final_rows": (c_long, [c_long, c_int]),
+    "savad_live_state_bytes": (c_int, [c_void_p, POINTER(c_size_t)]),
+    "savad_live_table_bytes": (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
+    "savad_live_max_rows": (c_int, [c_void_p, POINTER(c_int)]),
+    "savad_live_workspace_bytes": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_size_t)]),
+    "savad_live_open": (c_int, [c_void_p, c_void_p, c_int]),
+    "savad_live_plan": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "savad_live_append": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "savad_live_logmel": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "savad_live_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "savad_live_boost": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "savad_live_commit": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "savad_live_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "savad_last_error": (c_char_p, []),
     "savad_version": (c_char_p, []),
 }

@@ -21,6 +21,7 @@
 #include "savad_eval_device.h"
 #include "savad_schedule.h"
 #include "savad_weights.h"
+#include "savad_live.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -1499,6 +1500,221 @@ SAVAD_EXPORT int savad_logmel(const float* audio, int n_samples, float* workspac
     return SAVAD_OK;
 }
 
+// ---- live sessions (savad_live_plan.h: the host plan; savad_live.h: the kernels) ----------------------------------
+namespace {
+
+static_assert(sizeof(savad_live_slot) == sizeof(live::Slot) && sizeof(savad_live_push) == sizeof(live::Push), "live ABI structs");
+
+int live_geometry(const savad_live_config* c, live::Geometry* g) {
+    if (!c) return fail(SAVAD_E_INVALID, "null config");
+    *g = live::geometry(c->streams, c->max_push_samples, c->half, c->jump);
+    if (g->err) return fail(g->err, "%s", g->msg);
+    if (c->chunk < 1) return fail(SAVAD_E_INVALID, "chunk=%d", c->chunk);
+    return SAVAD_OK;
+}
+
+WindowOffsets live_offsets(const live::Geometry& g) {
+    WindowOffsets wo;
+    wo.w = g.W;
+    for (int i = 0; i < g.W; ++i) wo.off[i] = g.off[i];
+    return wo;
+}
+
+// geometry + both copies of a tick's table
+int live_tables(const savad_live_config* c, const void* table_host, const void* table_dev, live::Geometry* g, const live::Header** h) {
+    int rc = live_geometry(c, g);
+    if (rc) return rc;
+    if (!table_host || !table_dev) return fail(SAVAD_E_INVALID, "null table");
+    const live::PlanResult r = live::check_table(*g, table_host, nullptr);
+    if (r.err) return fail(r.err, "%s", r.msg);
+    if ((uintptr_t)table_dev & 15) return fail(SAVAD_E_INVALID, "the device table must be 16-byte aligned");
+    *h = live::header(table_host);
+    return SAVAD_OK;
+}
+
+template <class T>
+const T* live_at(const void* table_dev, int32_t offset) { return reinterpret_cast<const T*>(reinterpret_cast<const char*>(table_dev) + offset); }
+
+// windows [chunk, W, F] | logp [items, W, 2] | the forward's own scratch
+struct LiveWorkspace {
+    int chunk;
+    size_t windows, logp, fwd, fwd_bytes, total;
+};
+int live_workspace(savad_handle m, const live::Geometry& g, int chunk, long max_items, LiveWorkspace* w) {
+    const int unit = live::chunk_items(g, 1);
+    max_items = (max_items + unit - 1) / unit * unit;
+    w->chunk = live::chunk_items(g, chunk);
+    if (w->chunk > max_items) w->chunk = (int)(max_items > unit ? max_items : unit);
+    if (m->cfg.feature_size != g.F) return fail(SAVAD_E_UNSUPPORTED, "the live mode runs the shipped %d-mel front-end; the model takes %d features", g.F, m->cfg.feature_size);
+    int rc = savad_workspace_bytes(m, w->chunk, g.W, &w->fwd_bytes);
+    if (rc) return rc;
+    Arena a;
+    w->windows = a.take(sizeof(float) * (size_t)w->chunk * g.W * g.F);
+    w->logp = a.take(sizeof(float) * (size_t)max_items * g.W * 2);
+    w->fwd = a.take(w->fwd_bytes);
+    w->total = a.off;
+    return SAVAD_OK;
+}
+
+}  // namespace
+
+SAVAD_EXPORT long savad_live_ready_frames(long n_samples) { return n_samples < 0 ? fail(SAVAD_E_INVALID, "n_samples") : live::ready_frames(n_samples); }
+SAVAD_EXPORT long savad_live_final_rows(long n_samples, int half) {
+    return n_samples < 0 || half < 0 ? fail(SAVAD_E_INVALID, "bad argument") : live::final_rows(live::ready_frames(n_samples), half);
+}
+SAVAD_EXPORT int savad_live_state_bytes(const savad_live_config* config, size_t* bytes) {
+    live::Geometry g;
+    if (int rc = live_geometry(config, &g)) return rc;
+    if (!bytes) return fail(SAVAD_E_INVALID, "null argument");
+    *bytes = g.state_bytes();
+    return SAVAD_OK;
+}
+SAVAD_EXPORT int savad_live_table_bytes(const savad_live_config* config, int max_pushes, size_t* bytes) {
+    live::Geometry g;
+    if (int rc = live_geometry(config, &g)) return rc;
+    if (!bytes || max_pushes < 0 || max_pushes > g.streams) return fail(SAVAD_E_INVALID, "max_pushes=%d of %d streams", max_pushes, g.streams);
+    *bytes = live::table_bytes(g, max_pushes);
+    return SAVAD_OK;
+}
+SAVAD_EXPORT int savad_live_max_rows(const savad_live_config* config, int* rows_per_stream) {
+    live::Geometry g;
+    if (int rc = live_geometry(config, &g)) return rc;
+    if (!rows_per_stream) return fail(SAVAD_E_INVALID, "null argument");
+    *rows_per_stream = g.max_rows;
+    return SAVAD_OK;
+}
+SAVAD_EXPORT int savad_live_workspace_bytes(savad_handle m, const savad_live_config* config, int max_pushes, size_t* bytes) {
+    if (!m || !bytes) return fail(SAVAD_E_INVALID, "null argument");
+    live::Geometry g;
+    if (int rc = live_geometry(config, &g)) return rc;
+    if (max_pushes < 0 || max_pushes > g.streams) return fail(SAVAD_E_INVALID, "max_pushes=%d of %d streams", max_pushes, g.streams);
+    LiveWorkspace w;
+    if (int rc = live_workspace(m, g, config->chunk, (long)max_pushes * g.max_items(), &w)) return rc;
+    *bytes = w.total;
+    return SAVAD_OK;
+}
+SAVAD_EXPORT int savad_live_open(const savad_live_config* config, savad_live_slot* slots, int slot) {
+    live::Geometry g;
+    if (int rc = live_geometry(config, &g)) return rc;
+    if (!slots || slot < 0 || slot >= g.streams) return fail(SAVAD_E_INVALID, "slot %d of %d", slot, g.streams);
+    if (slots[slot].open) return fail(SAVAD_E_INVALID, "slot %d is open", slot);
+    slots[slot] = savad_live_slot{0, 0, 1, 0};
+    return SAVAD_OK;
+}
+SAVAD_EXPORT int savad_live_plan(const savad_live_config* config, const savad_live_slot* slots, const savad_live_push* pushes, int n_pushes,
+                                 const void* state, void* table_host, size_t table_bytes, savad_live_counts* counts, int64_t* rows) {
+    live::Geometry g;
+    if (int rc = live_geometry(config, &g)) return rc;
+    if (!slots || !table_host || !counts) return fail(SAVAD_E_INVALID, "null table, slots or counts");
+    if ((uintptr_t)state & 15) return fail(SAVAD_E_INVALID, "the state must be 16-byte aligned");
+    const live::PlanResult r = live::plan_tick(g, reinterpret_cast<const live::Slot*>(slots), reinterpret_cast<const live::Push*>(pushes), n_pushes,
+                                               (uint64_t)(uintptr_t)state, table_host, table_bytes, rows);
+    if (r.err) return fail(r.err, "%s", r.msg);
+    const live::Header* h = live::header(table_host);
+    *counts = savad_live_counts{h->n_entries, h->n_tiles, h->n_items, h->n_rows, h->total, g.W};
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_live_append(const savad_live_config* config, const void* table_host, const void* table_dev, void* stream) {
+    live::Geometry g;
+    const live::Header* h;
+    if (int rc = live_tables(config, table_host, table_dev, &g, &h)) return rc;
+    if (h->n_entries == 0) return SAVAD_OK;
+    const int bx = (h->max_append + live::HEAD_FLOATS + live::TAIL_FLOATS + 255) / 256;
+    hipLaunchKernelGGL(live::append_kernel, dim3(bx < 64 ? bx : 64, h->n_entries < 32768 ? h->n_entries : 32768), dim3(256), 0,
+                       (hipStream_t)stream, live_at<live::Entry>(table_dev, h->o_entries), h->n_entries);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_live_logmel(const savad_live_config* config, const void* table_host, const void* table_dev, void* stream) {
+    live::Geometry g;
+    const live::Header* h;
+    if (int rc = live_tables(config, table_host, table_dev, &g, &h)) return rc;
+    if (h->n_tiles == 0) return SAVAD_OK;
+    int rc, n_cu;
+    MelTables::Ptrs tb;
+    if ((rc = mel_tables(&tb, &n_cu))) return rc;
+    const int grid = h->n_tiles < n_cu ? h->n_tiles : n_cu;
+    hipLaunchKernelGGL(live::logmel_fft_kernel_table, dim3(grid), dim3(256), mel::FFT_LDS_BYTES, (hipStream_t)stream,
+                       live_at<live::Tile>(table_dev, h->o_tiles), h->n_tiles, (const float*)std::get<2>(tb), (const float*)std::get<3>(tb),
+                       (const float*)std::get<4>(tb));
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_live_gather(const savad_live_config* config, const void* table_host, const void* table_dev, int first, int count,
+                                   float* windows, void* stream) {
+    live::Geometry g;
+    const live::Header* h;
+    if (int rc = live_tables(config, table_host, table_dev, &g, &h)) return rc;
+    if (first < 0 || count < 0 || (long)first + count > h->n_items)
+        return fail(SAVAD_E_INVALID, "items [%d,%ld) reach outside the %d items of the tick", first, (long)first + count, h->n_items);
+    if (count == 0) return SAVAD_OK;
+    if (!windows || ((uintptr_t)windows & 15)) return fail(SAVAD_E_INVALID, "windows must be a 16-byte aligned pointer");
+    hipLaunchKernelGGL(live::gather_items_kernel, dim3(grid_for((long)count * g.W * (g.F / 4), 2048)), dim3(256), 0, (hipStream_t)stream,
+                       live_at<live::Entry>(table_dev, h->o_entries), live_at<live::Item>(table_dev, h->o_items), g.F, g.feat_cap, first, count,
+                       live_offsets(g), windows);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_live_boost(const savad_live_config* config, const void* table_host, const void* table_dev, const float* logp,
+                                  float* probs, float* mean, void* stream) {
+    live::Geometry g;
+    const live::Header* h;
+    if (int rc = live_tables(config, table_host, table_dev, &g, &h)) return rc;
+    if (h->n_rows == 0) return SAVAD_OK;
+    if (!probs || (h->n_items > 0 && !logp)) return fail(SAVAD_E_INVALID, "null pointer");
+    hipLaunchKernelGGL(live::boost_history_kernel, dim3(grid_for(h->n_rows, 2048)), dim3(256), 0, (hipStream_t)stream,
+                       live_at<live::Entry>(table_dev, h->o_entries), live_at<int32_t>(table_dev, h->o_rows), h->n_entries, h->n_rows, logp, g.half,
+                       g.logp_cap, live_offsets(g), probs, mean);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_live_commit(const savad_live_config* config, const void* table_host, savad_live_slot* slots) {
+    live::Geometry g;
+    if (int rc = live_geometry(config, &g)) return rc;
+    if (!slots) return fail(SAVAD_E_INVALID, "null slots");
+    const live::PlanResult r = live::check_table(g, table_host, reinterpret_cast<const live::Slot*>(slots));
+    if (r.err) return fail(r.err, "%s", r.msg);
+    live::commit(table_host, reinterpret_cast<live::Slot*>(slots));
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_live_step(savad_handle m, const savad_live_config* config, savad_live_slot* slots, const void* table_host,
+                                 const void* table_dev, float* probs, float* mean, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!m) return fail(SAVAD_E_INVALID, "null handle");
+    live::Geometry g;
+    const live::Header* h;
+    if (int rc = live_tables(config, table_host, table_dev, &g, &h)) return rc;
+    if (!slots) return fail(SAVAD_E_INVALID, "null slots");
+    const live::PlanResult r = live::check_table(g, table_host, reinterpret_cast<const live::Slot*>(slots));
+    if (r.err) return fail(r.err, "%s", r.msg);
+    LiveWorkspace w{};
+    if (h->n_items > 0) {
+        if (int rc = live_workspace(m, g, config->chunk, h->n_items, &w)) return rc;
+        if (!workspace || ((uintptr_t)workspace & 15)) return fail(SAVAD_E_INVALID, "workspace must be a 16-byte aligned pointer");
+        if (workspace_bytes < w.total) return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, w.total);
+    }
+    if (h->n_rows > 0 && !probs) return fail(SAVAD_E_INVALID, "null output");
+    int rc;
+    if ((rc = savad_live_append(config, table_host, table_dev, stream))) return rc;
+    if ((rc = savad_live_logmel(config, table_host, table_dev, stream))) return rc;
+    char* ws = (char*)workspace;
+    float* logp = h->n_items > 0 ? (float*)(ws + w.logp) : nullptr;
+    for (int first = 0; first < h->n_items; first += w.chunk) {
+        const int count = h->n_items - first < w.chunk ? h->n_items - first : w.chunk;
+        float* win = (float*)(ws + w.windows);
+        if ((rc = savad_live_gather(config, table_host, table_dev, first, count, win, stream))) return rc;
+        if ((rc = savad_forward(m, win, count, g.W, logp + (size_t)first * g.W * 2, ws + w.fwd, w.fwd_bytes, stream))) return rc;
+    }
+    if ((rc = savad_live_boost(config, table_host, table_dev, logp, probs, mean, stream))) return rc;
+    live::commit(table_host, reinterpret_cast<live::Slot*>(slots));
+    return SAVAD_OK;
+}
+
 // ---- feature front-end for any transform config (savad_frontend.h) ----------------------------------------------
 namespace {
 
@@ -1877,6 +2093,7 @@ int audio_device(int dev, int* n_cu) {
         if ((rc = allow_lds(mel::logmel_fft_kernel, mel::FFT_LDS_BYTES))) return rc;
         if ((rc = allow_lds(ingest::resample_kernel<true>, ingest::LDS_BYTES_MAX))) return rc;   // rs_host refuses a rate that needs more
         if ((rc = allow_lds(ingest::resample_kernel<false>, ingest::LDS_BYTES_MAX - ingest::NWIN * 16))) return rc;
+        if ((rc = allow_lds(live::logmel_fft_kernel_table, mel::FFT_LDS_BYTES))) return rc;
         g_audio_n_cu[dev] = n;
     }
     *n_cu = g_audio_n_cu[dev];

@@ -103,6 +103,13 @@ __global__ void boost_softmax_kernel(const float* __restrict__ boosted, int N, i
     }
 }
 
+// softmax(z)[1] of one slot's (log p0, log p1): the arithmetic every boost kernel that reads slots as a gather shares
+__device__ __forceinline__ float boost_slot(f32x2 z) {
+    const float mx = fmaxf(z[0], z[1]);
+    const float e0 = expf(z[0] - mx), e1 = expf(z[1] - mx);
+    return e1 / (e0 + e1);
+}
+
 // The same result as scatter + softmax, read the other way round: slot (n, w) of the boosted array was written by
 // window b = n - half - off[w] if that window exists, else it still holds (0, 0) -> 0.5.  Same arithmetic on the same
 // values, no memset, no scatter launch, no positions array.
@@ -115,9 +122,7 @@ __global__ void boost_gather_kernel(const float* __restrict__ logp, int n_items,
             const int b = nrow - half - wo.off[wi];
             f32x2 z = f32x2{0.0f, 0.0f};
             if (b >= 0 && b < n_items) z = *reinterpret_cast<const f32x2*>(logp + ((size_t)b * W + wi) * 2);
-            const float mx = fmaxf(z[0], z[1]);
-            const float e0 = expf(z[0] - mx), e1 = expf(z[1] - mx);
-            const float p = e1 / (e0 + e1);
+            const float p = boost_slot(z);
             probs[(size_t)nrow * W + wi] = p;
             acc += p;
         }

@@ -4,6 +4,7 @@
 // neighbour.  items_first[C + 1] = the exclusive prefix sum of n_c: global item g belongs to the clip c with
 // items_first[c] <= g < items_first[c + 1] (an empty clip, or one too short for a window, owns no g and is never found).
 #pragma once
+#include "savad_aux_kernels.h"   // boost_slot
 #include "savad_device.h"
 
 namespace savad {
@@ -112,9 +113,7 @@ __global__ void boost_gather_batch_kernel(const float* __restrict__ logp, const 
             const int b = local - half - wo.off[wi];
             f32x2 z = f32x2{0.0f, 0.0f};
             if (b >= 0 && b < n_items) z = *reinterpret_cast<const f32x2*>(logp + ((size_t)(item0 + b) * W + wi) * 2);
-            const float mx = fmaxf(z[0], z[1]);
-            const float e0 = expf(z[0] - mx), e1 = expf(z[1] - mx);
-            const float p = e1 / (e0 + e1);
+            const float p = boost_slot(z);
             probs[(size_t)nrow * W + wi] = p;
             acc += p;
         }

@@ -234,9 +234,35 @@ struct FftSrc {
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-__global__ __launch_bounds__(256, 1) void logmel_fft_kernel(FftSrc src, int frame_first, int frame_count, int n_tiles,
-                                                            const float* __restrict__ t1, const float* __restrict__ t3,
-                                                            const float* __restrict__ tm, float* __restrict__ out) {
+// A tile's place, wave-uniform: padded index j is read at src? + 4 j (A below jA_end, B from jB0 on, Y between), the tile's stretch
+// starts at J0 and no frame of its run reads past chunk j_last.
+struct FftWhere {
+    uintptr_t srcA, srcB, srcY;
+    long J0, j_last, jA_end, jB0;
+};
+
+// The tiles of one span of one signal (savad_logmel_span): tile t = frames frame_first + 32 t ... of the launch.
+struct SpanTiles {
+    FftSrc src;
+    int frame_first, frame_count;
+    float* out;
+    __device__ __forceinline__ FftWhere where(int tile) const {
+        // sources as integers: address of padded index j = base + 4 j
+        return FftWhere{(uintptr_t)src.padA - 4 * (uintptr_t)src.jA0, (uintptr_t)src.padB - 4 * (uintptr_t)src.jB0,
+                        (uintptr_t)src.y0 - 4 * (uintptr_t)(N_FFT / 2), (long)HOP * (frame_first + tile * 32) + 48,
+                        (long)HOP * (frame_first + frame_count - 1) + 460,  // the last chunk any frame of the launch reads
+                        src.jA_end, src.jB0};
+    }
+    // frames of the tile - 1 (not clamped: below 0 past the last tile, 31 and more for a full one)
+    __device__ __forceinline__ int room(int tile, int /*n_tiles*/) const { return frame_count - 1 - 32 * tile; }
+    __device__ __forceinline__ float* rows(int tile) const { return out + (size_t)tile * 32 * N_MELS; }
+};
+
+// The tile loop of the factored kernel over the tiles a provider names (SpanTiles above; the tile table of savad_live.h): a frame
+// is a column of every MFMA B operand, so its bits depend on nothing but its own 400 samples.
+template <class Tiles>
+__device__ __forceinline__ void logmel_fft_tiles(const Tiles& tiles, int n_tiles, const float* __restrict__ t1,
+                                                 const float* __restrict__ t3, const float* __restrict__ tm) {
     extern __shared__ __attribute__((aligned(16))) float fft_lds[];
     float* Yl = fft_lds;                                     // [k1 >> 2][frame 32][FFT_YLD]
     float* part = fft_lds + FFT_Y_FLOATS;                    // [wave 4][mel block 3][g 4][lane 64][4]
@@ -261,25 +287,22 @@ __global__ __launch_bounds__(256, 1) void logmel_fft_kernel(FftSrc src, int fram
         const int q = 64 * (wv + 4 * k) + lane, b = q / 41, c = q % 41;
         rel[k] = 160 * b + 4 * (c < 39 ? c : 39);
     }
-    const long j_last = (long)HOP * (frame_first + frame_count - 1) + 460;  // the last chunk any frame of the launch reads
     const unsigned stage_m0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)stage) + 1024u * (unsigned)wv;
-    // sources as integers: address of padded index j = base + 4 j
-    const uintptr_t srcA = (uintptr_t)src.padA - 4 * (uintptr_t)src.jA0, srcB = (uintptr_t)src.padB - 4 * (uintptr_t)src.jB0,
-                    srcY = (uintptr_t)src.y0 - 4 * (uintptr_t)(N_FFT / 2);
     // the six source addresses of this wave's part of a tile's stage
     const float* sptr[6];
     auto stage_ptrs = [&](int tile) {
-        const long J0 = (long)HOP * (frame_first + tile * 32) + 48;
+        const FftWhere at = tiles.where(tile);
+        const long J0 = at.J0;
         const long J1 = J0 + 160 * 37 + 160;  // one past the last chunk the 24 instructions touch
-        if (J0 >= src.jA_end && J1 <= src.jB0 && J1 <= j_last + 4) {  // wave-uniform: every chunk straight from the audio
+        if (J0 >= at.jA_end && J1 <= at.jB0 && J1 <= at.j_last + 4) {  // wave-uniform: every chunk straight from the audio
 #pragma unroll
-            for (int k = 0; k < 6; ++k) sptr[k] = (const float*)(srcY + 4 * (uintptr_t)(J0 + rel[k]));
+            for (int k = 0; k < 6; ++k) sptr[k] = (const float*)(at.srcY + 4 * (uintptr_t)(J0 + rel[k]));
         } else {
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
                 long j = J0 + rel[k];
-                if (j > j_last) j = j_last;
-                const uintptr_t b = (j < src.jA_end) ? srcA : (j >= src.jB0) ? srcB : srcY;
+                if (j > at.j_last) j = at.j_last;
+                const uintptr_t b = (j < at.jA_end) ? at.srcA : (j >= at.jB0) ? at.srcB : at.srcY;
                 sptr[k] = (const float*)(b + 4 * (uintptr_t)j);
             }
         }
@@ -294,7 +317,7 @@ __global__ __launch_bounds__(256, 1) void logmel_fft_kernel(FftSrc src, int fram
     f32x16 acc[4];
     // lanes past the launch's last frame redo that frame: they store the same values to the same place, unpredicated
     auto step1 = [&](int tile) {
-        const int room = frame_count - 1 - 32 * tile, mm = m < room ? m : (room > 0 ? room : 0);
+        const int room = tiles.room(tile, n_tiles), mm = m < room ? m : (room > 0 ? room : 0);
         const float* sp = stage + FFT_SBLK * mm + 16 * h + 4 * wv;
         f32x4 x[13];
 #pragma unroll
@@ -399,8 +422,8 @@ __global__ __launch_bounds__(256, 1) void logmel_fft_kernel(FftSrc src, int fram
         // ---- the next tile's step 1 (MFMA) in one basic block with this tile's sums, log and stores (LDS, VALU): no branch in
         // here (after the last tile step 1 reruns on the stale stage; nobody reads its result)
         {
-            const int room = frame_count - 1 - 32 * tile, fl = tile * 32 + (m < room ? m : room);  // frame inside the launch
-            float* op = out + (size_t)fl * N_MELS + 4 * h;
+            const int room = tiles.room(tile, n_tiles), fl = m < room ? m : room;  // frame inside the tile
+            float* op = tiles.rows(tile) + (size_t)fl * N_MELS + 4 * h;
             step1(next);
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
@@ -421,6 +444,12 @@ __global__ __launch_bounds__(256, 1) void logmel_fft_kernel(FftSrc src, int fram
         for (int i = 0; i < 8; ++i) g_savad_dbg[24 + i] = facc[i];
 #endif
 #undef SAVAD_FFT_DMA
+}
+
+__global__ __launch_bounds__(256, 1) void logmel_fft_kernel(FftSrc src, int frame_first, int frame_count, int n_tiles,
+                                                            const float* __restrict__ t1, const float* __restrict__ t3,
+                                                            const float* __restrict__ tm, float* __restrict__ out) {
+    logmel_fft_tiles(SpanTiles{src, frame_first, frame_count, out}, n_tiles, t1, t3, tm);
 }
 
 }  // namespace mel

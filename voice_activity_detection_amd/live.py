@@ -1,0 +1,224 @@
+"""Live sessions: audio fed as it arrives, many streams per tick (C ABI: the savad_live_* entries of include/savad.h).
+
+What a stream's ticks and its finish return, concatenated, is ``predict_audio_device`` of the finished recording, row for row,
+however the recording was cut into pushes: after n samples (n - 208) // 160 + 1 frames are ready (none below 257 samples), and a row
+is final once the window centred `half` frames after it exists.  The latency of a row is therefore 2 * half frames + 208 samples:
+393 ms at the shipped geometry (half = 19).
+
+One tick of S streams is a fixed number of launches (append, log-mel, window gather and forward per `chunk_size` windows, boost),
+one upload (the tick's tables and every host chunk, from one pinned buffer) and no read-back: every count comes from host arithmetic.
+
+Not built: online post-processing to segments (`trim` needs look-ahead of its own), other sample rates and channel counts, the
+extended front-ends, HIP-graph capture of a tick, a CLI subcommand, more than one GPU.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Iterable, Mapping, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .predictor import ContextResolution, _indexed, _require_hip
+
+_PCM_INT16, _PCM_FLOAT32 = 0, 1   # SAVAD_PCM_*
+
+
+class LiveTick:
+    """The rows one tick made final.  probs [rows, W] and mean [rows] are device tensors holding the slots' rows one after the other;
+    `rows` maps slot -> (first row index in its recording, offset into probs / mean, count); tick[slot] -> (first, probs, mean)."""
+
+    def __init__(self, probs: torch.Tensor, mean: torch.Tensor, rows: "dict[int, tuple[int, int, int]]"):
+        self.probs, self.mean, self.rows = probs, mean, rows
+
+    def __getitem__(self, slot: int):
+        first, at, count = self.rows[slot]
+        return first, self.probs[at:at + count], self.mean[at:at + count]
+
+    def __contains__(self, slot: int) -> bool:
+        return slot in self.rows
+
+    def __len__(self) -> int:
+        return len(self.rows)
+
+
+class LiveVAD:
+    """`streams` slots of live voice-activity detection on one GPU.
+
+        vad = LiveVAD(model, "cuda:0", streams=64, max_push_samples=1600)
+        a, b = vad.open(), vad.open()
+        tick = vad.push({a: chunk_a, b: chunk_b})        # chunks: int16 or float32, numpy / CPU tensor, or float32 device tensor
+        first, probs, mean = tick[a]                      # rows first .. first + len(probs) - 1 of a's recording
+        last = vad.finish([a])                            # the remaining rows; the slot is free again
+
+    `model_or_predictor`: a SelfAttentiveVAD on `device`, or a VADFromScratchPredictor (its model, window geometry and chunk size
+    are used; its front-end must be the shipped one).  The model's `precision`, `row_mode` and the chunk size are honoured as in the
+    offline paths.  16 kHz mono only."""
+
+    def __init__(self, model_or_predictor, device, streams: int, max_push_samples: int, context: Optional[ContextResolution] = None,
+                 chunk_size: Optional[int] = None, sample_rate: int = 16000, channels: int = 1):
+        if int(sample_rate) != 16000 or int(channels) != 1:
+            raise NotImplementedError(f"live sessions take 16 kHz mono audio ({sample_rate} Hz, {channels} channel(s) asked for): "
+                                      "resample and downmix before pushing (features.resample_to_16k_device)")
+        self.device = torch.device(device)
+        _require_hip(self.device)
+        self.device = _indexed(self.device)
+        model = model_or_predictor
+        if hasattr(model_or_predictor, "front_end") and hasattr(model_or_predictor, "model"):
+            predictor = model_or_predictor
+            predictor._require_shipped_front_end("LiveVAD")
+            model = predictor.model
+            if context is None:
+                context = ContextResolution(predictor.context_window_half_frames, predictor.context_window_jump_frames)
+            if chunk_size is None:
+                chunk_size = predictor.chunk_size
+        context = ContextResolution() if context is None else context
+        self.model = model
+        self.streams, self.max_push_samples = int(streams), int(max_push_samples)
+        self.half, self.jump = int(context.context_window_half_frames), int(context.context_window_jump_frames)
+        self.chunk_size = 16384 if chunk_size is None else int(chunk_size)
+        lib = self._lib = _lib.load()
+        self._cfg = _lib.savad_live_config(self.streams, self.max_push_samples, self.half, self.jump, self.chunk_size)
+        nbytes = ctypes.c_size_t()
+        _lib.check(lib.savad_live_state_bytes(ctypes.byref(self._cfg), ctypes.byref(nbytes)))
+        self.W = lib.savad_window_offsets(self.half, self.jump, None)
+        self._slots = (_lib.savad_live_slot * self.streams)()
+        with torch.cuda.device(self.device):
+            self._state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)   # (the allocator aligns it far beyond 16 bytes)
+            self._state_ptr = self._state.data_ptr()
+            _lib.check(lib.savad_live_table_bytes(ctypes.byref(self._cfg), self.streams, ctypes.byref(nbytes)))
+            # staging: [the tick's tables | every host chunk, 16-byte aligned]; two pinned buffers, so that filling one never waits for
+            # the upload of the other
+            self._stage_bytes = nbytes.value + self.streams * ((4 * self.max_push_samples + 15) & ~15)
+            self._pinned = [torch.empty(self._stage_bytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            self._uploaded = [None, None]
+            self._stage_dev = torch.empty(self._stage_bytes, dtype=torch.uint8, device=self.device)
+        self._turn = 0
+        self._ws_bytes = {}
+
+    # ---- slots ----------------------------------------------------------------------------------
+    def open(self) -> int:
+        """a free slot, opened"""
+        for slot in range(self.streams):
+            if not self._slots[slot].open:
+                _lib.check(self._lib.savad_live_open(ctypes.byref(self._cfg), self._slots, slot))
+                return slot
+        raise _lib.SavadError(f"all {self.streams} slots are open")
+
+    def samples(self, slot: int) -> int:
+        """samples pushed into an open slot so far"""
+        return int(self._slots[slot].n_samples)
+
+    # ---- ticks ----------------------------------------------------------------------------------
+    def push(self, chunks: Mapping[int, object]) -> LiveTick:
+        return self.step(chunks, ())
+
+    def finish(self, slots: Iterable[int], chunks: Optional[Mapping[int, object]] = None) -> LiveTick:
+        """ends the streams in `slots` (after their last chunk in `chunks`, if any): their remaining rows; other slots in `chunks`
+        just push -- one tick underneath"""
+        return self.step(chunks or {}, slots)
+
+    @torch.no_grad()
+    def step(self, chunks: Mapping[int, object], finish: Iterable[int] = ()) -> LiveTick:
+        """One tick: every slot in `chunks` pushes its chunk, every slot in `finish` ends after it."""
+        lib, cfg = self._lib, self._cfg
+        finish = list(dict.fromkeys(int(s) for s in finish))
+        order = list(dict.fromkeys([int(s) for s in chunks] + finish))
+        n = len(order)
+        dev = self.device
+        if n == 0:
+            return LiveTick(torch.empty((0, self.W), dtype=torch.float32, device=dev), torch.empty((0,), dtype=torch.float32, device=dev), {})
+        if n > self.streams:
+            raise _lib.SavadError(f"{n} slots in one tick, the state has {self.streams}")
+        nbytes = ctypes.c_size_t()
+        _lib.check(lib.savad_live_table_bytes(ctypes.byref(cfg), n, ctypes.byref(nbytes)))
+        table_bytes = nbytes.value
+        turn = self._turn
+        if self._uploaded[turn] is not None:
+            self._uploaded[turn].synchronize()   # (the upload of the tick before last: long done)
+        pinned = self._pinned[turn]
+        pinned_np = pinned.numpy()
+        dev_base = self._stage_dev.data_ptr()
+        pushes = (_lib.savad_live_push * n)()
+        at = table_bytes
+        keep = []   # device chunks stay referenced until the tick is enqueued
+        for i, slot in enumerate(order):
+            chunk = chunks.get(slot) if slot in chunks else None
+            dtype, count, ptr = _PCM_FLOAT32, 0, None
+            if chunk is not None:
+                if isinstance(chunk, torch.Tensor) and chunk.device.type == "cuda":
+                    if chunk.dtype != torch.float32 or chunk.dim() != 1:
+                        raise ValueError("a device chunk must be a 1-D float32 tensor")
+                    if chunk.device != dev:
+                        raise _lib.SavadError(f"chunk on {chunk.device}, the session on {dev}")
+                    chunk = chunk.contiguous()
+                    keep.append(chunk)
+                    count, ptr = chunk.numel(), chunk.data_ptr()
+                else:
+                    arr = chunk.numpy() if isinstance(chunk, torch.Tensor) else np.asarray(chunk)
+                    if arr.ndim != 1:
+                        raise ValueError(f"a chunk must be 1-D mono audio, got shape {arr.shape}")
+                    if arr.dtype == np.int16:
+                        dtype = _PCM_INT16
+                    elif arr.dtype != np.float32:
+                        raise ValueError(f"a chunk must be int16 or float32, got {arr.dtype}")
+                    count = arr.shape[0]
+                    if count > self.max_push_samples:
+                        raise _lib.SavadError(f"a push of {count} samples; max_push_samples is {self.max_push_samples}")
+                    size = count * arr.itemsize
+                    pinned_np[at:at + size].view(arr.dtype)[:] = arr
+                    ptr = dev_base + at
+                    at += (size + 15) & ~15
+            pushes[i] = _lib.savad_live_push(slot, count, dtype, int(slot in finish), ptr if count else None)
+        table_host = pinned.data_ptr()
+        counts = _lib.savad_live_counts()
+        rows = np.zeros((n, 2), dtype=np.int64)
+        _lib.check(lib.savad_live_plan(ctypes.byref(cfg), self._slots, pushes, n, ctypes.c_void_p(self._state_ptr), ctypes.c_void_p(table_host),
+                                       table_bytes, ctypes.byref(counts), ctypes.c_void_p(rows.ctypes.data)))
+        with torch.cuda.device(dev):
+            model = self.model
+            model.eval()
+            model._prepare_call(dev)
+            key = (n, model._pushed_knobs)
+            ws_bytes = self._ws_bytes.get(key)
+            if ws_bytes is None:
+                _lib.check(lib.savad_live_workspace_bytes(model._handle, ctypes.byref(cfg), n, ctypes.byref(nbytes)))
+                ws_bytes = self._ws_bytes[key] = nbytes.value
+            ws = model._workspace_for(ws_bytes, dev)
+            self._stage_dev[:at].copy_(pinned[:at], non_blocking=True)   # the one upload of the tick
+            event = self._uploaded[turn]
+            if event is None:
+                event = self._uploaded[turn] = torch.cuda.Event()
+            event.record()
+            self._turn = turn ^ 1
+            probs = torch.empty((counts.rows, self.W), dtype=torch.float32, device=dev)
+            mean = torch.empty((counts.rows,), dtype=torch.float32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.savad_live_step(model._handle, ctypes.byref(cfg), self._slots, ctypes.c_void_p(table_host), ctypes.c_void_p(dev_base),
+                                           ctypes.c_void_p(probs.data_ptr()), ctypes.c_void_p(mean.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                           ws.numel(), ctypes.c_void_p(stream)))
+        del keep
+        out, first_out = {}, 0
+        for i, slot in enumerate(order):
+            out[slot] = (int(rows[i, 0]), first_out, int(rows[i, 1]))
+            first_out += int(rows[i, 1])
+        return LiveTick(probs, mean, out)
+
+
+class LiveSession:
+    """One live stream: LiveVAD with a single slot.  push(chunk) -> (first, probs, mean): the rows first .. that became final;
+    finish() -> the remaining rows."""
+
+    def __init__(self, model_or_predictor, device, max_push_samples: int, context: Optional[ContextResolution] = None, **kwargs):
+        self.vad = LiveVAD(model_or_predictor, device, 1, max_push_samples, context, **kwargs)
+        self.slot = self.vad.open()
+
+    def push(self, chunk):
+        return self.vad.push({self.slot: chunk})[self.slot]
+
+    def finish(self, chunk=None):
+        """ends the recording (after `chunk`, if given); the session can take a new recording afterwards"""
+        result = self.vad.finish([self.slot], {self.slot: chunk} if chunk is not None else None)[self.slot]
+        self.slot = self.vad.open()
+        return result
