@@ -535,6 +535,53 @@ int savad_live_commit(const savad_live_config* config, const void* table_host, s
 int savad_live_step(savad_handle h, const savad_live_config* config, savad_live_slot* slots, const void* table_host,
                     const void* table_dev, float* probs, float* mean, void* workspace, size_t workspace_bytes, void* stream);
 
+/* LIVE SESSIONS, EVENTS (csrc/savad_live_post.h): "speech started at sample s" / "speech ended at sample e" as soon as no
+ * continuation of the recording can change them.  One more stage of a tick, called after savad_live_step (or savad_live_boost) with
+ * the tick's tables and its compact probs [counts.rows, W]; two launches whatever the number of streams.  The events of a stream,
+ * concatenated over its ticks, are the segments savad_post_frames + savad_post_segments (max_samples = 0) give for the finished
+ * recording's probabilities, index for index: START = a segment's first sample, END = its last.
+ *   post config W = the window geometry's; threshold and the trim parameters in frames, as predict() derives them (all >= 0).
+ *   look-ahead  after R final rows of an open stream every event at a sample s with 160 (R - v - h - b) > s + 1 has been emitted
+ *               (v, h, b = min_vally, min_hill, hang_before; hang_over needs none); a finish emits the rest.  Nothing is retracted.
+ *               Worst-case latency behind the audio: the rows' 2 half frames + 208 samples, plus (v + h + b) frames.
+ *   post state  DEVICE, savad_live_post_state_bytes (64 bytes per stream, whatever the parameters and however long the recording),
+ *               16-byte aligned, caller-owned; needs no initialisation: an entry with row_first == 0 starts a recording.  An entry
+ *               whose row_first is not the state's next row (the stage was skipped for a tick) gets count -1 and its state is left
+ *               as it is.
+ *   events      DEVICE, savad_live_post_event_bytes of the tick's table, 16-byte aligned, one contiguous buffer:
+ *               int32 offsets[entries + 1] | int32 counts[entries] | padding to *events_offset | savad_live_event[offsets[entries]];
+ *               the events of entry i (table order) are [offsets[i], offsets[i + 1]), in ascending sample order; counts[i] is their
+ *               number, or -1.
+ *   workspace   DEVICE, savad_live_post_workspace_bytes of the tick's table, 16-byte aligned.
+ * savad_live_post is asynchronous on `stream`: no allocation, no synchronisation, no read-back.  Refused before anything is launched
+ * (SAVAD_E_INVALID): W outside 1 .. 128 or not the geometry's, a negative parameter, null pointers, an event buffer or workspace
+ * too small for the tick.
+ * savad_live_post_host: HOST twin for the CPU tests -- the same inline functions in plain loops on a HOST state of
+ * savad_live_post_state_bytes(post, 1, ..) bytes: one entry (rows row_first .. row_first + row_count - 1 of one stream, probs
+ * [row_count, W], finish) -> up to `cap` events and *count (all events, also those beyond cap; -1 as above). */
+#define SAVAD_LIVE_EVENT_START 0
+#define SAVAD_LIVE_EVENT_END 1
+typedef struct savad_live_event {
+    int64_t sample;
+    int32_t slot;
+    int32_t kind; /* SAVAD_LIVE_EVENT_* */
+} savad_live_event;
+typedef struct savad_live_post_config {
+    int32_t W;
+    float threshold;
+    int32_t min_vally, min_hill, hang_before, hang_over; /* frames */
+} savad_live_post_config;
+int savad_live_post_state_bytes(const savad_live_post_config* post, int streams, size_t* bytes);
+int savad_live_post_event_bytes(const savad_live_config* config, const savad_live_post_config* post, const void* table_host, size_t* bytes,
+                                size_t* events_offset);
+int savad_live_post_workspace_bytes(const savad_live_config* config, const savad_live_post_config* post, const void* table_host,
+                                    size_t* bytes);
+int savad_live_post(const savad_live_config* config, const savad_live_post_config* post, const void* table_host, const void* table_dev,
+                    const float* probs, void* post_state, void* events, size_t events_bytes, void* workspace, size_t workspace_bytes,
+                    void* stream);
+int savad_live_post_host(const savad_live_post_config* post, void* state, int slot, int64_t row_first, int row_count, int finish,
+                         const float* probs, savad_live_event* events, int cap, int* count);
+
 const char* savad_last_error(void);
 const char* savad_version(void);
 

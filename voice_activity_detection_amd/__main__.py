@@ -2,6 +2,8 @@
 ``... evaluate EVAL_LIST CHECKPOINT [options]`` -- the reference's ``python main.py predict`` / ``evaluate``
 (``main.py:8-10``, ``vad/predict.py:10-50``, ``vad/evaluate.py:20-29``) on the MI355X path: same positional
 arguments, same options, JSON v0.3 (predict) / metric lines (evaluate) to ``--output-path`` or stdout.
+``... live AUDIO CHECKPOINT --push-ms 100`` feeds the file through a live session (live.py): one JSON line per speech start / end as
+soon as it is final, then the JSON ``predict`` writes for that file and those parameters.
 ``train`` is out of scope."""
 from __future__ import annotations
 
@@ -69,6 +71,19 @@ def main(argv=None) -> int:
                    help="compute a file's metrics on the GPU (same values; the labels go up and a few hundred bytes come back instead "
                         "of the probability matrix going down): pays for long recordings, a short clip is launch-bound")
     e.add_argument("--precision", choices=("fp32", "fp32s", "bf16"), default="fp32", help="as for predict")
+    lv = sub.add_parser("live", help="one 16 kHz WAV file fed through a live session: an event line as soon as it is final, then "
+                                     "predict's JSON")
+    lv.add_argument("audio_path", type=Path)
+    lv.add_argument("checkpoint_path", type=Path)
+    lv.add_argument("--push-ms", type=int, default=100, help="audio per push in milliseconds")
+    lv.add_argument("--output-path", type=Path, default=None, help="Path to store the final output. Default to stdout.")
+    lv.add_argument("--threshold", type=float, default=0.5)
+    lv.add_argument("--min-vally-ms", type=int, default=0)
+    lv.add_argument("--min-hill-ms", type=int, default=0)
+    lv.add_argument("--hang-before-ms", type=int, default=0)
+    lv.add_argument("--hang-over-ms", type=int, default=0)
+    lv.add_argument("--device", default="cuda")
+    lv.add_argument("--precision", choices=("fp32", "fp32s", "bf16"), default="fp32", help="as for predict")
     args = ap.parse_args(argv)
 
     if args.command == "evaluate":
@@ -78,6 +93,9 @@ def main(argv=None) -> int:
                                   args.shuffle, args.limit, args.random_seed, args.device, extended_front_end=args.extended_front_end,
                                   device_ingest=args.device_ingest, device_metrics=args.device_metrics, precision=args.precision)
         return 0
+
+    if args.command == "live":
+        return live(args)
 
     from .predictor import VADFromScratchPredictor, VADPredictParameters
 
@@ -89,6 +107,48 @@ def main(argv=None) -> int:
         args.audio_path,
         VADPredictParameters(args.split_max_seconds, args.threshold, args.min_vally_ms, args.min_hill_ms, args.hang_before_ms,
                              args.hang_over_ms, args.activity_max_sec, args.return_probs, args.probs_sample_rate, True))
+    if args.output_path:
+        args.output_path.parent.mkdir(parents=True, exist_ok=True)
+        voice_activity.save(args.output_path)
+    else:
+        print(json.dumps(voice_activity.to_json(), ensure_ascii=False, indent=4))
+    return 0
+
+
+def live(args) -> int:
+    """The file through a LiveSession in pushes of --push-ms: one JSON line per event as it becomes final (sample index and seconds),
+    then the VoiceActivity JSON predict writes for the same file and parameters."""
+    from datetime import timedelta
+
+    from .clips import chunk_bounds
+    from .data_models import VoiceActivity, merge_voice_activities
+    from .features import SAMPLE_RATE, load_wav_mono16k
+    from .live import START, LiveSession
+    from .predictor import VADFromScratchPredictor, VADPredictParameters
+
+    if args.push_ms < 1:
+        raise SystemExit("--push-ms must be at least 1")
+    predictor = VADFromScratchPredictor.from_checkpoint(args.checkpoint_path, args.device)
+    predictor.model.precision = args.precision
+    parameters = VADPredictParameters(None, args.threshold, args.min_vally_ms, args.min_hill_ms, args.hang_before_ms, args.hang_over_ms)
+    audio = load_wav_mono16k(args.audio_path)
+    push = SAMPLE_RATE * args.push_ms // 1000
+    session = LiveSession(predictor, predictor.device, max(push, 1), post=parameters)
+    activities = []
+
+    def report():
+        for kind, sample in session.events():
+            print(json.dumps({"event": "start" if kind == START else "end", "sample": sample, "seconds": sample / SAMPLE_RATE}), flush=True)
+        activities.extend(session.activities())
+
+    for at in range(0, len(audio), max(push, 1)):
+        session.push(audio[at:at + push])
+        report()
+    session.finish()
+    report()
+    adjusted, _ = chunk_bounds(len(audio), SAMPLE_RATE, None)
+    voice_activity = merge_voice_activities([VoiceActivity(duration=timedelta(seconds=adjusted), activities=activities, probs_sample_rate=None,
+                                                           probs=None)])
     if args.output_path:
         args.output_path.parent.mkdir(parents=True, exist_ok=True)
         voice_activity.save(args.output_path)

@@ -41,6 +41,15 @@ class savad_live_counts(ctypes.Structure):
     _fields_ = [("entries", c_int32), ("tiles", c_int32), ("items", c_int32), ("rows", c_int32), ("table_bytes", c_int32), ("W", c_int32)]
 
 
+class savad_live_event(ctypes.Structure):
+    _fields_ = [("sample", c_int64), ("slot", c_int32), ("kind", c_int32)]
+
+
+class savad_live_post_config(ctypes.Structure):
+    _fields_ = [("W", c_int32), ("threshold", c_float), ("min_vally", c_int32), ("min_hill", c_int32), ("hang_before", c_int32),
+                ("hang_over", c_int32)]
+
+
 # every symbol include/savad.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "savad_create": (c_int, [POINTER(savad_config), POINTER(c_void_p)]),
@@ -136,6 +145,11 @@ SYMBOLS = {
     "savad_live_boost": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "savad_live_commit": (c_int, [c_void_p, c_void_p, c_void_p]),
     "savad_live_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "savad_live_post_state_bytes": (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
+    "savad_live_post_event_bytes": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_size_t), POINTER(c_size_t)]),
+    "savad_live_post_workspace_bytes": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_size_t)]),
+    "savad_live_post": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "savad_live_post_host": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, POINTER(c_int)]),
     "savad_last_error": (c_char_p, []),
     "savad_version": (c_char_p, []),
 }

@@ -22,6 +22,7 @@
 #include "savad_schedule.h"
 #include "savad_weights.h"
 #include "savad_live.h"
+#include "savad_live_post.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -1712,6 +1713,139 @@ SAVAD_EXPORT int savad_live_step(savad_handle m, const savad_live_config* config
     }
     if ((rc = savad_live_boost(config, table_host, table_dev, logp, probs, mean, stream))) return rc;
     live::commit(table_host, reinterpret_cast<live::Slot*>(slots));
+    return SAVAD_OK;
+}
+
+// ---- live sessions: events as they become final (savad_live_post.h) -----------------------------------------------
+namespace {
+
+namespace lp = savad::livepost;
+
+static_assert(sizeof(savad_live_event) == sizeof(lp::Event), "live event ABI");
+
+int live_post_params(const savad_live_post_config* c, lp::Params* p) {
+    if (!c) return fail(SAVAD_E_INVALID, "null post config");
+    if (c->W < 1 || c->W > postdev::W_MAX) return fail(SAVAD_E_INVALID, "W = %d: the row mean has numpy's order for 1 .. %d", c->W, postdev::W_MAX);
+    if (c->min_vally < 0 || c->min_hill < 0 || c->hang_before < 0 || c->hang_over < 0)
+        return fail(SAVAD_E_INVALID, "negative trim parameter (%d, %d, %d, %d)", c->min_vally, c->min_hill, c->hang_before, c->hang_over);
+    if (!(c->threshold == c->threshold)) return fail(SAVAD_E_INVALID, "threshold is NaN");
+    *p = lp::Params{c->W, c->threshold, c->min_vally, c->min_hill, c->hang_before, c->hang_over};
+    return SAVAD_OK;
+}
+
+// events [offsets entries + 1 | counts entries | events cap]; workspace [counts entries | raw entries x cap_max]
+struct LivePostLayout {
+    size_t ev_counts, ev_events, ev_total, ws_raw, ws_total;
+    long events_cap;
+    int cap_max;
+};
+int live_post_layout(const live::Geometry& g, const live::Header* h, const void* table_host, const lp::Params& p, LivePostLayout* L) {
+    const live::Entry* e = live::entries(table_host);
+    long total = 0;
+    int cap_max = 0;
+    for (int i = 0; i < h->n_entries; ++i) {
+        if (e[i].row_count < 0 || e[i].row_out < 0 || (long)e[i].row_out + e[i].row_count > h->n_rows)
+            return fail(SAVAD_E_INVALID, "entry %d names rows [%d, +%d) of %d", i, e[i].row_out, e[i].row_count, h->n_rows);
+        if (e[i].slot < 0 || e[i].slot >= g.streams) return fail(SAVAD_E_INVALID, "entry %d names slot %d of %d", i, e[i].slot, g.streams);
+        const int cap = lp::event_cap(e[i].row_count, p);
+        total += cap;
+        cap_max = cap > cap_max ? cap : cap_max;
+    }
+    const size_t n = (size_t)h->n_entries;
+    L->ev_counts = sizeof(int32_t) * (n + 1);
+    L->ev_events = live::up16(sizeof(int32_t) * (2 * n + 1));
+    L->ev_total = L->ev_events + sizeof(lp::Event) * (size_t)total;
+    L->ws_raw = live::up16(sizeof(int32_t) * n);
+    L->ws_total = L->ws_raw + sizeof(lp::Event) * n * (size_t)cap_max;
+    L->events_cap = total;
+    L->cap_max = cap_max;
+    return SAVAD_OK;
+}
+
+// config, post config and the host table -> geometry, parameters, layout
+int live_post_plan(const savad_live_config* config, const savad_live_post_config* post, const void* table_host, live::Geometry* g,
+                   const live::Header** h, lp::Params* p, LivePostLayout* L) {
+    int rc;
+    if ((rc = live_geometry(config, g))) return rc;
+    if ((rc = live_post_params(post, p))) return rc;
+    if (!table_host) return fail(SAVAD_E_INVALID, "null table");
+    const live::PlanResult r = live::check_table(*g, table_host, nullptr);
+    if (r.err) return fail(r.err, "%s", r.msg);
+    *h = live::header(table_host);
+    return live_post_layout(*g, *h, table_host, *p, L);
+}
+
+}  // namespace
+
+SAVAD_EXPORT int savad_live_post_state_bytes(const savad_live_post_config* post, int streams, size_t* bytes) {
+    lp::Params p;
+    if (int rc = live_post_params(post, &p)) return rc;
+    if (!bytes || streams < 1) return fail(SAVAD_E_INVALID, "streams = %d", streams);
+    *bytes = sizeof(lp::State) * (size_t)streams;
+    return SAVAD_OK;
+}
+SAVAD_EXPORT int savad_live_post_event_bytes(const savad_live_config* config, const savad_live_post_config* post, const void* table_host,
+                                             size_t* bytes, size_t* events_offset) {
+    live::Geometry g;
+    const live::Header* h;
+    lp::Params p;
+    LivePostLayout L;
+    if (int rc = live_post_plan(config, post, table_host, &g, &h, &p, &L)) return rc;
+    if (!bytes) return fail(SAVAD_E_INVALID, "null argument");
+    *bytes = L.ev_total;
+    if (events_offset) *events_offset = L.ev_events;
+    return SAVAD_OK;
+}
+SAVAD_EXPORT int savad_live_post_workspace_bytes(const savad_live_config* config, const savad_live_post_config* post, const void* table_host,
+                                                 size_t* bytes) {
+    live::Geometry g;
+    const live::Header* h;
+    lp::Params p;
+    LivePostLayout L;
+    if (int rc = live_post_plan(config, post, table_host, &g, &h, &p, &L)) return rc;
+    if (!bytes) return fail(SAVAD_E_INVALID, "null argument");
+    *bytes = L.ws_total;
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_live_post(const savad_live_config* config, const savad_live_post_config* post, const void* table_host,
+                                 const void* table_dev, const float* probs, void* post_state, void* events, size_t events_bytes, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    live::Geometry g;
+    const live::Header* h;
+    lp::Params p;
+    LivePostLayout L;
+    if (int rc = live_post_plan(config, post, table_host, &g, &h, &p, &L)) return rc;
+    if (p.W != g.W) return fail(SAVAD_E_INVALID, "the post config has W = %d, the window geometry %d", p.W, g.W);
+    if (!table_dev || ((uintptr_t)table_dev & 15)) return fail(SAVAD_E_INVALID, "null table, or a device table that is not 16-byte aligned");
+    if (!post_state || !events || !workspace || (h->n_rows > 0 && !probs)) return fail(SAVAD_E_INVALID, "null pointer");
+    if (((uintptr_t)post_state & 15) || ((uintptr_t)events & 15) || ((uintptr_t)workspace & 15))
+        return fail(SAVAD_E_INVALID, "post state, events and workspace must be 16-byte aligned");
+    if (events_bytes < L.ev_total) return fail(SAVAD_E_INVALID, "event buffer too small for the tick: %zu < %zu bytes", events_bytes, L.ev_total);
+    if (workspace_bytes < L.ws_total) return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, L.ws_total);
+    char* ev = (char*)events;
+    char* ws = (char*)workspace;
+    int32_t* counts = (int32_t*)ws;
+    lp::Event* raw = (lp::Event*)(ws + L.ws_raw);
+    if (h->n_entries > 0) {
+        hipLaunchKernelGGL(lp::post_kernel, dim3(h->n_entries < 65536 ? h->n_entries : 65536), dim3(64), 0, (hipStream_t)stream,
+                           live_at<live::Entry>(table_dev, h->o_entries), h->n_entries, g.streams, probs, p, (lp::State*)post_state, raw, L.cap_max,
+                           counts);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(lp::compact_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const lp::Event*)raw, L.cap_max, (const int32_t*)counts,
+                       h->n_entries, (int32_t*)ev, (int32_t*)(ev + L.ev_counts), (lp::Event*)(ev + L.ev_events), L.events_cap);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_live_post_host(const savad_live_post_config* post, void* state, int slot, int64_t row_first, int row_count, int finish,
+                                      const float* probs, savad_live_event* events, int cap, int* count) {
+    lp::Params p;
+    if (int rc = live_post_params(post, &p)) return rc;
+    if (!state || !count || row_count < 0 || cap < 0) return fail(SAVAD_E_INVALID, "null state or count, or a negative count");
+    if ((row_count > 0 && !probs) || (cap > 0 && !events)) return fail(SAVAD_E_INVALID, "null pointer");
+    *count = lp::run_host((lp::State*)state, p, slot, row_first, row_count, finish, probs, (lp::Event*)events, cap);
     return SAVAD_OK;
 }
 
