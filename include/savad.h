@@ -168,9 +168,12 @@ int savad_set_profiling(savad_handle h, int capacity);
 int savad_profiling_skip(savad_handle h, int forwards);
 int savad_last_kernel_times(savad_handle h, const char** names, float* ms, int max);
 
-/* Window geometry of the predictor: W = 2*(half-1)/jump + 3 (vad/predictor.py:57-59); offsets =
- * arange(-half,0,jump) ++ [0] ++ arange(1,half+1,jump) (vad/predictor.py:186-212). Returns W;
- * offsets (host pointer, >= W ints) may be NULL. */
+/* Window geometry of the predictor: offsets = arange(-half,0,jump) ++ [0] ++ arange(1,half+1,jump) (vad/predictor.py:186-212).
+ * Returns W = the NUMBER OF OFFSETS = 2*ceil(half/jump) + 1 (half >= 0, jump >= 1; any other value: SAVAD_E_INVALID); offsets (host
+ * pointer, >= W ints) may be NULL.  Every entry below counts its window frames this way.  The reference sizes its result with
+ * 2*(half-1)/jump + 3 (floor division, vad/predictor.py:57-59), which equals W exactly when 2*((half-1) mod jump) < jump (19/9, any
+ * jump = 1 ...); where it does not (4/2, 9/3, 0/2) the reference itself fails, and the Python layer refuses the geometry.  The C ABI
+ * serves every half / jump with W <= 64. */
 int savad_window_offsets(int half, int jump, int32_t* offsets);
 
 /* Replaces the per-window python gather loop (vad/predictor.py:182-220): for item i in

@@ -139,10 +139,10 @@ def main():
           f"{(OUT/'golden.npz').stat().st_size/1e3:.1f} kB on disk")
 
 
-def predictor_golden(model):
-    """Run vad/predictor.py:159-262 unmodified.  Its module-level imports need packages
-    absent here (more_itertools, omegaconf, librosa, soundfile, pysrt, cv2): stub them in
-    sys.modules for this process only."""
+def reference_predictor(model, half=19, jump=9):
+    """The reference's VADFromScratchPredictor (vad/predictor.py, unmodified) around `model` at the window geometry half / jump.
+    Its module-level imports need packages absent here (more_itertools, omegaconf, librosa, soundfile, pysrt, cv2): stub them in
+    sys.modules for this process only.  predict_probabilities takes SimpleNamespace(feat=[N, F], sample_rate=16000)."""
     from itertools import islice
 
     def ichunked(it, n):
@@ -191,9 +191,15 @@ def predictor_golden(model):
     ns = types.SimpleNamespace
     fe = ns(config=ns(transform=ns(hop_ms=10, window_ms=25)),
             extract_with_postprocessing=lambda audio: audio.feat)
-    config = ns(context_resolution=ns(context_window_half_frames=19, context_window_jump_frames=9),
+    config = ns(context_resolution=ns(context_window_half_frames=half, context_window_jump_frames=jump),
                 model=ns(name="self-attention"))
-    pred = VADFromScratchPredictor(model=model, feature_extractor=fe, device=torch.device("cpu"), config=config)
+    return VADFromScratchPredictor(model=model, feature_extractor=fe, device=torch.device("cpu"), config=config)
+
+
+def predictor_golden(model):
+    """Run vad/predictor.py:159-262 unmodified at the shipped geometry."""
+    ns = types.SimpleNamespace
+    pred = reference_predictor(model)
     out = {}
     # N=1022 frames: the reference test clip's length (SURVEY §8d config 1); N=2100 -> 3 chunks
     for tag, n, seed in (("g5", 1022, 500), ("g5b", 2100, 501), ("g5c", 39, 502)):

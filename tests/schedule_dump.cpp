@@ -4,6 +4,7 @@
 #include "savad_schedule.h"
 
 #include <stdio.h>
+#include <stdlib.h>
 #include <initializer_list>
 
 using namespace savad::sched;
@@ -78,7 +79,14 @@ static Knobs with(Knobs k, int splits, bool batch_invariant = false) {
     return k;
 }
 
-int main() {
+int main(int argc, char** argv) {
+    // `schedule_dump windows HALF_MAX JUMP_MAX`: one line "half jump W" per geometry (tests/test_window_geometry_host.py); without
+    // arguments the recorded table below
+    if (argc == 4 && argv[1][0] == 'w') {
+        for (int half = 0; half <= atoi(argv[2]); ++half)
+            for (int jump = 1; jump <= atoi(argv[3]); ++jump) printf("%d %d %ld\n", half, jump, window_count(half, jump));
+        return 0;
+    }
     // ---- general: every sequence length under the automatic schedule, every row_mode at a short and a long one, a large batch
     for (int precision = 0; precision < 3; ++precision) {
         for (int T : {1, 7, 20, 32, 33, 50, 96, 800, 3200}) fwd(knobs(precision, 0), 5, T);

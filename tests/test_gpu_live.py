@@ -50,15 +50,19 @@ def model(torch_cuda, state1234):
     return m.to("cuda").eval()
 
 
-@pytest.fixture(scope="module")
-def signals():
-    """seeded noise plus a chirp, one per total; never written"""
+def make_signals():
+    """seeded noise plus a chirp, one per total; never written (tests/test_gpu_window_geometry.py runs two of them at other geometries)"""
     out = []
     for k, n in enumerate(TOTALS):
         t = np.arange(n, dtype=np.float64) / 16000.0
         chirp = 0.2 * np.sin(2 * np.pi * (200.0 + 900.0 * t) * t)
         out.append((np.random.default_rng(40 + k).standard_normal(n) * 0.05 + chirp).astype(np.float32))
     return out
+
+
+@pytest.fixture(scope="module")
+def signals():
+    return make_signals()
 
 
 def cut(total, sizes):
@@ -75,13 +79,16 @@ def chunking(name, total):
     return {"a": [total], "b": cut(total, [1600]), "c": cut(total, IRREGULAR), "d": cut(total, [1600])}[name]
 
 
-def run_live(torch, model, signals, name, dtype=np.float32):
-    """every recording through one LiveVAD under chunking `name` -> [(probs, mean)] on the host, in recording order"""
+def run_live(torch, model, signals, name, dtype=np.float32, context=None):
+    """every recording through one LiveVAD under chunking `name` -> [(probs, mean)] on the host, in recording order.
+    `context` (ContextResolution; None = the shipped 19 / 9): the session's window geometry, whose W the rows must have"""
     from voice_activity_detection_amd import LiveVAD
 
     cuts = [chunking(name, len(s)) for s in signals]
     slots_n = 3 if name == "d" else len(signals)
-    vad = LiveVAD(model, "cuda", streams=slots_n, max_push_samples=max(max(c) for c in cuts))
+    vad = LiveVAD(model, "cuda", streams=slots_n, max_push_samples=max(max(c) for c in cuts), context=context)
+    W = vad.W
+    assert W == 7 or context is not None
     waiting = list(range(len(signals)))
     active = {}    # slot -> [recording, next chunk index, samples pushed]
     got = [[] for _ in signals]

@@ -32,7 +32,8 @@ import torch
 
 from . import _lib
 from .data_models import Activity
-from .predictor import ContextResolution, VADFromScratchPredictor, VADPredictParameters, _indexed, _require_hip
+from .predictor import (ContextResolution, VADFromScratchPredictor, VADPredictParameters, _indexed, _require_hip,
+                        context_window_frames)
 
 _PCM_INT16, _PCM_FLOAT32 = 0, 1   # SAVAD_PCM_*
 START, END = 0, 1                 # SAVAD_LIVE_EVENT_*: the kinds of LiveTick.events
@@ -134,7 +135,7 @@ class LiveVAD:
         self._cfg = _lib.savad_live_config(self.streams, self.max_push_samples, self.half, self.jump, self.chunk_size)
         nbytes = ctypes.c_size_t()
         _lib.check(lib.savad_live_state_bytes(ctypes.byref(self._cfg), ctypes.byref(nbytes)))
-        self.W = lib.savad_window_offsets(self.half, self.jump, None)
+        self.W = context_window_frames(self.half, self.jump)   # (refuses a geometry the reference cannot run)
         self._slots = (_lib.savad_live_slot * self.streams)()
         with torch.cuda.device(self.device):
             self._state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)   # (the allocator aligns it far beyond 16 bytes)

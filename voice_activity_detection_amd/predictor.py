@@ -30,11 +30,29 @@ from .postprocessing import (convert_frames_to_samples, convert_samples_to_segme
 
 def window_offsets(half: int, jump: int) -> np.ndarray:
     """arange(-half, 0, jump) ++ [0] ++ arange(1, half+1, jump)  (vad/predictor.py:186-212)."""
-    buf = (ctypes.c_int32 * 64)()
-    w = _lib.load().savad_window_offsets(half, jump, buf)
+    lib = _lib.load()
+    w = lib.savad_window_offsets(half, jump, None)
     if w < 0:
         _lib.check(w)
+    buf = (ctypes.c_int32 * w)()
+    lib.savad_window_offsets(half, jump, buf)
     return np.array(buf[:w], dtype=np.int64)
+
+
+def context_window_frames(half: int, jump: int) -> int:
+    """W of a window geometry: the number of offsets (savad_window_offsets), which is what every kernel, gather and boost uses.
+    The reference sizes its result by 2 * (half - 1) // jump + 3 (vad/predictor.py:57-59) and fills it from the offsets (:186-212);
+    the two numbers differ whenever 2 * ((half - 1) % jump) >= jump (4 / 2, 9 / 3, 0 / 2 ...), where the reference itself fails with an
+    IndexError: such a geometry has no reference result and is refused here."""
+    half, jump = int(half), int(jump)
+    W = _lib.load().savad_window_offsets(half, jump, None)
+    if W < 0:
+        _lib.check(W)
+    formula = 2 * (half - 1) // jump + 3
+    if W != formula:
+        raise ValueError(f"window geometry {half} / {jump}: the reference's context_window_frames formula gives {formula} frames, its "
+                         f"window offsets are {W}; the reference cannot run this geometry, so there is nothing to reproduce")
+    return W
 
 
 def split_by_clip_pairs(result, table) -> list:
@@ -126,8 +144,8 @@ class VADFromScratchPredictor:
         self.device = torch.device(device)
         self.context_window_half_frames = context.context_window_half_frames
         self.context_window_jump_frames = context.context_window_jump_frames
-        # vad/predictor.py:57-59
-        self.context_window_frames = 2 * (self.context_window_half_frames - 1) // self.context_window_jump_frames + 3
+        # vad/predictor.py:57-59, as the count of the window offsets (a geometry where the two differ is refused)
+        self.context_window_frames = context_window_frames(self.context_window_half_frames, self.context_window_jump_frames)
         # windows per forward.  The reference uses 1000 (vad/predictor.py:180); windows are independent, so any value gives
         # the same probabilities up to fp32 summation order (<= 1e-6: a larger batch may pick another launch schedule), and
         # 10 min of audio take 9.4 ms with 1000 against 5.1 ms with 16384
