@@ -65,8 +65,9 @@ def _threads(n: int):
 class _Arith:
     """the rounding operators (identities when rounding is off) and the counters"""
 
-    def __init__(self, rounding: bool, plant):
+    def __init__(self, rounding: bool, plant, dtype=torch.float64):
         self.rounding = rounding
+        self.dtype = dtype
         self.plant = plant
         self.moves = 0
         self.saturations = 0
@@ -75,7 +76,7 @@ class _Arith:
         # every (__bf16) conversion of the kernels: v_cvt_pk_bf16_f32, round to nearest even, of an fp32 value
         if not self.rounding:
             return t
-        return t.to(torch.float32).to(torch.bfloat16).to(torch.float64)
+        return t.to(torch.float32).to(torch.bfloat16).to(self.dtype)
 
     def park(self, t: torch.Tensor) -> torch.Tensor:
         # store_hblock (csrc/savad_kernels_bf16.h:110-133; park_h, csrc/savad_packed_bf16.h:42): clamp to +-65504 (:120), then
@@ -85,7 +86,7 @@ class _Arith:
         self.saturations += int((~(t.abs() <= F16_MAX)).sum())
         if self.plant == "residual_bf16":
             return self.bf(t.clamp(-F16_MAX, F16_MAX))
-        return t.clamp(-F16_MAX, F16_MAX).to(torch.float32).to(torch.float16).to(torch.float64)
+        return t.clamp(-F16_MAX, F16_MAX).to(torch.float32).to(torch.float16).to(self.dtype)
 
 
 def positional_encoding(T: int) -> np.ndarray:
@@ -109,8 +110,8 @@ def _fold(W, b, gamma, beta):
     return Wf, bf
 
 
-def _t(a) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+def _t(a, dtype=torch.float64) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dtype)
 
 
 def _prepare(state: dict, A: _Arith):
@@ -118,7 +119,7 @@ def _prepare(state: dict, A: _Arith):
     csrc/savad_kernels_bf16.h:1027: (__bf16)W), biases fp32; the classifier stays fp32 (RowArgsBf16::wc, :798)"""
     s = {k: np.asarray(v, dtype=np.float32) for k, v in state.items()}
     L = 1 + max(int(k.split(".")[2]) for k in s if k.startswith("encoder.layers."))
-    P = {"win": A.bf(_t(s["input_layer.0.weight"])), "bin": _t(s["input_layer.0.bias"]), "layers": []}
+    P = {"win": A.bf(_t(s["input_layer.0.weight"], A.dtype)), "bin": _t(s["input_layer.0.bias"], A.dtype), "layers": []}
     for l in range(L):
         p = f"encoder.layers.{l}."
         g1, b1n = s[p + "self_attention_sublayer.layer_norm.weight"], s[p + "self_attention_sublayer.layer_norm.bias"]
@@ -126,14 +127,14 @@ def _prepare(state: dict, A: _Arith):
         lay = {}
         for nm, key in (("q", "query"), ("k", "key"), ("v", "value")):
             W, b = _fold(s[p + f"self_attention.{key}_projection.weight"], s[p + f"self_attention.{key}_projection.bias"], g1, b1n)
-            lay["w" + nm], lay["b" + nm] = A.bf(_t(W)), _t(b)
-        lay["wo"], lay["bo"] = A.bf(_t(s[p + "self_attention.final_projection.weight"])), _t(s[p + "self_attention.final_projection.bias"])
+            lay["w" + nm], lay["b" + nm] = A.bf(_t(W, A.dtype)), _t(b, A.dtype)
+        lay["wo"], lay["bo"] = A.bf(_t(s[p + "self_attention.final_projection.weight"], A.dtype)), _t(s[p + "self_attention.final_projection.bias"], A.dtype)
         W1, b1 = _fold(s[p + "feed_forward.feed_forward.0.weight"], s[p + "feed_forward.feed_forward.0.bias"], g2, b2n)
-        lay["w1"], lay["b1"] = A.bf(_t(W1)), _t(b1)
-        lay["w2"], lay["b2"] = A.bf(_t(s[p + "feed_forward.feed_forward.3.weight"])), _t(s[p + "feed_forward.feed_forward.3.bias"])
+        lay["w1"], lay["b1"] = A.bf(_t(W1, A.dtype)), _t(b1, A.dtype)
+        lay["w2"], lay["b2"] = A.bf(_t(s[p + "feed_forward.feed_forward.3.weight"], A.dtype)), _t(s[p + "feed_forward.feed_forward.3.bias"], A.dtype)
         P["layers"].append(lay)
     wc, bc = _fold(s["classifier.weight"], s["classifier.bias"], s["encoder.layer_norm.weight"], s["encoder.layer_norm.bias"])
-    P["wc"], P["bc"] = _t(wc), _t(bc)
+    P["wc"], P["bc"] = _t(wc, A.dtype), _t(bc, A.dtype)
     return P
 
 
@@ -159,10 +160,10 @@ def _online(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, blocks, A: _Arith
     q [B,M,D] (bf16, pre-scaled: scores in the base-2 exponent domain), k / v [B,T,D] (bf16).  count [B,M] bool: rows whose
     moves are counted.  Returns (O, l, reference)."""
     B, M, _ = q.shape
-    ref = torch.zeros(B, M, dtype=torch.float64)               # attn_state_init (:615-620): reference 0
-    l0 = torch.zeros(B, M, dtype=torch.float64)                # l_run of lane half h = 0 (keys 8 i + 0..3) ...
-    l1 = torch.zeros(B, M, dtype=torch.float64)                # ... and h = 1 (keys 8 i + 4..7): they meet in store_ctx (:674)
-    O = torch.zeros(B, M, D, dtype=torch.float64)
+    ref = torch.zeros(B, M, dtype=q.dtype)               # attn_state_init (:615-620): reference 0
+    l0 = torch.zeros(B, M, dtype=q.dtype)                # l_run of lane half h = 0 (keys 8 i + 0..3) ...
+    l1 = torch.zeros(B, M, dtype=q.dtype)                # ... and h = 1 (keys 8 i + 4..7): they meet in store_ctx (:674)
+    O = torch.zeros(B, M, D, dtype=q.dtype)
     for i, j in enumerate(blocks):
         first = i == 0
         kj, vj, ok = _tiles(k, v, j, A)
@@ -201,7 +202,7 @@ def _attention(q, k, v, A: _Arith, key_split: bool):
     """the context of every query row: [B,T,D] (bf16)"""
     B, T, _ = q.shape
     QB = (T + TILE - 1) // TILE
-    ctx = torch.empty(B, T, D, dtype=torch.float64)
+    ctx = torch.empty(B, T, D, dtype=q.dtype)
     split_from = T
     if key_split and QB % 8 in (1, 2):
         # persistent attention kernel (csrc/savad_attn_pw_bf16.h:7; row_mode 5): a sequence's tail group of one or two query
@@ -242,23 +243,25 @@ def _qkv(n: torch.Tensor, lay: dict, A: _Arith):
 
 
 def forward(state: dict, x: np.ndarray, *, rounding: bool = True, key_split: bool = False, plant: str | None = None,
-            info: dict | None = None, threads: int = 16) -> np.ndarray:
+            info: dict | None = None, threads: int = 16, dtype: str = "float64") -> np.ndarray:
     """state: the state_dict (key -> float32 array) that oracle.forward takes; x [B,T,F] (float32, or values that are already
-    bf16: feeding a bf16 tensor to the kernels is the same as rounding these).  Returns float64 log-probabilities [B,T,2]."""
+    bf16: feeding a bf16 tensor to the kernels is the same as rounding these).  Returns float64 log-probabilities [B,T,2].
+    dtype="float32" evaluates the SAME model on float tensors: its difference from the float64 evaluation (the model's
+    self-difference) is the rounding-flip floor of this arithmetic at a state and input."""
     if plant is not None and plant not in PLANTS:
         raise ValueError(f"unknown plant {plant!r}")
-    A = _Arith(rounding, plant)
+    A = _Arith(rounding, plant, getattr(torch, dtype))
     with _threads(threads), torch.no_grad():
         P = _prepare(state, A)
         x = np.asarray(x, dtype=np.float32)
         B, T, F = x.shape
         assert P["win"].shape == (D, F), "feature size / d_model mismatch"
         pe = positional_encoding(T + 1)
-        pe = _t(pe[1:] if plant == "pe_shift" else pe[:T])
+        pe = _t(pe[1:] if plant == "pe_shift" else pe[:T], A.dtype)
         # input stage (input_qkv_kernel_bf16, csrc/savad_kernels_bf16.h:376-392; the persistent form :520-578 and the packed
         # single launch, csrc/savad_packed_bf16.h:144-189, do the same): features -> bf16 (load_x_frag :335-336), the fp32
         # accumulator starts at bias + PE (:380-381) and takes the bf16 products (:390)
-        h = P["bin"] + pe[None] + A.bf(_t(x)) @ P["win"].T
+        h = P["bin"] + pe[None] + A.bf(_t(x, A.dtype)) @ P["win"].T
         hp = A.park(h)                                                # store_hblock (:392)
         for l, lay in enumerate(P["layers"]):
             last = l == len(P["layers"]) - 1
@@ -283,4 +286,4 @@ def forward(state: dict, x: np.ndarray, *, rounding: bool = True, key_split: boo
     if info is not None:
         info["moves"] = A.moves
         info["saturations"] = A.saturations
-    return out.numpy()
+    return out.to(torch.float64).numpy()

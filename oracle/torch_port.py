@@ -32,7 +32,7 @@ def forward(state: dict, x: torch.Tensor) -> torch.Tensor:
     D = state["input_layer.0.weight"].shape[0]
     L = 1 + max(int(k.split(".")[2]) for k in state if k.startswith("encoder.layers."))
     h = F.linear(x, state["input_layer.0.weight"], state["input_layer.0.bias"])
-    h = h + positional_encoding(T, D).unsqueeze(0) / math.sqrt(D)
+    h = h + positional_encoding(T, D).unsqueeze(0).to(h.dtype) / math.sqrt(D)   # (the fp32 table in the input's type, then the division: transformer.py:398-401)
     for l in range(L):
         p = f"encoder.layers.{l}."
         n = F.layer_norm(h, (D,), state[p + "self_attention_sublayer.layer_norm.weight"],

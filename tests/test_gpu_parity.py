@@ -1594,9 +1594,9 @@ def test_auc_parity_on_the_reference_labelled_files(torch_cuda, model, state1234
             assert abs(out["files"][i]["boosted_auc"] - auc32) < 1e-6
 
 
-def test_config3_size_batch(torch_cuda, model, state1234):
-    """BASELINE configs[2]/[3] per-GPU size [256,800,80]: sampled sequences against the oracle (fp32 path and
-    bf16 path), plus the size-independent properties on the whole batch."""
+def test_config3_size_batch(torch_cuda, model, state1234, fp32_mode):
+    """BASELINE configs[2]/[3] per-GPU size [256,800,80]: sampled sequences against the oracle (the fp32 path in each of its
+    modes -- fp32s is the headline precision -- and the bf16 path), plus the size-independent properties on the whole batch."""
     from oracle import oracle
 
     x = feats(2048, (256, 800, 80))
