@@ -152,8 +152,10 @@ class Entry(ctypes.Structure):   # csrc/savad_live_plan.h: Entry
                 [("row_first", ctypes.c_int64), ("phase_after", ctypes.c_int32), ("pad", ctypes.c_int32)])
 
 
-def run_stages(torch, lib, model, audio, sizes):
-    """One stream in slot 1 of 2, every stage entry called by hand; every stage's output compared with the offline entry's bits."""
+def run_stages(torch, lib, model, audio, sizes, sub_ranges=False):
+    """One stream in slot 1 of 2, every stage entry called by hand; every stage's output compared with the offline entry's bits.
+    sub_ranges: the gather also runs over items [first, first + count) at the edges of its 32-item tiles, and `seen` counts the
+    ticks whose first 32 items have the feature ring's wrap between their centres."""
     from voice_activity_detection_amd import _lib
     from voice_activity_detection_amd.features import log_mel
 
@@ -172,7 +174,7 @@ def run_stages(torch, lib, model, audio, sizes):
     ok(lib.savad_live_open(ctypes.byref(cfg), slots, 1))
     full = log_mel(audio, "cuda")                                   # the finished recording's features
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    live_rows, all_logp, seen = [], [], {"one_frame": 0, "tiles": 0, "frames": 0, "windows": 0}
+    live_rows, all_logp, seen = [], [], {"one_frame": 0, "tiles": 0, "frames": 0, "windows": 0, "wrapped": 0}
     at = 0
     for size, last in [(s, False) for s in sizes] + [(0, True)]:
         chunk = torch.from_numpy(audio[at:at + size].copy()).cuda() if size else None
@@ -204,6 +206,15 @@ def run_stages(torch, lib, model, audio, sizes):
             assert e.item0 % 4 == E0 % 4 and same_bits(win[e.item0:e.item0 + e.n_windows], want)
             dummies = torch.cat([win[:e.item0], win[e.item0 + e.n_windows:]])
             assert not dummies.any()
+            if sub_ranges:
+                centre0 = (E0 + HALF) % feat_cap - e.item0        # ring position item 0 would have: item i sits at centre0 + i, modulo the ring
+                seen["wrapped"] += counts.items >= 33 and centre0 + e.item0 < feat_cap <= centre0 + 31
+                for first in (0, 5):
+                    for count in (1, 31, 32, 33):
+                        if first + count <= counts.items:
+                            part = torch.empty((count, W, 80), dtype=torch.float32, device="cuda")
+                            ok(lib.savad_live_gather(ctypes.byref(cfg), host, ptr(table_dev), first, count, ptr(part), stream))
+                            assert same_bits(part, win[first:first + count]), (first, count)
             logp = model(features=win)
             all_logp.append(logp[e.item0:e.item0 + e.n_windows])
             seen["windows"] += e.n_windows
@@ -241,6 +252,15 @@ def test_stages_many_tiles_in_one_tick(torch_cuda, lib, model, signals):
     """one push of the whole 37 333 samples: interior tiles, tiles cut at the ring's wrap, and the finish tile"""
     seen = run_stages(torch_cuda, lib, model, signals[4], [len(signals[4])])
     assert seen["tiles"] >= 8
+
+
+def test_gather_tile_edges_with_the_ring_wrap_inside(torch_cuda, lib, model, signals):
+    """pushes of 6000 samples: 37 or 38 windows a tick (more than the gather's 32-item tile) in a ring of 78 rows, so the wrap falls
+    between the centres of a tick's first tile again and again; savad_live_gather over 1, 31, 32 and 33 items from item 0 and from
+    item 5 gives the rows of the whole-tick gather, which run_stages holds to the offline gather's bits"""
+    n = len(signals[4])
+    seen = run_stages(torch_cuda, lib, model, signals[4], [6000] * (n // 6000) + [n % 6000], sub_ranges=True)
+    assert seen["wrapped"] >= 1
 
 
 # ---- 2. chunking invariance and 3. the offline path, pinned variants: bits ------------------------------------------------------

@@ -120,7 +120,7 @@ def boost_batch(torch, lib, logp, table, half, jump):
 
 # ---- 1. the gather against the oracle --------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("half,jump", [(19, 9), (5, 1)])
+@pytest.mark.parametrize("half,jump", [(19, 9), (5, 1), (16, 1)])     # W = 7, 11 and 33 (more frames than a tile has items)
 @pytest.mark.parametrize("F", [80, 13])
 def test_gather_matches_the_oracle_per_clip(torch_cuda, lib, half, jump, F):
     from oracle import oracle
@@ -154,6 +154,20 @@ def test_gather_matches_the_oracle_per_clip(torch_cuda, lib, half, jump, F):
         assert not with_positions or np.array_equal(pos.cpu().numpy(), want_pos[first:first + count])
     win, _, _ = gather_batch(torch, lib, feature, table, half, jump, total - 1, 1)   # the last item alone: clip 6's second window
     assert np.array_equal(win.cpu().numpy(), want_win[-1:])
+    # one clip runs the same tile kernel (savad_gather_windows): the indexing rule feature[half + first + item + off[w]], positions
+    # included, at the edges of a 32-item tile, on a matrix that ends with the last window's last frame
+    off = oracle.window_offsets(half, jump)
+    rows = np.concatenate(per_clip)
+    for first in (0, 5):
+        for count in (1, 31, 32, 33):
+            N = 2 * half + first + count
+            one = torch.from_numpy(rows[:N].copy()).cuda()
+            win = torch.empty((count, len(off), F), dtype=torch.float32, device="cuda")
+            pos = torch.empty((count, len(off)), dtype=torch.int64, device="cuda")
+            ok(lib.savad_gather_windows(ptr(one), N, F, half, jump, first, count, ptr(win), ptr(pos), stream_(torch)))
+            want = half + first + np.arange(count)[:, None] + off[None, :]
+            assert want.min() == first and want[-1, -1] == N - 1
+            assert np.array_equal(pos.cpu().numpy(), want) and np.array_equal(win.cpu().numpy(), rows[want]), (first, count)
 
 
 # ---- 2. the boost against the existing path --------------------------------------------------------------------------------------

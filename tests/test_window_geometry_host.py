@@ -126,15 +126,58 @@ def _live_W(lib, half, jump):
     return counts.W
 
 
-def test_window_count_is_the_number_of_offsets_everywhere(lib, tmp_path):
+def _dump(tmp_path, name, *args):
+    """stdout of tests/<name>.cpp, compiled with the host compiler against the library's headers"""
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     if not cxx:
         pytest.fail("no host C++ compiler (g++ / c++ / clang++, or CXX)")
-    exe = tmp_path / "schedule_dump"
+    exe = tmp_path / name
     subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra", f"-I{REPO / 'voice_activity_detection_amd' / 'csrc'}",
-                    str(REPO / "tests" / "schedule_dump.cpp"), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe), "windows", "40", "12"], check=True, capture_output=True, text=True, timeout=60)
-    planned = {(int(h), int(j)): int(w) for h, j, w in (line.split() for line in out.stdout.splitlines())}
+                    str(REPO / "tests" / f"{name}.cpp"), "-o", str(exe)], check=True)
+    return subprocess.run([str(exe), *args], check=True, capture_output=True, text=True, timeout=60).stdout
+
+
+def test_the_geometry_header_is_the_rule(tmp_path):
+    """csrc/savad_windows.h alone (tests/windows_dump.cpp): the one copy of the offsets rule against numpy for half 0 .. 40 and jump
+    1 .. 12, the refusal of a window longer than 64 frames (a caller's int32_t[64] is never overrun), and the item, chunk and
+    workspace rules against their one-line definitions."""
+    lines = _dump(tmp_path, "windows_dump", "offsets", "40", "12").splitlines()
+    assert len(lines) == 41 * 12
+    seen_refusal = False
+    for line in lines:
+        head, _, tail = line.partition(" :")
+        _, half, jump, W, message = head.split(" ", 4)
+        half, jump, W = int(half), int(jump), int(W)
+        want = np.concatenate([np.arange(-half, 0, jump), [0], np.arange(1, half + 1, jump)])
+        assert np.array_equal(want, cases.offsets(half, jump))
+        assert W == len(want), (half, jump)
+        assert message == ("'window longer than 64 frames'" if W > 64 else "''"), (half, jump)
+        assert [int(v) for v in tail.split()] == list(want[:64]), (half, jump)
+        seen_refusal |= W > 64
+    assert seen_refusal and len(cases.offsets(32, 1)) == 65      # the boundary itself is among them
+    n = {"i": 0, "c": 0, "l": 0}
+    up = lambda b: (b + 255) // 256 * 256
+    for line in _dump(tmp_path, "windows_dump", "rules").splitlines():
+        kind, *v = line.replace(":", " ").split()
+        v = [int(x) for x in v]
+        n[kind] += 1
+        if kind == "i":
+            rows, half, items = v
+            assert items == max(0, rows - 2 * half), line
+        elif kind == "c":
+            chunk, n_items, even, at_most = v
+            assert at_most == max(1, min(chunk, n_items)), line
+            assert even == max(1, min(chunk + chunk % 2, n_items)), line      # even, at most n_items, at least 1
+        else:
+            table, logp_items, chunk, W, F, fwd, o_table, o_logp, o_win, o_fwd, total = v
+            assert o_table == 0 and o_logp == up(4 * table) and o_win == o_logp + up(4 * logp_items * W * 2), line
+            assert o_fwd == o_win + up(4 * chunk * W * F) and total == o_fwd + up(fwd), line
+    assert n == {"i": 40, "c": 99, "l": 5}
+
+
+def test_window_count_is_the_number_of_offsets_everywhere(lib, tmp_path):
+    out = _dump(tmp_path, "schedule_dump", "windows", "40", "12")
+    planned = {(int(h), int(j)): int(w) for h, j, w in (line.split() for line in out.splitlines())}
     assert len(planned) == 41 * 12
     disagree = []
     for half in range(41):

@@ -1038,24 +1038,31 @@ SAVAD_EXPORT int savad_last_kernel_times(savad_handle m, const char** names, flo
 
 SAVAD_EXPORT int savad_window_offsets(int half, int jump, int32_t* offsets) {
     if (half < 0 || jump <= 0) return fail(SAVAD_E_INVALID, "half=%d jump=%d", half, jump);
-    int w = 0;
-    for (int o = -half; o < 0; o += jump, ++w)
-        if (offsets) offsets[w] = o;
-    if (offsets) offsets[w] = 0;
-    ++w;
-    for (int o = 1; o < half + 1; o += jump, ++w)
-        if (offsets) offsets[w] = o;
-    return w;
+    const long W = windows::offsets(half, jump, nullptr);   // (the caller's buffer holds every offset, however many)
+    return (int)windows::offsets(half, jump, offsets, W);
 }
 
 namespace {
 // the window geometry as the kernels take it; a window longer than WindowOffsets holds is refused
 int window_offsets(int half, int jump, WindowOffsets* wo) {
-    wo->w = savad_window_offsets(half, jump, nullptr);
-    if (wo->w < 0) return wo->w;
-    if (wo->w > 64) return fail(SAVAD_E_UNSUPPORTED, "window longer than 64 frames");
-    static_assert(std::is_same<decltype(wo->off[0]), int32_t&>::value, "WindowOffsets::off");
-    savad_window_offsets(half, jump, wo->off);
+    if (half < 0 || jump <= 0) return fail(SAVAD_E_INVALID, "half=%d jump=%d", half, jump);
+    static_assert(std::is_same<decltype(wo->off[0]), int32_t&>::value && sizeof wo->off == sizeof(int32_t) * windows::MAX_FRAMES, "WindowOffsets::off");
+    const long W = windows::offsets(half, jump, wo->off);
+    if (W > windows::MAX_FRAMES) return fail(SAVAD_E_UNSUPPORTED, "%s", windows::TOO_LONG);
+    wo->w = (int)W;
+    return SAVAD_OK;
+}
+
+// The items [0, n_items) in `chunk` steps: gather(first, count) leaves a chunk's windows in `win`, one savad_forward turns them into
+// the chunk's log-probs at logp + first * W * 2 (16-byte aligned: chunk is even).  The boost that follows reads all of logp.
+template <class Gather>
+int forward_chunks(savad_handle m, int n_items, int chunk, int W, float* win, float* logp, void* fwd, size_t fwd_bytes, void* stream,
+                   Gather gather) {
+    for (int first = 0; first < n_items; first += chunk) {
+        const int count = n_items - first < chunk ? n_items - first : chunk;
+        if (int rc = gather(first, count)) return rc;
+        if (int rc = savad_forward(m, win, count, W, logp + (size_t)first * W * 2, fwd, fwd_bytes, stream)) return rc;
+    }
     return SAVAD_OK;
 }
 }  // namespace
@@ -1136,18 +1143,19 @@ SAVAD_EXPORT int savad_predict_probabilities(savad_handle m, const float* featur
         return fail(SAVAD_E_INVALID, "windows reach outside the %d feature frames", N);
     char* ws = (char*)workspace;
     float* logp = (float*)(ws + p.logp);
-    if (p.windowed && p.n_items > 0 && (rc = ensure_ready(m, p.family, W, st))) return rc;
-    for (int first = 0; first < p.n_items; first += p.chunk) {
-        const int count = p.n_items - first < p.chunk ? p.n_items - first : p.chunk;
-        float* out = logp + (size_t)first * W * 2;
-        const int variant = count == p.chunk ? p.variant : p.variant_last;
-        if (p.windowed) {
-            launch_single(m, p.family, variant, st, feature, count, W, F, out, wo, half + first);
-        } else {
-            float* win = (float*)(ws + p.windows);
-            if ((rc = savad_gather_windows(feature, N, F, half, jump, first, count, win, nullptr, stream))) return rc;
-            if ((rc = savad_forward(m, win, count, W, out, ws + p.fwd, p.fwd_bytes, stream))) return rc;
+    if (p.windowed) {   // the single-launch forwards read their windows in place
+        if (p.n_items > 0 && (rc = ensure_ready(m, p.family, W, st))) return rc;
+        for (int first = 0; first < p.n_items; first += p.chunk) {
+            const int count = p.n_items - first < p.chunk ? p.n_items - first : p.chunk;
+            launch_single(m, p.family, count == p.chunk ? p.variant : p.variant_last, st, feature, count, W, F, logp + (size_t)first * W * 2, wo,
+                          half + first);
         }
+    } else {
+        float* win = (float*)(ws + p.windows);
+        rc = forward_chunks(m, p.n_items, p.chunk, W, win, logp, ws + p.fwd, p.fwd_bytes, stream, [&](int first, int count) {
+            return savad_gather_windows(feature, N, F, half, jump, first, count, win, nullptr, stream);
+        });
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(boost_gather_kernel, dim3(grid_for(N, 2048)), dim3(256), 0, st, logp, p.n_items, N, half, wo, probs, mean);
     HIP_TRY(hipGetLastError());
@@ -1257,12 +1265,12 @@ SAVAD_EXPORT int savad_predict_probabilities_batch(savad_handle m, const float* 
     float* logp = (float*)(ws + p.logp);
     float* win = (float*)(ws + p.windows);
     launch_items_scan(clip_first, C, half, items_first, st);
-    for (int first = 0; first < p.n_items; first += p.chunk) {
-        const int count = p.n_items - first < p.chunk ? p.n_items - first : p.chunk;
+    rc = forward_chunks(m, p.n_items, p.chunk, W, win, logp, ws + p.fwd, p.fwd_bytes, stream, [&](int first, int count) {
         launch_gather_batch(feature, F, clip_first, items_first, C, half, first, count, wo, win, nullptr, st);
         HIP_TRY(hipGetLastError());
-        if ((rc = savad_forward(m, win, count, W, logp + (size_t)first * W * 2, ws + p.fwd, p.fwd_bytes, stream))) return rc;
-    }
+        return (int)SAVAD_OK;
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(boost_gather_batch_kernel, dim3(grid_for(p.rows, 2048)), dim3(256), 0, st, logp, clip_first, (const int32_t*)items_first, C,
                        p.rows, half, wo, probs, mean);
     HIP_TRY(hipGetLastError());
@@ -1536,10 +1544,11 @@ int live_tables(const savad_live_config* c, const void* table_host, const void* 
 template <class T>
 const T* live_at(const void* table_dev, int32_t offset) { return reinterpret_cast<const T*>(reinterpret_cast<const char*>(table_dev) + offset); }
 
-// windows [chunk, W, F] | logp [items, W, 2] | the forward's own scratch
+// the tick's chunk and its workspace (savad_windows.h: layout; no table)
 struct LiveWorkspace {
     int chunk;
-    size_t windows, logp, fwd, fwd_bytes, total;
+    size_t fwd_bytes;
+    windows::Layout at;
 };
 int live_workspace(savad_handle m, const live::Geometry& g, int chunk, long max_items, LiveWorkspace* w) {
     const int unit = live::chunk_items(g, 1);
@@ -1549,11 +1558,7 @@ int live_workspace(savad_handle m, const live::Geometry& g, int chunk, long max_
     if (m->cfg.feature_size != g.F) return fail(SAVAD_E_UNSUPPORTED, "the live mode runs the shipped %d-mel front-end; the model takes %d features", g.F, m->cfg.feature_size);
     int rc = savad_workspace_bytes(m, w->chunk, g.W, &w->fwd_bytes);
     if (rc) return rc;
-    Arena a;
-    w->windows = a.take(sizeof(float) * (size_t)w->chunk * g.W * g.F);
-    w->logp = a.take(sizeof(float) * (size_t)max_items * g.W * 2);
-    w->fwd = a.take(w->fwd_bytes);
-    w->total = a.off;
+    w->at = windows::layout(0, max_items, w->chunk, g.W, g.F, w->fwd_bytes);
     return SAVAD_OK;
 }
 
@@ -1591,7 +1596,7 @@ SAVAD_EXPORT int savad_live_workspace_bytes(savad_handle m, const savad_live_con
     if (max_pushes < 0 || max_pushes > g.streams) return fail(SAVAD_E_INVALID, "max_pushes=%d of %d streams", max_pushes, g.streams);
     LiveWorkspace w;
     if (int rc = live_workspace(m, g, config->chunk, (long)max_pushes * g.max_items(), &w)) return rc;
-    *bytes = w.total;
+    *bytes = w.at.total;
     return SAVAD_OK;
 }
 SAVAD_EXPORT int savad_live_open(const savad_live_config* config, savad_live_slot* slots, int slot) {
@@ -1697,20 +1702,19 @@ SAVAD_EXPORT int savad_live_step(savad_handle m, const savad_live_config* config
     if (h->n_items > 0) {
         if (int rc = live_workspace(m, g, config->chunk, h->n_items, &w)) return rc;
         if (!workspace || ((uintptr_t)workspace & 15)) return fail(SAVAD_E_INVALID, "workspace must be a 16-byte aligned pointer");
-        if (workspace_bytes < w.total) return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, w.total);
+        if (workspace_bytes < w.at.total) return fail(SAVAD_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, w.at.total);
     }
     if (h->n_rows > 0 && !probs) return fail(SAVAD_E_INVALID, "null output");
     int rc;
     if ((rc = savad_live_append(config, table_host, table_dev, stream))) return rc;
     if ((rc = savad_live_logmel(config, table_host, table_dev, stream))) return rc;
     char* ws = (char*)workspace;
-    float* logp = h->n_items > 0 ? (float*)(ws + w.logp) : nullptr;
-    for (int first = 0; first < h->n_items; first += w.chunk) {
-        const int count = h->n_items - first < w.chunk ? h->n_items - first : w.chunk;
-        float* win = (float*)(ws + w.windows);
-        if ((rc = savad_live_gather(config, table_host, table_dev, first, count, win, stream))) return rc;
-        if ((rc = savad_forward(m, win, count, g.W, logp + (size_t)first * g.W * 2, ws + w.fwd, w.fwd_bytes, stream))) return rc;
-    }
+    float* logp = h->n_items > 0 ? (float*)(ws + w.at.logp) : nullptr;
+    float* win = (float*)(ws + w.at.windows);
+    rc = forward_chunks(m, h->n_items, w.chunk, g.W, win, logp, ws + w.at.fwd, w.fwd_bytes, stream, [&](int first, int count) {
+        return savad_live_gather(config, table_host, table_dev, first, count, win, stream);
+    });
+    if (rc) return rc;
     if ((rc = savad_live_boost(config, table_host, table_dev, logp, probs, mean, stream))) return rc;
     live::commit(table_host, reinterpret_cast<live::Slot*>(slots));
     return SAVAD_OK;

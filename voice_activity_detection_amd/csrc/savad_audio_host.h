@@ -10,17 +10,9 @@
 #include <utility>
 #include <vector>
 
-namespace savad {
+#include "savad_windows.h"   // Arena
 
-// consecutive 256-byte-aligned regions of a caller's workspace or of one device allocation
-struct Arena {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    }
-};
+namespace savad {
 
 // ---- Slaney mel scale and filterbank (librosa htk=False, norm="slaney", fmin 0, fmax 8 kHz @16 kHz) ---------------------------
 

@@ -46,6 +46,15 @@ __global__ void fold_ln_kernel(const float* __restrict__ W, const float* __restr
 // ---------------------------------------------------------------------------------------------
 // a13: window gather (vad/predictor.py:180-220).  One thread per output float4.
 // ---------------------------------------------------------------------------------------------
+// one piece of a window row, 16 bytes (VEC) or one float, from `from` to `to`: what every window gather moves (DUMMIES: a null
+// `from` gives zeros)
+template <bool VEC, bool DUMMIES = false>
+__device__ __forceinline__ void move_piece(const float* __restrict__ from, float* __restrict__ to) {
+    if (VEC)
+        st4(to, !DUMMIES || from ? ld4(from) : f32x4{0.0f, 0.0f, 0.0f, 0.0f});
+    else
+        *to = !DUMMIES || from ? *from : 0.0f;
+}
 __global__ void gather_windows_kernel(const float* __restrict__ feature, int F, int half, int first, int count,
                                       WindowOffsets wo, float* __restrict__ windows, int64_t* __restrict__ positions) {
     const int f4 = F / 4;
@@ -56,7 +65,7 @@ __global__ void gather_windows_kernel(const float* __restrict__ feature, int F, 
         const int wi = (int)(iw % wo.w);
         const size_t item = iw / wo.w;
         const size_t pos = (size_t)half + first + item + wo.off[wi];
-        st4(windows + iw * F + 4 * c, ld4(feature + pos * F + 4 * c));
+        move_piece<true>(feature + pos * F + 4 * c, windows + iw * F + 4 * c);
         if (c == 0 && positions) positions[iw] = (int64_t)pos;
     }
 }
@@ -71,7 +80,7 @@ __global__ void gather_windows_scalar_kernel(const float* __restrict__ feature, 
         const int wi = (int)(iw % wo.w);
         const size_t item = iw / wo.w;
         const size_t pos = (size_t)half + first + item + wo.off[wi];
-        windows[i] = feature[pos * F + c];
+        move_piece<false>(feature + pos * F + c, windows + i);
         if (c == 0 && positions) positions[iw] = (int64_t)pos;
     }
 }
@@ -110,6 +119,19 @@ __device__ __forceinline__ float boost_slot(f32x2 z) {
     return e1 / (e0 + e1);
 }
 
+// One output row of every such kernel: slot(w) names the (log p0, log p1) of slot w, or the (0, 0) placeholder -> exactly 0.5;
+// the row's W probabilities are stored and summed in slot order, the mean is the sum over W.  The kernels differ only in `slot`.
+template <class Slot>
+__device__ __forceinline__ void boost_row(int row, int W, Slot slot, float* __restrict__ probs, float* __restrict__ mean) {
+    float acc = 0.0f;
+    for (int wi = 0; wi < W; ++wi) {
+        const float p = boost_slot(slot(wi));
+        probs[(size_t)row * W + wi] = p;
+        acc += p;
+    }
+    if (mean) mean[row] = acc / (float)W;
+}
+
 // The same result as scatter + softmax, read the other way round: slot (n, w) of the boosted array was written by
 // window b = n - half - off[w] if that window exists, else it still holds (0, 0) -> 0.5.  Same arithmetic on the same
 // values, no memset, no scatter launch, no positions array.
@@ -117,16 +139,12 @@ __global__ void boost_gather_kernel(const float* __restrict__ logp, int n_items,
                                     float* __restrict__ probs, float* __restrict__ mean) {
     const int W = wo.w;
     for (int nrow = blockIdx.x * blockDim.x + threadIdx.x; nrow < N; nrow += gridDim.x * blockDim.x) {
-        float acc = 0.0f;
-        for (int wi = 0; wi < W; ++wi) {
+        boost_row(nrow, W, [&](int wi) {
             const int b = nrow - half - wo.off[wi];
             f32x2 z = f32x2{0.0f, 0.0f};
             if (b >= 0 && b < n_items) z = *reinterpret_cast<const f32x2*>(logp + ((size_t)b * W + wi) * 2);
-            const float p = boost_slot(z);
-            probs[(size_t)nrow * W + wi] = p;
-            acc += p;
-        }
-        if (mean) mean[nrow] = acc / (float)W;
+            return z;
+        }, probs, mean);
     }
 }
 

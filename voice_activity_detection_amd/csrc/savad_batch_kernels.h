@@ -4,8 +4,9 @@
 // neighbour.  items_first[C + 1] = the exclusive prefix sum of n_c: global item g belongs to the clip c with
 // items_first[c] <= g < items_first[c + 1] (an empty clip, or one too short for a window, owns no g and is never found).
 #pragma once
-#include "savad_aux_kernels.h"   // boost_slot
+#include "savad_aux_kernels.h"   // boost_row
 #include "savad_device.h"
+#include "savad_windows.h"   // the item rule
 
 namespace savad {
 
@@ -36,10 +37,7 @@ __global__ __launch_bounds__(BATCH_SCAN_THREADS) void clip_items_scan_kernel(con
     for (int base = 0; base < C; base += BATCH_SCAN_THREADS) {
         const int c = base + t;
         int n = 0;
-        if (c < C) {
-            n = clip_first[c + 1] - clip_first[c] - 2 * half;
-            n = n > 0 ? n : 0;
-        }
+        if (c < C) n = (int)windows::items(clip_first[c + 1] - clip_first[c], half);
         part[t] = n;
         __syncthreads();
         for (int d = 1; d < BATCH_SCAN_THREADS; d <<= 1) {
@@ -86,10 +84,7 @@ __global__ __launch_bounds__(256) void gather_windows_batch_kernel(const float* 
             const int wi = r / pieces, p = r - wi * pieces;
             const size_t row = (size_t)(centre[it] + wo.off[wi]);
             const size_t iw = (size_t)(i0 + it) * W + wi;
-            if (VEC)
-                st4(windows + iw * F + 4 * p, ld4(feature + row * F + 4 * p));
-            else
-                windows[iw * F + p] = feature[row * F + p];
+            move_piece<VEC>(feature + row * F + (VEC ? 4 : 1) * p, windows + iw * F + (VEC ? 4 : 1) * p);
             if (p == 0 && positions) positions[iw] = (int64_t)row;
         }
         __syncthreads();
@@ -99,7 +94,7 @@ __global__ __launch_bounds__(256) void gather_windows_batch_kernel(const float* 
 // ---------------------------------------------------------------------------------------------
 // Boosted prediction (vad/predictor.py:238-258, :95) read as a gather, per clip: row n of clip c (local = n - clip_first[c]) takes
 // slot w from the clip's window b = local - half - off[w] when it exists, else (0, 0) -> exactly 0.5.  The arithmetic is
-// boost_gather_kernel's (savad_aux_kernels.h) operation for operation: a one-clip table gives its bits.
+// boost_gather_kernel's (savad_aux_kernels.h: boost_row): a one-clip table gives its bits.
 // ---------------------------------------------------------------------------------------------
 __global__ void boost_gather_batch_kernel(const float* __restrict__ logp, const int32_t* __restrict__ clip_first,
                                           const int32_t* __restrict__ items_first, int C, int N, int half, WindowOffsets wo,
@@ -108,16 +103,12 @@ __global__ void boost_gather_batch_kernel(const float* __restrict__ logp, const 
     for (int nrow = blockIdx.x * blockDim.x + threadIdx.x; nrow < N; nrow += gridDim.x * blockDim.x) {
         const int c = last_not_above(clip_first, C, nrow);
         const int local = nrow - clip_first[c], item0 = items_first[c], n_items = items_first[c + 1] - item0;
-        float acc = 0.0f;
-        for (int wi = 0; wi < W; ++wi) {
+        boost_row(nrow, W, [&](int wi) {
             const int b = local - half - wo.off[wi];
             f32x2 z = f32x2{0.0f, 0.0f};
             if (b >= 0 && b < n_items) z = *reinterpret_cast<const f32x2*>(logp + ((size_t)(item0 + b) * W + wi) * 2);
-            const float p = boost_slot(z);
-            probs[(size_t)nrow * W + wi] = p;
-            acc += p;
-        }
-        if (mean) mean[nrow] = acc / (float)W;
+            return z;
+        }, probs, mean);
     }
 }
 

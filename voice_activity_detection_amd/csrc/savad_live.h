@@ -2,7 +2,7 @@
 // host plan (savad_live_plan.h) built for the tick: append -> log-mel over the tile table -> window gather over the item table ->
 // savad_forward -> log-prob history and boost.  Entries, tiles and items are read-only here; the state they point into is the caller's.
 #pragma once
-#include "savad_aux_kernels.h"     // boost_slot
+#include "savad_aux_kernels.h"     // boost_row, move_piece
 #include "savad_batch_kernels.h"   // last_not_above
 #include "savad_live_plan.h"
 #include "savad_logmel.h"
@@ -80,12 +80,12 @@ __global__ __launch_bounds__(256) void gather_items_kernel(const Entry* __restri
         const long iw = i / pieces;
         const int wi = (int)(iw % W);
         const Item it = items[first + iw / W];
-        f32x4 v = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        const float* from = nullptr;
         if (it.entry >= 0) {
             const int row = (it.centre + wo.off[wi] + cap) % cap;
-            v = ld4(reinterpret_cast<const float*>(entries[it.entry].feat) + (size_t)row * F + 4 * p);
+            from = reinterpret_cast<const float*>(entries[it.entry].feat) + (size_t)row * F + 4 * p;
         }
-        st4(windows + (size_t)iw * F + 4 * p, v);
+        move_piece<true, true>(from, windows + (size_t)iw * F + 4 * p);
     }
 }
 
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void gather_items_kernel(const Entry* __restri
 // Log-prob history and boost: output row t (compact, stream order) is row r = t - row_out of its entry, row row_first + r of the
 // recording.  Slot w takes window r - half - off[w] counted from the entry's first new window: >= 0 is an item of this tick (when it
 // exists), below 0 a window the ring kept (when the recording has it), anything else the (0, 0) placeholder -> exactly 0.5
-// (boost_gather_kernel's arithmetic: boost_slot).  Row r < n_windows also files window r's log-probs in the ring -- at positions
+// (boost_gather_kernel's arithmetic: boost_row).  Row r < n_windows also files window r's log-probs in the ring -- at positions
 // no row of this launch reads.
 // ---------------------------------------------------------------------------------------------
 __global__ void boost_history_kernel(const Entry* __restrict__ entries, const int32_t* __restrict__ row_out, int n_entries, int n_rows,
@@ -105,8 +105,7 @@ __global__ void boost_history_kernel(const Entry* __restrict__ entries, const in
         const Entry& e = entries[c];
         const int r = t - e.row_out;
         float* ring = reinterpret_cast<float*>(e.logp);
-        float acc = 0.0f;
-        for (int wi = 0; wi < W; ++wi) {
+        boost_row(t, W, [&](int wi) {
             const int b = r - half - wo.off[wi];
             f32x2 z = f32x2{0.0f, 0.0f};
             if (b >= 0) {
@@ -114,11 +113,8 @@ __global__ void boost_history_kernel(const Entry* __restrict__ entries, const in
             } else if (b >= -e.win_kept) {
                 z = *reinterpret_cast<const f32x2*>(ring + ((size_t)((e.win_first_mod + b + cap) % cap) * W + wi) * 2);
             }
-            const float p = boost_slot(z);
-            probs[(size_t)t * W + wi] = p;
-            acc += p;
-        }
-        if (mean) mean[t] = acc / (float)W;
+            return z;
+        }, probs, mean);
         if (r < e.n_windows)
             for (int wi = 0; wi < W; ++wi)
                 *reinterpret_cast<f32x2*>(ring + ((size_t)((e.win_first_mod + r) % cap) * W + wi) * 2) =

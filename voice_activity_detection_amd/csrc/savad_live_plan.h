@@ -27,6 +27,7 @@
 #include <string.h>
 
 #include "savad_audio_host.h"
+#include "savad_windows.h"   // the window offsets, the item rule
 
 namespace savad {
 namespace live {
@@ -41,30 +42,19 @@ constexpr uint32_t TABLE_MAGIC = 0x4c495645u;
 
 inline long ready_frames(long n) { return n < MIN_SAMPLES ? 0 : (n - READ_BEFORE) / HOP + 1; }
 inline long total_frames(long n) { return 1 + n / HOP; }
-inline long final_rows(long frames, int half) { return frames > 2L * half ? frames - 2L * half : 0; }
+inline long final_rows(long frames, int half) { return windows::items(frames, half); }
 // first sample the frames that are not ready after n samples still read
 inline long keep_from(long n) {
     const long s = (long)HOP * ready_frames(n) - READ_BEFORE;
     return s > 0 ? s : 0;
 }
 
-inline int window_offsets(int half, int jump, int32_t* off) {   // savad_window_offsets
-    int w = 0;
-    for (int o = -half; o < 0; o += jump, ++w)
-        if (off && w < 64) off[w] = o;
-    if (off && w < 64) off[w] = 0;
-    ++w;
-    for (int o = 1; o < half + 1; o += jump, ++w)
-        if (off && w < 64) off[w] = o;
-    return w;
-}
-
 struct Geometry {
     int err = 0;
     const char* msg = nullptr;
     int streams = 0, max_push = 0, half = 0, jump = 0, F = N_MELS, W = 0, P = 1;
-    int32_t off[64];
-    int max_new = 0;                        // frames (hence windows) one tick adds to a stream at most
+    int32_t off[windows::MAX_FRAMES];
+    int max_new = 0;                       // frames (hence windows) one tick adds to a stream at most
     int max_rows = 0;                       // rows one tick emits for a stream at most (finish)
     int feat_cap = 0, logp_cap = 0, sample_cap = 0;
     size_t o_samples = 0, o_head = 0, o_tail = 0, o_feat = 0, o_logp = 0, stride = 0;   // bytes inside a slot's state
@@ -87,13 +77,13 @@ inline Geometry geometry(int streams, int max_push, int half, int jump) {
         g.msg = "more than 2^24 samples per push or 2^20 streams";
         return g;
     }
-    g.W = window_offsets(half, jump, nullptr);
-    if (g.W > 64) {
+    const long W = windows::offsets(half, jump, g.off);
+    if (W > windows::MAX_FRAMES) {
         g.err = -2;
-        g.msg = "window longer than 64 frames";
+        g.msg = windows::TOO_LONG;
         return g;
     }
-    window_offsets(half, jump, g.off);
+    g.W = (int)W;
     g.streams = streams, g.max_push = max_push, g.half = half, g.jump = jump;
     g.P = g.W <= 32 ? 32 / g.W : 1;
     // K(n + p) - K(n) <= p / 160 + 2 (from K = 0), N(n + p) - K(n) <= p / 160 + 3

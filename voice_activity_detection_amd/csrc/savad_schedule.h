@@ -9,6 +9,7 @@
 
 #include "../../include/savad.h"
 #include "savad_dims.h"
+#include "savad_windows.h"
 
 // ---- experiment-build knobs (-D on the compile line; the product is built with the defaults)
 #ifndef SAVAD_INPUT_PERSISTENT
@@ -86,7 +87,7 @@ struct PredictPlan {
 
 constexpr const char* STRIDE_REFUSED = "strided input: no kernel takes the stride for this shape";
 
-inline long window_count(int half, int jump) { return 2 * (((long)half + jump - 1) / jump) + 1; }  // savad_window_offsets: -half .. -1, 0, 1 .. half in steps of jump
+inline long window_count(int half, int jump) { return windows::offsets(half, jump, nullptr); }  // W, as tests/schedule_dump.cpp prints it
 
 // packed blocks of a T <= 32 batch: floor(32 / T) sequences share a 32-row block
 inline long packed_blocks(int B, int T) { return ((long)B + 32 / T - 1) / (32 / T); }
@@ -420,14 +421,14 @@ inline ForwardPlan plan_forward(const Knobs& m, int B, int T, bool x_is_bf16, lo
 inline PredictPlan plan_predict(const Knobs& m, int N, int half, int jump, int chunk) {
     PredictPlan pp;
     PredictPlan* p = &pp;
-    const long Wl = window_count(half, jump);
+    const long Wl = windows::offsets(half, jump, nullptr);
     p->W = (int)(Wl < 65 ? Wl : 65);
-    if (p->W > 64) {
+    if (Wl > windows::MAX_FRAMES) {
         p->err = SAVAD_E_UNSUPPORTED;
-        p->msg = "window longer than 64 frames";
+        p->msg = windows::TOO_LONG;
         return pp;
     }
-    p->n_items = N - 2 * half > 0 ? N - 2 * half : 0;  // vad/predictor.py:169
+    p->n_items = (int)windows::items(N, half);
     const int F = m.feature_size;
     // windowed: the whole clip in ONE single-launch forward (up to 1024 packed tiles = 4096 windows of 7 frames, ~41 s of
     // audio: savad_forward's own limit for that kernel); longer inputs go through `chunk`-sized M-split forwards, which
@@ -442,11 +443,8 @@ inline PredictPlan plan_predict(const Knobs& m, int N, int half, int jump, int c
         p->windowed = !m.generic && p->W <= 32 && m.num_layers <= PACKED_MAX_LAYERS && m.FP == F &&
                       (m.row_mode == 4 || (m.row_mode == 0 && p->n_items <= 1024 * (32 / p->W)));
     p->family = m.generic ? GENERIC : m.precision == 1 ? BF16 : p->f32s ? F32S : F32;
-    // chunk-sized forwards write their log-probs at logp + first*W*2 floats and savad_forward wants 16-byte aligned
-    // pointers: an even chunk keeps every offset a multiple of 16 bytes whatever W is (windows are independent, so the
-    // chunking never changes a result beyond fp32 summation order)
-    p->chunk = p->windowed ? (m.precision == 1 || p->f32s ? (1 << 22) : 1024 * (32 / p->W)) : chunk + (chunk & 1);
-    if (p->chunk > p->n_items) p->chunk = p->n_items > 0 ? p->n_items : 1;
+    p->chunk = p->windowed ? windows::at_most_items(m.precision == 1 || p->f32s ? (1 << 22) : 1024 * (32 / p->W), p->n_items)
+                           : windows::even_chunk(chunk, p->n_items);
     if (p->windowed && p->n_items > 0 && p->family != F32) {
         auto variant = [&](int count) {
             const long nblk = packed_blocks(count, p->W);
@@ -456,19 +454,9 @@ inline PredictPlan plan_predict(const Knobs& m, int N, int half, int jump, int c
         p->variant = variant(p->chunk);
         p->variant_last = last ? variant(last) : p->variant;
     }
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    size_t off = 0;
-    p->logp = off;
-    off += up(sizeof(float) * (size_t)(p->n_items > 0 ? p->n_items : 1) * p->W * 2);
-    p->windows = p->fwd = off;
-    p->fwd_bytes = 0;
-    if (!p->windowed) {
-        off += up(sizeof(float) * (size_t)p->chunk * p->W * F);
-        p->fwd = off;
-        p->fwd_bytes = plan_forward(m, p->chunk, p->W, false, 0).total;
-        off += up(p->fwd_bytes);
-    }
-    p->total = off;
+    p->fwd_bytes = p->windowed ? 0 : plan_forward(m, p->chunk, p->W, false, 0).total;
+    const windows::Layout l = windows::layout(0, p->n_items > 0 ? p->n_items : 1, p->windowed ? 0 : p->chunk, p->W, F, p->fwd_bytes);
+    p->logp = l.logp, p->windows = l.windows, p->fwd = l.fwd, p->total = l.total;
     return pp;
 }
 
@@ -500,15 +488,15 @@ inline ClipTotals clip_totals(const int32_t* clip_first, int C, int half, int ju
     };
     if (!clip_first || C < 1) return refuse(SAVAD_E_INVALID, "clip table: at least one clip");
     if (half < 0 || jump <= 0) return refuse(SAVAD_E_INVALID, "half must not be negative, jump must be positive");
-    const long Wl = window_count(half, jump);
-    if (Wl > 64) return refuse(SAVAD_E_UNSUPPORTED, "window longer than 64 frames");
+    const long Wl = windows::offsets(half, jump, nullptr);
+    if (Wl > windows::MAX_FRAMES) return refuse(SAVAD_E_UNSUPPORTED, windows::TOO_LONG);
     t.W = (int)Wl;
     if (clip_first[0] != 0) return refuse(SAVAD_E_INVALID, "clip table: clip_first[0] must be 0");
     long items = 0;
     for (int c = 0; c < C; ++c) {
         const long n = (long)clip_first[c + 1] - clip_first[c];
         if (n < 0) return refuse(SAVAD_E_INVALID, "clip table: clip_first must not decrease");
-        items += n - 2L * half > 0 ? n - 2L * half : 0;
+        items += windows::items(n, half);
     }
     t.rows = clip_first[C];  // (an int32 table cannot name more than BATCH_INDEX_LIMIT rows)
     if (items * t.W > BATCH_INDEX_LIMIT) return refuse(SAVAD_E_UNSUPPORTED, "windows x frames of all clips exceed the 32-bit index range");
@@ -519,7 +507,7 @@ inline ClipTotals clip_totals(const int32_t* clip_first, int C, int half, int ju
 // The plan of the one call from the HOST copy of the table: validates it, counts the items and lays the
 // workspace out: items_first [C + 1] int32 | logp [n_items, W, 2] | windows [chunk, W, F] | the chunk-sized forward's workspace.  The
 // windows are always copied and every chunk is a savad_forward of its own, in every precision and row mode (the packed kernels
-// read windows in place at ONE row pitch; a chunk of a ragged matrix has none).  The chunk rule is plan_predict's: even, at most n_items.
+// read windows in place at ONE row pitch; a chunk of a ragged matrix has none).
 inline PredictBatchPlan plan_predict_batch(const Knobs& m, const int32_t* clip_first, int C, int half, int jump, int chunk) {
     PredictBatchPlan p;
     const ClipTotals t = clip_totals(clip_first, C, half, jump);
@@ -534,20 +522,10 @@ inline PredictBatchPlan plan_predict_batch(const Knobs& m, const int32_t* clip_f
     p.C = C;
     p.rows = t.rows;
     p.n_items = t.n_items;
-    const long even = (long)chunk + (chunk & 1);
-    p.chunk = even <= p.n_items ? (int)even : (p.n_items > 0 ? p.n_items : 1);
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    size_t off = 0;
-    p.items_first = off;
-    off += up(sizeof(int32_t) * ((size_t)C + 1));
-    p.logp = off;
-    off += up(sizeof(float) * (size_t)(p.n_items > 0 ? p.n_items : 1) * p.W * 2);
-    p.windows = off;
-    off += up(sizeof(float) * (size_t)p.chunk * p.W * m.feature_size);
-    p.fwd = off;
+    p.chunk = windows::even_chunk(chunk, p.n_items);
     p.fwd_bytes = plan_forward(m, p.chunk, p.W, false, 0).total;
-    off += up(p.fwd_bytes);
-    p.total = off;
+    const windows::Layout l = windows::layout((size_t)C + 1, p.n_items > 0 ? p.n_items : 1, p.chunk, p.W, m.feature_size, p.fwd_bytes);
+    p.items_first = l.items_first, p.logp = l.logp, p.windows = l.windows, p.fwd = l.fwd, p.total = l.total;
     return p;
 }
 

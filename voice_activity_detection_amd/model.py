@@ -391,32 +391,7 @@ class SelfAttentiveVAD(nn.Module):
         """The whole of VADFromScratchPredictor.predict_probabilities (vad/predictor.py:159-262) in ONE library call
         (savad_predict_probabilities): feature [N, F] fp32 on the device -> (probs [N, W], mean [N]); the windows are
         read straight out of the feature matrix when the single-launch forward applies."""
-        device = feature.device
-        if device.type != "cuda":
-            self._prepare_call(device)  # raises: no CPU fallback
-        feat = feature.detach().float().contiguous()
-        if feat.dim() != 2 or feat.shape[1] != self.feature_size:
-            raise ValueError(f"feature must be [N, {self.feature_size}], got {tuple(feat.shape)}")
-        if feat.data_ptr() % 16:   # (savad_predict_probabilities wants the matrix 16-byte aligned; the module takes any tensor)
-            feat = feat.clone()
-        N = feat.shape[0]
-        lib = _lib.load()
-        W = lib.savad_window_offsets(int(half), int(jump), None)
-        probs = torch.empty((N, W), dtype=torch.float32, device=device)
-        mean = torch.empty((N,), dtype=torch.float32, device=device)
-        if N == 0:
-            return probs, mean
-        with torch.cuda.device(device):
-            self._prepare_call(device)
-            nbytes = ctypes.c_size_t()
-            _lib.check(lib.savad_predict_workspace_bytes(self._handle, N, int(half), int(jump), int(chunk), ctypes.byref(nbytes)))
-            ws = self._workspace_for(nbytes.value, device)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.savad_predict_probabilities(self._handle, ctypes.c_void_p(feat.data_ptr()), N, int(half), int(jump),
-                                                       int(chunk), ctypes.c_void_p(probs.data_ptr()),
-                                                       ctypes.c_void_p(mean.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                                                       ws.numel(), ctypes.c_void_p(stream)))
-        return probs, mean
+        return self._predict_windows(feature, half, jump, chunk)
 
     @torch.no_grad()
     def predict_windows_batch(self, feature: Tensor, clip_first, half: int, jump: int, chunk: int):
@@ -424,38 +399,49 @@ class SelfAttentiveVAD(nn.Module):
         device holds the clips one after the other, clip_first [C + 1] (clips.clip_table: list, array or tensor) says where each
         starts -> (probs [sum N, W], mean [sum N]), clip c's result in its rows.  No window crosses a clip boundary and every clip
         keeps its own 0.5 placeholders; the windows of all clips share `chunk`-sized forwards."""
-        from .clips import check_clip_table
+        return self._predict_windows(feature, half, jump, chunk, clip_first)
 
+    def _predict_windows(self, feature: Tensor, half: int, jump: int, chunk: int, clip_first=None):
+        """predict_windows (no clip table) and predict_windows_batch: the feature check and alignment clone, the outputs, the
+        workspace query and the call."""
         device = feature.device
         if device.type != "cuda":
             self._prepare_call(device)  # raises: no CPU fallback
         feat = feature.detach().float().contiguous()
         if feat.dim() != 2 or feat.shape[1] != self.feature_size:
             raise ValueError(f"feature must be [N, {self.feature_size}], got {tuple(feat.shape)}")
-        table = check_clip_table(clip_first.cpu().numpy() if isinstance(clip_first, Tensor) else clip_first)
-        N, C = feat.shape[0], table.size - 1
-        if int(table[-1]) != N:
-            raise ValueError(f"the clip table ends at row {int(table[-1])}, the feature matrix has {N}")
+        N = feat.shape[0]
+        table = None
+        if clip_first is not None:
+            from .clips import check_clip_table
+
+            table = check_clip_table(clip_first.cpu().numpy() if isinstance(clip_first, Tensor) else clip_first)
+            if int(table[-1]) != N:
+                raise ValueError(f"the clip table ends at row {int(table[-1])}, the feature matrix has {N}")
         if feat.data_ptr() % 16:   # (the library wants the matrix 16-byte aligned; the module takes any tensor)
             feat = feat.clone()
         lib = _lib.load()
-        W = lib.savad_window_offsets(int(half), int(jump), None)
+        geometry = (int(half), int(jump), int(chunk))
+        W = lib.savad_window_offsets(geometry[0], geometry[1], None)
         probs = torch.empty((N, W), dtype=torch.float32, device=device)
         mean = torch.empty((N,), dtype=torch.float32, device=device)
         if N == 0:
             return probs, mean
-        host = ctypes.c_void_p(table.ctypes.data)
         with torch.cuda.device(device):
             self._prepare_call(device)
-            table_dev = torch.from_numpy(table).to(device)   # (the library uploads nothing: the device copy is the caller's)
+            if table is None:
+                size, run, clips_host, clips = lib.savad_predict_workspace_bytes, lib.savad_predict_probabilities, (N,), (N,)
+            else:
+                table_dev = torch.from_numpy(table).to(device)   # (the library uploads nothing: the device copy is the caller's)
+                host = ctypes.c_void_p(table.ctypes.data)
+                size, run = lib.savad_predict_batch_workspace_bytes, lib.savad_predict_probabilities_batch
+                clips_host, clips = (host, table.size - 1), (host, ctypes.c_void_p(table_dev.data_ptr()), table.size - 1)
             nbytes = ctypes.c_size_t()
-            _lib.check(lib.savad_predict_batch_workspace_bytes(self._handle, host, C, int(half), int(jump), int(chunk), ctypes.byref(nbytes)))
+            _lib.check(size(self._handle, *clips_host, *geometry, ctypes.byref(nbytes)))
             ws = self._workspace_for(nbytes.value, device)
             stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.savad_predict_probabilities_batch(self._handle, ctypes.c_void_p(feat.data_ptr()), host,
-                                                             ctypes.c_void_p(table_dev.data_ptr()), C, int(half), int(jump), int(chunk),
-                                                             ctypes.c_void_p(probs.data_ptr()), ctypes.c_void_p(mean.data_ptr()),
-                                                             ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream)))
+            _lib.check(run(self._handle, ctypes.c_void_p(feat.data_ptr()), *clips, *geometry, ctypes.c_void_p(probs.data_ptr()),
+                           ctypes.c_void_p(mean.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream)))
         return probs, mean
 
     def reserve(self, max_frames: int, device=None, max_batch: int = 0):

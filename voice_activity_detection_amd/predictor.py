@@ -235,31 +235,28 @@ class VADFromScratchPredictor:
             from .features import FrontEnd
 
             front = FrontEnd.from_config(fe)
-            model = SelfAttentiveVAD(front.feature_size, get(sa, "num_layers"), get(sa, "d_model"), get(sa, "dropout"))
-            model.load_state_dict(ckpt["state_dict"])
-            ctx = ContextResolution(get(cfg, "context_resolution", "context_window_half_frames"),
-                                    get(cfg, "context_resolution", "context_window_jump_frames"))
-            predictor = cls(model.to(device).eval(), device, ctx, front_end=front, device_ingest=device_ingest, device_post=device_post,
-                            batch_chunks=batch_chunks)
-            predictor.hop_ms, predictor.window_ms = front.hop_ms, front.window_ms  # vad/predictor.py:103-104
-            return predictor
-        tr = get(fe, "transform")
-        want = {"name": "log-mel", "n_fft": 512, "hop_ms": 10, "window_ms": 25, "n_mels": 80}
-        got = {k: get(tr, k) for k in want}
-        if got != want:
-            raise NotImplementedError(f"unsupported transform {got}: the MI355X front-end implements {want} "
-                                      "(vad/acoustics/transforms/transform_factory.py:30-59 has further transforms)")
-        if get(fe, "temporal_differences", default=False) or get(fe, "stack_differences", default=False):
-            raise NotImplementedError("unsupported feature_extractor: temporal_differences / stack_differences "
-                                      "(vad/acoustics/feature_extractor.py:135-147) are not built")
-        if get(fe, "silence_remover", default=None):
-            raise NotImplementedError("unsupported feature_extractor: silence_remover (vad/acoustics/feature_extractor.py:115-116) is not built")
-        model = SelfAttentiveVAD(got["n_mels"], get(sa, "num_layers"), get(sa, "d_model"), get(sa, "dropout"))
+            feature_size, hop_ms, window_ms = front.feature_size, front.hop_ms, front.window_ms
+        else:
+            front = None   # the shipped one
+            tr = get(fe, "transform")
+            want = {"name": "log-mel", "n_fft": 512, "hop_ms": 10, "window_ms": 25, "n_mels": 80}
+            got = {k: get(tr, k) for k in want}
+            if got != want:
+                raise NotImplementedError(f"unsupported transform {got}: the MI355X front-end implements {want} "
+                                          "(vad/acoustics/transforms/transform_factory.py:30-59 has further transforms)")
+            if get(fe, "temporal_differences", default=False) or get(fe, "stack_differences", default=False):
+                raise NotImplementedError("unsupported feature_extractor: temporal_differences / stack_differences "
+                                          "(vad/acoustics/feature_extractor.py:135-147) are not built")
+            if get(fe, "silence_remover", default=None):
+                raise NotImplementedError("unsupported feature_extractor: silence_remover (vad/acoustics/feature_extractor.py:115-116) is not built")
+            feature_size, hop_ms, window_ms = got["n_mels"], got["hop_ms"], got["window_ms"]
+        model = SelfAttentiveVAD(feature_size, get(sa, "num_layers"), get(sa, "d_model"), get(sa, "dropout"))
         model.load_state_dict(ckpt["state_dict"])
         ctx = ContextResolution(get(cfg, "context_resolution", "context_window_half_frames"),
                                 get(cfg, "context_resolution", "context_window_jump_frames"))
-        predictor = cls(model.to(device).eval(), device, ctx, device_ingest=device_ingest, device_post=device_post, batch_chunks=batch_chunks)
-        predictor.hop_ms, predictor.window_ms = got["hop_ms"], got["window_ms"]  # vad/predictor.py:103-104
+        predictor = cls(model.to(device).eval(), device, ctx, front_end=front, device_ingest=device_ingest, device_post=device_post,
+                        batch_chunks=batch_chunks)
+        predictor.hop_ms, predictor.window_ms = hop_ms, window_ms  # vad/predictor.py:103-104
         return predictor
 
     def predict_from_path(self, audio_path, parameters: VADPredictParameters) -> VoiceActivity:
@@ -284,13 +281,20 @@ class VADFromScratchPredictor:
         if not (isinstance(audio, torch.Tensor) and audio.device.type == "cuda" and audio.dtype == torch.float32 and audio.dim() == 1):
             audio = np.asarray(audio, dtype=np.float32)
         adjusted, bounds = chunk_bounds(len(audio), SAMPLE_RATE, parameters.split_max_seconds)
+        def chunk_probs():
+            for start_sample, end_sample in bounds:
+                chunk = audio[start_sample:end_sample]
+                if features_fn is not None:
+                    yield self.predict_probabilities_device(features_fn(chunk))[0]
+                else:
+                    yield self.predict_audio_device(chunk)[0]   # (a replayed HIP graph for clip-sized chunks when graph=True)
+
+        return self._voice_activity(adjusted, chunk_probs(), parameters)
+
+    def _voice_activity(self, adjusted, chunk_probs, parameters: VADPredictParameters) -> VoiceActivity:
+        """a recording's VoiceActivity from the probabilities of its chunks, each post-processed as it arrives (vad/predictor.py:120-157)"""
         chunks = []
-        for start_sample, end_sample in bounds:
-            chunk = audio[start_sample:end_sample]
-            if features_fn is not None:
-                probs_dev, mean_dev = self.predict_probabilities_device(features_fn(chunk))
-            else:
-                probs_dev, mean_dev = self.predict_audio_device(chunk)   # (a replayed HIP graph for clip-sized chunks when graph=True)
+        for probs_dev in chunk_probs:
             activities, probs = self._post(probs_dev, parameters)
             chunks.append(VoiceActivity(duration=timedelta(seconds=adjusted), activities=activities,
                                         probs_sample_rate=parameters.probs_sample_rate if parameters.return_probs else None,
@@ -336,16 +340,7 @@ class VADFromScratchPredictor:
         else:
             results = self.predict_probabilities_many([features_fn(piece) if features_fn is not None else self.features(piece)
                                                        for piece in pieces])
-        out = []
-        for adjusted, indices in plan:
-            chunks = []
-            for i in indices:
-                activities, probs = self._post(results[i][0], parameters)
-                chunks.append(VoiceActivity(duration=timedelta(seconds=adjusted), activities=activities,
-                                            probs_sample_rate=parameters.probs_sample_rate if parameters.return_probs else None,
-                                            probs=probs))
-            out.append(merge_voice_activities(chunks))
-        return out
+        return [self._voice_activity(adjusted, (results[i][0] for i in indices), parameters) for adjusted, indices in plan]
 
     @torch.no_grad()
     def _predict_matrix(self, feature, table):
