@@ -24,7 +24,9 @@ Guarded arguments (alignment of the placement) and shapes:
     savad_pcm16_to_f32           pcm (2, once 8), audio (16): n = 1, 3, 5, 1001; savad_ingest_downmix: raw (2 / 4), mono (4)
     savad_resample, _span        audio / slice (4), out (4): 48 kHz, 44.1 kHz, 8 kHz; middle and last span, exact and latest cut
     savad_logmel, _span          audio / slice (16 and 4), features (16): n = 159, 160, 513, 1601 x both algorithms; head / middle / tail span
-    savad_frontend               audio (16 and 4), features (16): every config of tests/test_gpu_frontend.py, n = 1601 and the minimum
+    savad_frontend               audio (16 and 4), features (16): every config of tests/test_gpu_frontend.py, n = 1601 and the minimum;
+                                 four geometries of tests/frontend_cases.py (odd hop, window off the 4-sample grid, K range past n_fft)
+                                 at 10 frames, with and without differences ([N, 3F]), the workspace (16) guarded as well
     savad_post_frames            probs (4), boosted (4), trimmed (1): [61, 7], [1, 1]; _segments: trimmed (1), boosted (4); _sample_probs: out (8)
     savad_eval_counts            probs (4), labels (1): (N, n_labels) = (61, 61), (61, 50), (50, 61), block 0 / 64; savad_eval_sort: n = 61, 4097
 
@@ -439,6 +441,40 @@ def test_frontend(torch_cuda, c):
             ya = arena.place_input(y, align, "audio")
             out = out_f32(arena, (N.value, F.value), 16, "features")
             ws = workspace(torch, nb.value)
+            ok(lib.savad_frontend(ctypes.byref(cfg), ptr(ya), n, ptr(ws), ptr(out), st))
+            arena.check()
+            assert same_bits(out, want), (n, align)
+
+
+# tests/frontend_cases.py: an odd-hop spectrogram, an odd-hop centred case, a window off the 4-sample grid, the K range past n_fft
+FRONTEND_CASE_IDS = ["spectrogram-320-163-320", "mfcc-512-101-400-40-13", "log-mel-500-160-401-80", "spectrogram-402-160-401"]
+
+
+@pytest.mark.parametrize("deltas", [False, True], ids=["base", "deltas"])
+@pytest.mark.parametrize("case_id", FRONTEND_CASE_IDS)
+def test_frontend_cases(torch_cuda, case_id, deltas):
+    """10 frames, ending with the last frame (the spectrogram (402, 160, 401) then reads a copy) and 8 samples later (it reads the audio);
+    the workspace too lies between guards, at exactly the reported size; with deltas the [N, 3F] output is the guarded one"""
+    from tests import frontend_cases as fc
+    from voice_activity_detection_amd.features import FrontEnd
+
+    torch = torch_cuda
+    lib, st = lib_(), stream_(torch)
+    case = fc.BY_ID[case_id]
+    fe = FrontEnd(*fc.front_end_args(case, deltas))
+    cfg = fe.config()
+    for n in (fc.length_for(case, 10), fc.length_for(case, 10, 8)):
+        y = torch.from_numpy(_signal(n, n + fe.n_fft)).cuda()
+        want = fe.extract(y, "cuda")
+        N, F, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+        ok(lib.savad_frontend_shape(ctypes.byref(cfg), n, ctypes.byref(N), ctypes.byref(F)))
+        ok(lib.savad_frontend_workspace_bytes(ctypes.byref(cfg), n, ctypes.byref(nb)))
+        assert want.shape == (N.value, F.value) == (10, (3 if deltas else 1) * fc.base_size(case))
+        for align in (16, 4):
+            arena = arena_()
+            ya = arena.place_input(y, align, "audio")
+            out = out_f32(arena, (N.value, F.value), 16, "features")
+            ws = arena.place_output(nb.value, 16, torch.uint8, "workspace")
             ok(lib.savad_frontend(ctypes.byref(cfg), ptr(ya), n, ptr(ws), ptr(out), st))
             arena.check()
             assert same_bits(out, want), (n, align)
