@@ -90,12 +90,11 @@ def file_metrics_device(true_labels, probs_dev, threshold: float) -> "OrderedDic
     seg = np.empty(((n + 1) // 2, 8), dtype=np.uint8)
     need = ctypes.c_size_t()
     _lib.check(lib.savad_eval_workspace_bytes(N, W, ctypes.byref(need)))
-    with torch.cuda.device(p.device):
+    with _lib.on_device(p.device):
         labels_dev = torch.from_numpy(labels).to(p.device)
         ws = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=p.device)
-        count = lib.savad_eval_counts(ctypes.c_void_p(p.data_ptr()), N, W, ctypes.c_void_p(labels_dev.data_ptr()), len(labels), float(threshold),
-                                      BOUNDARY_HALF_WIDTH, ctypes.c_void_p(counters.ctypes.data), ctypes.c_void_p(seg.ctypes.data), len(seg),
-                                      ctypes.c_void_p(ws.data_ptr()), int(need.value), ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream))
+        count = lib.savad_eval_counts(p, N, W, labels_dev, len(labels), float(threshold), BOUNDARY_HALF_WIDTH, counters, seg, len(seg),
+                                      ws, int(need.value), torch.cuda.current_stream(p.device))
     if count < 0:
         _lib.check(int(count))
     if counters[EVAL_NAN] or counters[EVAL_BAD_LABEL]:

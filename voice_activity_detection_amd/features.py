@@ -188,17 +188,16 @@ def load_wav_mono16k(path) -> np.ndarray:
 
 
 _HOP = 160  # savad_audio_host.h: mel::HOP (frames = 1 + n // hop)
+_PCM16 = (torch.int16, np.dtype("int16"))
 
 
 def pcm16_to_f32(pcm: torch.Tensor) -> torch.Tensor:
     """int16 PCM samples on a HIP device -> float32 in [-1, 1) (sample / 32768, savad_pcm16_to_f32): the conversion soundfile does for
     the reference (vad/data_models/audio_data.py:21-24,32), on the device -- so that an upload moves 2 bytes per sample"""
-    if not (isinstance(pcm, torch.Tensor) and pcm.dtype == torch.int16 and pcm.dim() == 1 and pcm.device.type == "cuda" and pcm.is_contiguous()):
-        raise ValueError("pcm must be a contiguous 1-D int16 tensor on a HIP device")
-    with torch.cuda.device(pcm.device):
+    _lib.check_tensor(pcm, "pcm", torch.int16, 1)
+    with _lib.on_device(pcm.device):
         out = torch.empty(pcm.numel(), dtype=torch.float32, device=pcm.device)
-        _lib.check(_lib.load().savad_pcm16_to_f32(ctypes.c_void_p(pcm.data_ptr()), pcm.numel(), ctypes.c_void_p(out.data_ptr()),
-                                                 ctypes.c_void_p(torch.cuda.current_stream(pcm.device).cuda_stream)))
+        _lib.check(_lib.load().savad_pcm16_to_f32(pcm, pcm.numel(), out, torch.cuda.current_stream(pcm.device)))
     return out
 
 
@@ -221,7 +220,7 @@ def _resample_lib():
     if not _rs_window_set:
         win = kaiser_fast_window()
         assert win.shape == (_RS_WINDOW,)
-        _lib.check(lib.savad_resample_set_window(ctypes.c_void_p(win.ctypes.data)))
+        _lib.check(lib.savad_resample_set_window(win))
         _rs_window_set = True
     return lib
 
@@ -244,30 +243,23 @@ def resample_span_samples(n_samples: int, rate: int, out_first: int, out_count: 
 
 def resample_prepare(rate: int, device) -> None:
     """build and upload a source rate's tables on `device` (synchronises; the compute calls do it on first use otherwise)"""
-    with torch.cuda.device(torch.device(device)):
+    with _lib.on_device(torch.device(device)):
         _lib.check(_resample_lib().savad_resample_prepare(int(rate)))
-
-
-def _check_device_f32(audio, what="audio"):
-    if not (isinstance(audio, torch.Tensor) and audio.dtype == torch.float32 and audio.dim() == 1 and audio.device.type == "cuda"
-            and audio.is_contiguous()):
-        raise ValueError(f"{what} must be a contiguous 1-D float32 tensor on a HIP device")
 
 
 def resample_to_16k_device(audio_dev: torch.Tensor, rate: int) -> torch.Tensor:
     """float32 mono samples at `rate` Hz on a HIP device -> the 16 kHz signal, ceil(n * 16000 / rate) samples, on the device: the
     reference's librosa.resample(audio, sr, 16000, res_type="kaiser_fast") (vad/data_models/audio_data.py:27-30) with the bits of
     resampy's loop (savad_resample; include/savad.h).  A 16 kHz source is returned as it is."""
-    _check_device_f32(audio_dev)
+    _lib.check_tensor(audio_dev, "audio", torch.float32, 1)
     rate = int(rate)
     if rate == SAMPLE_RATE:
         return audio_dev
     lib = _resample_lib()
     n = audio_dev.numel()
-    with torch.cuda.device(audio_dev.device):
+    with _lib.on_device(audio_dev.device):
         out = torch.empty(resample_length(n, rate), dtype=torch.float32, device=audio_dev.device)
-        _lib.check(lib.savad_resample(ctypes.c_void_p(audio_dev.data_ptr()), n, rate, ctypes.c_void_p(out.data_ptr()),
-                                      ctypes.c_void_p(torch.cuda.current_stream(audio_dev.device).cuda_stream)))
+        _lib.check(lib.savad_resample(audio_dev, n, rate, out, torch.cuda.current_stream(audio_dev.device)))
     return out
 
 
@@ -276,17 +268,14 @@ def resample_span_device(audio_dev: torch.Tensor, audio_first: int, n_samples: i
     """Samples [out_first, out_first + out_count) of the 16 kHz signal of an n_samples-long recording, from a device slice that starts
     at input sample `audio_first` (savad_resample_span; `resample_span_samples` names the slice a span needs): the same bits as
     resample_to_16k_device(whole recording)[out_first:out_first + out_count].  `out`: where to write them."""
-    _check_device_f32(audio_dev)
+    _lib.check_tensor(audio_dev, "audio", torch.float32, 1)
     lib = _resample_lib()
-    with torch.cuda.device(audio_dev.device):
+    with _lib.on_device(audio_dev.device):
         if out is None:
             out = torch.empty(int(out_count), dtype=torch.float32, device=audio_dev.device)
-        elif out.numel() != int(out_count):
-            raise ValueError("out must hold out_count samples")
-        _check_device_f32(out, "out")
-        _lib.check(lib.savad_resample_span(ctypes.c_void_p(audio_dev.data_ptr()), int(audio_first), audio_dev.numel(), int(n_samples), int(rate),
-                                           int(out_first), int(out_count), ctypes.c_void_p(out.data_ptr()),
-                                           ctypes.c_void_p(torch.cuda.current_stream(audio_dev.device).cuda_stream)))
+        _lib.check_tensor(out, "out", torch.float32, shape=(int(out_count),))
+        _lib.check(lib.savad_resample_span(audio_dev, int(audio_first), audio_dev.numel(), int(n_samples), int(rate), int(out_first),
+                                           int(out_count), out, torch.cuda.current_stream(audio_dev.device)))
     return out
 
 
@@ -295,23 +284,18 @@ def downmix_device(raw_dev: torch.Tensor, channels: int, out: Optional[torch.Ten
     host loader (sample / 32768 for int16, then the float32 channel mean: vad/data_models/audio_data.py:26; savad_ingest_downmix).
     Limits: int16 up to 256 channels, float32 up to 7 (beyond that numpy's mean sums in another order: refused)."""
     channels = int(channels)
-    if not (isinstance(raw_dev, torch.Tensor) and raw_dev.dtype in (torch.int16, torch.float32) and raw_dev.dim() == 1
-            and raw_dev.device.type == "cuda" and raw_dev.is_contiguous()):
-        raise ValueError("raw must be a contiguous 1-D int16 or float32 tensor on a HIP device")
+    _lib.check_tensor(raw_dev, "raw", (torch.int16, torch.float32), 1)
     if channels < 1 or raw_dev.numel() % channels:
         raise ValueError(f"{raw_dev.numel()} samples are not whole frames of {channels} channels")
     if channels == 1 and raw_dev.dtype == torch.float32 and out is None:
         return raw_dev
     frames = raw_dev.numel() // channels
-    with torch.cuda.device(raw_dev.device):
+    with _lib.on_device(raw_dev.device):
         if out is None:
             out = torch.empty(frames, dtype=torch.float32, device=raw_dev.device)
-        elif out.numel() != frames:
-            raise ValueError("out must hold one sample per frame")
-        _check_device_f32(out, "out")
-        _lib.check(_lib.load().savad_ingest_downmix(ctypes.c_void_p(raw_dev.data_ptr()), 0 if raw_dev.dtype == torch.int16 else 1, channels,
-                                                    frames, ctypes.c_void_p(out.data_ptr()),
-                                                    ctypes.c_void_p(torch.cuda.current_stream(raw_dev.device).cuda_stream)))
+        _lib.check_tensor(out, "out", torch.float32, shape=(frames,))
+        _lib.check(_lib.load().savad_ingest_downmix(raw_dev, 0 if raw_dev.dtype == torch.int16 else 1, channels, frames, out,
+                                                    torch.cuda.current_stream(raw_dev.device)))
     return out
 
 
@@ -327,6 +311,21 @@ def load_audio_device(path, device="cuda") -> torch.Tensor:
     return resample_to_16k_device(downmix_device(torch.from_numpy(raw).to(dev), channels), rate)
 
 
+def _device_audio(audio, device, what: str) -> torch.Tensor:
+    """the audio argument of the front-ends -> a non-empty contiguous 1-D float32 tensor on `device`: int16 PCM goes up as it is
+    and is converted there, anything else becomes float32 on the device"""
+    dev = device if isinstance(device, torch.device) else torch.device(device)
+    if getattr(audio, "dtype", None) in _PCM16:
+        audio = pcm16_to_f32(torch.as_tensor(audio).to(dev).contiguous())
+    y = audio if (isinstance(audio, torch.Tensor) and audio.dtype == torch.float32 and audio.device == dev and audio.is_contiguous()) \
+        else torch.as_tensor(audio, dtype=torch.float32).to(dev).contiguous()
+    if y.dim() != 1 or y.numel() < 1:
+        raise ValueError("audio must be a non-empty 1-D array")
+    if y.device.type != "cuda":
+        raise _lib.SavadError(f"the {what} front-end runs only on a HIP device (no CPU fallback)")
+    return y
+
+
 def log_mel(audio, device="cuda", out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """audio: 1-D float32 samples @16 kHz (numpy or tensor; int16 PCM is uploaded as it is and converted on the device) -> device
     tensor [N, 80] float32, N = 1 + len // 160.  `out`: a contiguous float32 [N, 80] tensor on the device to write into (a clip's
@@ -334,29 +333,17 @@ def log_mel(audio, device="cuda", out: Optional[torch.Tensor] = None) -> torch.T
     (Host side kept thin on purpose: for a 10 s clip the two kernels take ~25 us, the Python around them used to
     take longer.)"""
     lib = _lib.load()
-    dev = device if isinstance(device, torch.device) else torch.device(device)
-    if getattr(audio, "dtype", None) in (torch.int16, np.dtype("int16")):
-        audio = pcm16_to_f32(torch.as_tensor(audio).to(dev).contiguous())
-    y = audio if (isinstance(audio, torch.Tensor) and audio.dtype == torch.float32 and audio.device == dev and audio.is_contiguous()) \
-        else torch.as_tensor(audio, dtype=torch.float32).to(dev).contiguous()
-    if y.dim() != 1 or y.numel() < 1:
-        raise ValueError("audio must be a non-empty 1-D array")
-    if y.device.type != "cuda":
-        raise _lib.SavadError("the log-mel front-end runs only on a HIP device (no CPU fallback)")
+    y = _device_audio(audio, device, "log-mel")
     n = y.numel()
     frames = 1 + n // _HOP
-    idx = y.device.index if y.device.index is not None else torch.cuda.current_device()
-    if idx != torch.cuda.current_device():
-        with torch.cuda.device(idx):
-            return log_mel(y, y.device, out)
-    buf = torch.empty(lib.savad_logmel_workspace_bytes(n) // 4, dtype=torch.float32, device=y.device)
-    if out is None:
-        out = torch.empty((frames, 80), dtype=torch.float32, device=y.device)
-    elif tuple(out.shape) != (frames, 80) or out.dtype != torch.float32 or out.device != y.device or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous float32 [{frames}, 80] tensor on {y.device}")
-    _lib.check(lib.savad_logmel(ctypes.c_void_p(y.data_ptr()), n, ctypes.c_void_p(buf.data_ptr()),
-                                ctypes.c_void_p(out.data_ptr()),
-                                ctypes.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)))
+    with _lib.on_device(y.device):
+        buf = torch.empty(lib.savad_logmel_workspace_bytes(n) // 4, dtype=torch.float32, device=y.device)
+        if out is None:
+            out = torch.empty((frames, 80), dtype=torch.float32, device=y.device)
+        else:
+            _lib.check_tensor(out, "out", torch.float32, shape=(frames, 80), device=y.device)
+        # (raw addresses, as in the model's forward: made or checked above, and a typed argument costs ~1 us each, a fifth of this call)
+        _lib.check(lib.savad_logmel(y.data_ptr(), n, buf.data_ptr(), out.data_ptr(), torch.cuda.current_stream(y.device)))
     return out
 
 
@@ -365,16 +352,12 @@ def log_mel_span(audio, audio_first: int, n_samples: int, frame_first: int, fram
     slice `audio` that starts at sample `audio_first` (savad_logmel_span; `span_samples` names the slice a frame span
     needs).  What one rank of a sharded run computes: the same bits as the rows of log_mel(whole signal)."""
     lib = _lib.load()
-    if not (isinstance(audio, torch.Tensor) and audio.dtype == torch.float32 and audio.dim() == 1 and audio.device.type == "cuda"
-            and audio.is_contiguous()):
-        raise ValueError("audio must be a contiguous 1-D float32 tensor on a HIP device")
-    with torch.cuda.device(audio.device):
+    _lib.check_tensor(audio, "audio", torch.float32, 1)
+    with _lib.on_device(audio.device):
         buf = torch.empty(lib.savad_logmel_span_workspace_bytes(int(frame_count)) // 4, dtype=torch.float32, device=audio.device)
         out = torch.empty((int(frame_count), 80), dtype=torch.float32, device=audio.device)
-        _lib.check(lib.savad_logmel_span(ctypes.c_void_p(audio.data_ptr()), int(audio_first), audio.numel(), int(n_samples),
-                                         int(frame_first), int(frame_count), ctypes.c_void_p(buf.data_ptr()),
-                                         ctypes.c_void_p(out.data_ptr()),
-                                         ctypes.c_void_p(torch.cuda.current_stream(audio.device).cuda_stream)))
+        _lib.check(lib.savad_logmel_span(audio, int(audio_first), audio.numel(), int(n_samples), int(frame_first), int(frame_count),
+                                         buf, out, torch.cuda.current_stream(audio.device)))
     return out
 
 
@@ -472,16 +455,13 @@ class FrontEnd:
     def frames(self, n_samples: int) -> int:
         """rows of extract() for n_samples samples (raises outside the limits)"""
         N, F = ctypes.c_int(), ctypes.c_int()
-        cfg = self.config()
-        _lib.check(_lib.load().savad_frontend_shape(ctypes.byref(cfg), int(n_samples), ctypes.byref(N), ctypes.byref(F)))
+        _lib.check(_lib.load().savad_frontend_shape(self.config(), int(n_samples), ctypes.byref(N), ctypes.byref(F)))
         return N.value
 
     def prepare(self, device) -> None:
         """build and upload this config's tables on `device` (synchronises: the step before a graph capture)"""
-        dev = torch.device(device)
-        with torch.cuda.device(dev):
-            cfg = self.config()
-            _lib.check(_lib.load().savad_frontend_prepare(ctypes.byref(cfg)))
+        with _lib.on_device(torch.device(device)):
+            _lib.check(_lib.load().savad_frontend_prepare(self.config()))
 
     def extract(self, audio, device="cuda", generic: bool = False) -> torch.Tensor:
         """audio: 1-D float32 samples @16 kHz (numpy or tensor; int16 PCM is uploaded as it is and converted on the device) ->
@@ -490,26 +470,16 @@ class FrontEnd:
         if self.is_shipped and not generic:
             return log_mel(audio, device)
         lib = _lib.load()
-        dev = device if isinstance(device, torch.device) else torch.device(device)
-        if getattr(audio, "dtype", None) in (torch.int16, np.dtype("int16")):
-            audio = pcm16_to_f32(torch.as_tensor(audio).to(dev).contiguous())
-        y = audio if (isinstance(audio, torch.Tensor) and audio.dtype == torch.float32 and audio.device == dev and audio.dim() == 1
-                      and audio.is_contiguous()) else torch.as_tensor(audio, dtype=torch.float32).to(dev).contiguous()
-        if y.dim() != 1 or y.numel() < 1:
-            raise ValueError("audio must be a non-empty 1-D array")
-        if y.device.type != "cuda":
-            raise _lib.SavadError("the feature front-end runs only on a HIP device (no CPU fallback)")
-        with torch.cuda.device(y.device):
+        y = _device_audio(audio, device, "feature")
+        with _lib.on_device(y.device):
             cfg = self.config()
             n = y.numel()
             N, F, ws = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
-            _lib.check(lib.savad_frontend_shape(ctypes.byref(cfg), n, ctypes.byref(N), ctypes.byref(F)))
-            _lib.check(lib.savad_frontend_workspace_bytes(ctypes.byref(cfg), n, ctypes.byref(ws)))
+            _lib.check(lib.savad_frontend_shape(cfg, n, ctypes.byref(N), ctypes.byref(F)))
+            _lib.check(lib.savad_frontend_workspace_bytes(cfg, n, ctypes.byref(ws)))
             buf = torch.empty(ws.value // 4, dtype=torch.float32, device=y.device)
             out = torch.empty((N.value, F.value), dtype=torch.float32, device=y.device)
-            _lib.check(lib.savad_frontend(ctypes.byref(cfg), ctypes.c_void_p(y.data_ptr()), n, ctypes.c_void_p(buf.data_ptr()),
-                                          ctypes.c_void_p(out.data_ptr()),
-                                          ctypes.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)))
+            _lib.check(lib.savad_frontend(cfg, y, n, buf, out, torch.cuda.current_stream(y.device)))
         return out
 
 

@@ -134,13 +134,12 @@ class LiveVAD:
         lib = self._lib = _lib.load()
         self._cfg = _lib.savad_live_config(self.streams, self.max_push_samples, self.half, self.jump, self.chunk_size)
         nbytes = ctypes.c_size_t()
-        _lib.check(lib.savad_live_state_bytes(ctypes.byref(self._cfg), ctypes.byref(nbytes)))
+        _lib.check(lib.savad_live_state_bytes(self._cfg, ctypes.byref(nbytes)))
         self.W = context_window_frames(self.half, self.jump)   # (refuses a geometry the reference cannot run)
         self._slots = (_lib.savad_live_slot * self.streams)()
-        with torch.cuda.device(self.device):
+        with _lib.on_device(self.device):
             self._state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)   # (the allocator aligns it far beyond 16 bytes)
-            self._state_ptr = self._state.data_ptr()
-            _lib.check(lib.savad_live_table_bytes(ctypes.byref(self._cfg), self.streams, ctypes.byref(nbytes)))
+            _lib.check(lib.savad_live_table_bytes(self._cfg, self.streams, ctypes.byref(nbytes)))
             # staging: [the tick's tables | every host chunk, 16-byte aligned]; two pinned buffers, so that filling one never waits for
             # the upload of the other
             self._stage_bytes = nbytes.value + self.streams * ((4 * self.max_push_samples + 15) & ~15)
@@ -149,7 +148,7 @@ class LiveVAD:
             self._stage_dev = torch.empty(self._stage_bytes, dtype=torch.uint8, device=self.device)
             if post is not None:
                 self._post_cfg = _lib.savad_live_post_config(self.W, float(post.threshold), *frames)
-                _lib.check(lib.savad_live_post_state_bytes(ctypes.byref(self._post_cfg), self.streams, ctypes.byref(nbytes)))
+                _lib.check(lib.savad_live_post_state_bytes(self._post_cfg, self.streams, ctypes.byref(nbytes)))
                 self._post_state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
                 self._post_ws = torch.empty(0, dtype=torch.uint8, device=self.device)
         self._turn = 0
@@ -162,7 +161,7 @@ class LiveVAD:
         """a free slot, opened"""
         for slot in range(self.streams):
             if not self._slots[slot].open:
-                _lib.check(self._lib.savad_live_open(ctypes.byref(self._cfg), self._slots, slot))
+                _lib.check(self._lib.savad_live_open(self._cfg, self._slots, slot))
                 return slot
         raise _lib.SavadError(f"all {self.streams} slots are open")
 
@@ -251,7 +250,7 @@ class LiveVAD:
         if n > self.streams:
             raise _lib.SavadError(f"{n} slots in one tick, the state has {self.streams}")
         nbytes = ctypes.c_size_t()
-        _lib.check(lib.savad_live_table_bytes(ctypes.byref(cfg), n, ctypes.byref(nbytes)))
+        _lib.check(lib.savad_live_table_bytes(cfg, n, ctypes.byref(nbytes)))
         table_bytes = nbytes.value
         turn = self._turn
         if self._uploaded[turn] is not None:
@@ -290,19 +289,16 @@ class LiveVAD:
                     ptr = dev_base + at
                     at += (size + 15) & ~15
             pushes[i] = _lib.savad_live_push(slot, count, dtype, int(slot in finish), ptr if count else None)
-        table_host = pinned.data_ptr()
-        counts = _lib.savad_live_counts()
-        rows = np.zeros((n, 2), dtype=np.int64)
-        _lib.check(lib.savad_live_plan(ctypes.byref(cfg), self._slots, pushes, n, ctypes.c_void_p(self._state_ptr), ctypes.c_void_p(table_host),
-                                       table_bytes, ctypes.byref(counts), ctypes.c_void_p(rows.ctypes.data)))
-        with torch.cuda.device(dev):
+        counts, rows = _lib.savad_live_counts(), np.zeros((n, 2), dtype=np.int64)
+        with _lib.on_device(dev):
+            _lib.check(lib.savad_live_plan(cfg, self._slots, pushes, n, self._state, pinned, table_bytes, ctypes.byref(counts), rows))
             model = self.model
             model.eval()
             model._prepare_call(dev)
             key = (n, model._pushed_knobs)
             ws_bytes = self._ws_bytes.get(key)
             if ws_bytes is None:
-                _lib.check(lib.savad_live_workspace_bytes(model._handle, ctypes.byref(cfg), n, ctypes.byref(nbytes)))
+                _lib.check(lib.savad_live_workspace_bytes(model._handle, cfg, n, ctypes.byref(nbytes)))
                 ws_bytes = self._ws_bytes[key] = nbytes.value
             ws = model._workspace_for(ws_bytes, dev)
             self._stage_dev[:at].copy_(pinned[:at], non_blocking=True)   # the one upload of the tick
@@ -313,23 +309,17 @@ class LiveVAD:
             self._turn = turn ^ 1
             probs = torch.empty((counts.rows, self.W), dtype=torch.float32, device=dev)
             mean = torch.empty((counts.rows,), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.savad_live_step(model._handle, ctypes.byref(cfg), self._slots, ctypes.c_void_p(table_host), ctypes.c_void_p(dev_base),
-                                           ctypes.c_void_p(probs.data_ptr()), ctypes.c_void_p(mean.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                                           ws.numel(), ctypes.c_void_p(stream)))
+            stream, stage = torch.cuda.current_stream(dev), self._stage_dev
+            _lib.check(lib.savad_live_step(model._handle, cfg, self._slots, pinned, stage, probs, mean, ws, ws.numel(), stream))
             if self.post is not None:
-                at = ctypes.c_size_t()
-                _lib.check(lib.savad_live_post_event_bytes(ctypes.byref(cfg), ctypes.byref(self._post_cfg), ctypes.c_void_p(table_host),
-                                                           ctypes.byref(nbytes), ctypes.byref(at)))
+                post, at = self._post_cfg, ctypes.c_size_t()
+                _lib.check(lib.savad_live_post_event_bytes(cfg, post, pinned, ctypes.byref(nbytes), ctypes.byref(at)))
                 events = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-                _lib.check(lib.savad_live_post_workspace_bytes(ctypes.byref(cfg), ctypes.byref(self._post_cfg), ctypes.c_void_p(table_host),
-                                                               ctypes.byref(nbytes)))
+                _lib.check(lib.savad_live_post_workspace_bytes(cfg, post, pinned, ctypes.byref(nbytes)))
                 if self._post_ws.numel() < nbytes.value:
                     self._post_ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-                _lib.check(lib.savad_live_post(ctypes.byref(cfg), ctypes.byref(self._post_cfg), ctypes.c_void_p(table_host), ctypes.c_void_p(dev_base),
-                                               ctypes.c_void_p(probs.data_ptr()), ctypes.c_void_p(self._post_state.data_ptr()),
-                                               ctypes.c_void_p(events.data_ptr()), events.numel(), ctypes.c_void_p(self._post_ws.data_ptr()),
-                                               self._post_ws.numel(), ctypes.c_void_p(stream)))
+                _lib.check(lib.savad_live_post(cfg, post, pinned, stage, probs, self._post_state, events, events.numel(),
+                                               self._post_ws, self._post_ws.numel(), stream))
         del keep
         out, first_out = {}, 0
         for i, slot in enumerate(order):

@@ -107,10 +107,9 @@ class SelfAttentiveVAD(nn.Module):
             return
         self._release()
         lib = _lib.load()
-        cfg = _lib.savad_config(self.feature_size, self.num_layers, self.d_model)
         h = ctypes.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(lib.savad_create(ctypes.byref(cfg), ctypes.byref(h)))
+        with _lib.on_device(device):
+            _lib.check(lib.savad_create(_lib.savad_config(self.feature_size, self.num_layers, self.d_model), ctypes.byref(h)))
         self._handle, self._handle_device = h, device
         self._synced_versions = None
         self._pushed_knobs = None
@@ -231,20 +230,20 @@ class SelfAttentiveVAD(nn.Module):
         if not force and versions == self._synced_versions:
             return
         lib = _lib.load()
-        stream = torch.cuda.current_stream(self._handle_device).cuda_stream
-        for key, p in self.state_dict(keep_vars=True).items():
-            t = p.detach()
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                t = t.to(torch.float32).contiguous()
-            _lib.check(lib.savad_set_param(self._handle, key.encode(), ctypes.c_void_p(t.data_ptr()), t.numel(),
-                                           ctypes.c_void_p(stream)))
-            if t.device.type != "cuda":
-                torch.cuda.current_stream(self._handle_device).synchronize()  # host source must outlive the copy
+        with _lib.on_device(self._handle_device):   # (a forced re-push may come from outside a forward)
+            stream = torch.cuda.current_stream(self._handle_device)
+            for key, p in self.state_dict(keep_vars=True).items():
+                t = p.detach()
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    t = t.to(torch.float32).contiguous()
+                _lib.check(lib.savad_set_param(self._handle, key.encode(), t, t.numel(), stream))
+                if t.device.type != "cuda":
+                    stream.synchronize()  # host source must outlive the copy
         self._synced_versions = versions
 
     # ---- forward ------------------------------------------------------------------------------
     def _prepare_call(self, device: torch.device):
-        """Shared entry checks of forward / predict_windows; call inside `with torch.cuda.device(device)`."""
+        """Shared entry checks of forward / predict_windows; call inside `with _lib.on_device(device)`."""
         if device.type != "cuda":
             raise _lib.SavadError(
                 "SelfAttentiveVAD (MI355X build) runs only on a HIP device tensor; there is no CPU fallback. "
@@ -310,22 +309,18 @@ class SelfAttentiveVAD(nn.Module):
         B, T, _ = x.shape
         if out is None:
             out = torch.empty((B, T, 2), dtype=torch.float32, device=device)
-        elif (tuple(out.shape) != (B, T, 2) or out.dtype != torch.float32 or out.device != device or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous float32 [{B}, {T}, 2] tensor on {device}")
+        else:
+            _lib.check_tensor(out, "out", torch.float32, shape=(B, T, 2), device=device)
         if B == 0 or T == 0:
             return out
-        if torch.cuda.current_device() == device.index:   # (the context manager costs ~10 us; it is only needed to switch devices)
+        with _lib.on_device(device):
             self._launch_forward(x, x_dtype, B, T, out, device)
-        else:
-            with torch.cuda.device(device):
-                self._launch_forward(x, x_dtype, B, T, out, device)
         return out
 
     def _launch_forward(self, x: Tensor, x_dtype: int, B: int, T: int, out: Tensor, device: torch.device) -> None:
         lib = self._prepare_call(device)
         ws = self._workspace_for(self._workspace_bytes(lib, B, T), device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        x_ptr, out_ptr, tmp = x.data_ptr(), out.data_ptr(), None
+        x_ptr, out_ptr, tmp = x.data_ptr(), out.data_ptr(), None   # (raw addresses: the alignment test needs them anyway)
         if (x_ptr | out_ptr) & 15:
             # the 16-byte alignment of x and out is the C ABI's rule (include/savad.h), not the module's: a contiguous view that starts
             # off a 16-byte boundary (batch[1:] of 7 x 13 MFCC windows, a slice of a larger result) is cloned / computed into a temporary
@@ -335,9 +330,7 @@ class SelfAttentiveVAD(nn.Module):
             if out_ptr & 15:
                 tmp = torch.empty_like(out)
                 out_ptr = tmp.data_ptr()
-        _lib.check(lib.savad_forward_ex(self._handle, ctypes.c_void_p(x_ptr), x_dtype, B, T,
-                                        ctypes.c_void_p(out_ptr), ctypes.c_void_p(ws.data_ptr()),
-                                        ws.numel(), ctypes.c_void_p(stream)))
+        _lib.check(lib.savad_forward_ex(self._handle, x_ptr, x_dtype, B, T, out_ptr, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(device)))
         if tmp is not None:
             out.copy_(tmp)
 
@@ -350,15 +343,14 @@ class SelfAttentiveVAD(nn.Module):
         device = feature.device
         if device.type != "cuda":
             self._prepare_call(device)  # raises: no CPU fallback
-        if feature.dim() != 2 or feature.shape[1] != self.feature_size or feature.dtype != torch.float32 or not feature.is_contiguous():
-            raise ValueError(f"feature must be a contiguous float32 [N, {self.feature_size}] tensor, got {tuple(feature.shape)} {feature.dtype}")
+        _lib.check_tensor(feature, "feature", torch.float32, shape=(None, self.feature_size))
         N, F = feature.shape
         if count < 1 or first < 0 or hop < 1 or T < 1 or hop * (first + count - 1) + T > N:
             raise ValueError(f"windows [{first}, {first + count}) of {T} frames every {hop} do not lie inside {N} frames")
         if out is None:
             out = torch.empty((count, T, 2), dtype=torch.float32, device=device)
-        elif tuple(out.shape) != (count, T, 2) or out.dtype != torch.float32 or out.device != device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 [{count}, {T}, 2] tensor on {device}")
+        else:
+            _lib.check_tensor(out, "out", torch.float32, shape=(count, T, 2), device=device)
         if feature.data_ptr() % 16:   # (the in-place reads and savad_gather_strided move 16-byte pieces: a misaligned view is cloned)
             feature = feature.clone()
         if T <= 32 or F % 16 or self.d_model != 128:
@@ -368,20 +360,16 @@ class SelfAttentiveVAD(nn.Module):
                 win = feature.as_strided((count, T, F), (hop * F, F, 1), first * hop * F).contiguous()
             else:
                 win = torch.empty((count, T, F), dtype=torch.float32, device=device)
-                with torch.cuda.device(device):
+                with _lib.on_device(device):
                     lib = self._prepare_call(device)
-                    stream = torch.cuda.current_stream(device).cuda_stream
-                    _lib.check(lib.savad_gather_strided(ctypes.c_void_p(feature.data_ptr()), N, F, T, hop, first, count,
-                                                        ctypes.c_void_p(win.data_ptr()), ctypes.c_void_p(stream)))
+                    _lib.check(lib.savad_gather_strided(feature, N, F, T, hop, first, count, win, torch.cuda.current_stream(device)))
             return self(features=win, out=out)   # (forward takes an `out` off a 16-byte boundary: odd T x odd window count)
         dst = out if out.data_ptr() % 16 == 0 else torch.empty_like(out)
-        with torch.cuda.device(device):
+        with _lib.on_device(device):
             lib = self._prepare_call(device)
             ws = self._workspace_for(self._workspace_bytes(lib, count, T), device)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            x = feature.data_ptr() + 4 * first * hop * F
-            _lib.check(lib.savad_forward_strided(self._handle, ctypes.c_void_p(x), 0, count, T, hop * F, ctypes.c_void_p(dst.data_ptr()),
-                                                 ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream)))
+            x = feature.data_ptr() + 4 * first * hop * F   # (an offset address: the raw form of the argument)
+            _lib.check(lib.savad_forward_strided(self._handle, x, 0, count, T, hop * F, dst, ws, ws.numel(), torch.cuda.current_stream(device)))
         if dst is not out:
             out.copy_(dst)
         return out
@@ -427,21 +415,18 @@ class SelfAttentiveVAD(nn.Module):
         mean = torch.empty((N,), dtype=torch.float32, device=device)
         if N == 0:
             return probs, mean
-        with torch.cuda.device(device):
+        with _lib.on_device(device):
             self._prepare_call(device)
             if table is None:
                 size, run, clips_host, clips = lib.savad_predict_workspace_bytes, lib.savad_predict_probabilities, (N,), (N,)
             else:
                 table_dev = torch.from_numpy(table).to(device)   # (the library uploads nothing: the device copy is the caller's)
-                host = ctypes.c_void_p(table.ctypes.data)
                 size, run = lib.savad_predict_batch_workspace_bytes, lib.savad_predict_probabilities_batch
-                clips_host, clips = (host, table.size - 1), (host, ctypes.c_void_p(table_dev.data_ptr()), table.size - 1)
+                clips_host, clips = (table, table.size - 1), (table, table_dev, table.size - 1)
             nbytes = ctypes.c_size_t()
             _lib.check(size(self._handle, *clips_host, *geometry, ctypes.byref(nbytes)))
             ws = self._workspace_for(nbytes.value, device)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(run(self._handle, ctypes.c_void_p(feat.data_ptr()), *clips, *geometry, ctypes.c_void_p(probs.data_ptr()),
-                           ctypes.c_void_p(mean.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(stream)))
+            _lib.check(run(self._handle, feat, *clips, *geometry, probs, mean, ws, ws.numel(), torch.cuda.current_stream(device)))
         return probs, mean
 
     def reserve(self, max_frames: int, device=None, max_batch: int = 0):
@@ -453,10 +438,9 @@ class SelfAttentiveVAD(nn.Module):
         device = torch.device(device) if device is not None else self.classifier.weight.device
         if device.type == "cuda" and device.index is None:  # "cuda" -> the indexed device tensors report
             device = torch.device("cuda", torch.cuda.current_device())
-        with torch.cuda.device(device):
+        with _lib.on_device(device):
             lib = self._prepare_call(device)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(lib.savad_reserve(self._handle, int(max_frames), ctypes.c_void_p(stream)))
+            _lib.check(lib.savad_reserve(self._handle, int(max_frames), torch.cuda.current_stream(device)))
             if max_batch > 0 and max_frames > 0:
                 nbytes = ctypes.c_size_t()
                 _lib.check(lib.savad_workspace_bytes(self._handle, int(max_batch), int(max_frames), ctypes.byref(nbytes)))
@@ -469,15 +453,14 @@ class SelfAttentiveVAD(nn.Module):
         if self._handle is None:
             return 0
         n = ctypes.c_ulonglong()
-        with torch.cuda.device(self._handle_device):
-            stream = torch.cuda.current_stream(self._handle_device).cuda_stream
-            _lib.check(_lib.load().savad_residual_saturations(self._handle, ctypes.byref(n), ctypes.c_void_p(stream)))
+        with _lib.on_device(self._handle_device):
+            _lib.check(_lib.load().savad_residual_saturations(self._handle, ctypes.byref(n), torch.cuda.current_stream(self._handle_device)))
         return int(n.value)
 
     # ---- profiling hooks used by bench.py -------------------------------------------------------
     def set_profiling(self, capacity: int, skip: int = 0):
         """record the kernels of the next `capacity` forwards, after `skip` un-recorded ones (clocks settle)"""
-        with torch.cuda.device(self._handle_device):
+        with _lib.on_device(self._handle_device):
             _lib.check(_lib.load().savad_set_profiling(self._handle, int(capacity)))
             if skip:
                 _lib.check(_lib.load().savad_profiling_skip(self._handle, int(skip)))

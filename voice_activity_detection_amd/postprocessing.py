@@ -8,12 +8,9 @@ import ctypes
 from datetime import timedelta
 
 import numpy as np
+import torch
 
 from . import _lib
-
-
-def _ptr(a: np.ndarray):
-    return ctypes.c_void_p(a.ctypes.data)
 
 
 def trim_voice_activity(predictions, min_vally=20, min_hill=20, hang_before=10, hang_over=10):
@@ -21,8 +18,7 @@ def trim_voice_activity(predictions, min_vally=20, min_hill=20, hang_before=10, 
     p = np.ascontiguousarray(predictions)
     src = (p != 0).astype(np.uint8)
     out = np.empty_like(src)
-    _lib.check(_lib.load().savad_trim_voice_activity(_ptr(src), len(src), int(min_vally), int(min_hill),
-                                                     int(hang_before), int(hang_over), _ptr(out)))
+    _lib.check(_lib.load().savad_trim_voice_activity(src, len(src), int(min_vally), int(min_hill), int(hang_before), int(hang_over), out))
     return out.astype(p.dtype)
 
 
@@ -30,11 +26,11 @@ def convert_frames_to_samples(frames, sample_rate=16000, hop_ms=10, window_ms=10
     """vad/postprocessing/convert.py:6-24 (float64 result, like numpy.zeros)."""
     f = np.ascontiguousarray(frames, dtype=np.float64)
     lib = _lib.load()
-    n = lib.savad_frames_to_samples(_ptr(f), len(f), int(sample_rate), float(hop_ms), float(window_ms), None)
+    n = lib.savad_frames_to_samples(f, len(f), int(sample_rate), float(hop_ms), float(window_ms), None)
     if n < 0:
         _lib.check(int(n))
     out = np.empty(int(n), dtype=np.float64)
-    lib.savad_frames_to_samples(_ptr(f), len(f), int(sample_rate), float(hop_ms), float(window_ms), _ptr(out))
+    lib.savad_frames_to_samples(f, len(f), int(sample_rate), float(hop_ms), float(window_ms), out)
     return out
 
 
@@ -42,13 +38,13 @@ def segment_indices(samples):
     """(start, end) SAMPLE indices of convert_samples_to_segments' segments."""
     s = np.ascontiguousarray(samples, dtype=np.float64)
     lib = _lib.load()
-    cnt = lib.savad_samples_to_segments(_ptr(s), len(s), None, None, 0)
+    cnt = lib.savad_samples_to_segments(s, len(s), None, None, 0)
     if cnt < 0:
         _lib.check(cnt)
     starts = np.empty(cnt, dtype=np.int64)
     ends = np.empty(cnt, dtype=np.int64)
     if cnt:
-        lib.savad_samples_to_segments(_ptr(s), len(s), _ptr(starts), _ptr(ends), cnt)
+        lib.savad_samples_to_segments(s, len(s), starts, ends, cnt)
     return starts, ends
 
 
@@ -63,8 +59,7 @@ def optimal_split_voice_activity(sample_predictions, sample_probs, max_length_se
     pred = np.ascontiguousarray(sample_predictions, dtype=np.float64)
     probs = np.ascontiguousarray(sample_probs, dtype=np.float64)
     out = np.empty_like(pred)
-    _lib.check(_lib.load().savad_optimal_split(_ptr(pred), _ptr(probs), len(pred), int(max_length_seconds * sample_rate),
-                                               _ptr(out)))
+    _lib.check(_lib.load().savad_optimal_split(pred, probs, len(pred), int(max_length_seconds * sample_rate), out))
     return out
 
 
@@ -78,36 +73,24 @@ def device_post_supported(W, sample_rate=16000, hop_ms=10, window_ms=25, n_frame
 
 
 def _post_workspace(n_frames, W, sample_rate, hop_ms, window_ms, device):
-    import torch
-
     need = ctypes.c_size_t()
     _lib.check(_lib.load().savad_post_workspace_bytes(int(n_frames), int(W), int(sample_rate), float(hop_ms), float(window_ms), ctypes.byref(need)))
     return torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=device), int(need.value)
 
 
-def _stream(device):
-    import torch
-
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def post_frames_device(probs, threshold=0.5, min_vally=0, min_hill=0, hang_before=0, hang_over=0):
     """probs [N, W] float32 on the device -> (boosted [N] float32, trimmed [N] uint8), both on the device: numpy's
     probs.mean(axis=1), and trim_voice_activity(boosted > threshold, ...).  Asynchronous on the current stream."""
-    import torch
-
-    if probs.device.type != "cuda" or probs.dtype != torch.float32 or probs.dim() != 2:
-        raise ValueError("probs must be a float32 [N, W] tensor on the device")
+    _lib.check_tensor(probs, "probs", torch.float32, 2, contiguous=False)
     probs = probs.contiguous()
     N, W = probs.shape
-    with torch.cuda.device(probs.device):
+    with _lib.on_device(probs.device):
         boosted = torch.empty((N,), dtype=torch.float32, device=probs.device)
         trimmed = torch.empty((N,), dtype=torch.uint8, device=probs.device)
         # (the frame stage's share of the workspace does not depend on the geometry: asked for at one sample per frame, the smallest)
         ws, ws_bytes = _post_workspace(N, W, 1000, 1, 1, probs.device)
-        _lib.check(_lib.load().savad_post_frames(ctypes.c_void_p(probs.data_ptr()), N, W, float(threshold), int(min_vally), int(min_hill),
-                                                 int(hang_before), int(hang_over), ctypes.c_void_p(boosted.data_ptr()),
-                                                 ctypes.c_void_p(trimmed.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws_bytes, _stream(probs.device)))
+        _lib.check(_lib.load().savad_post_frames(probs, N, W, float(threshold), int(min_vally), int(min_hill), int(hang_before),
+                                                 int(hang_over), boosted, trimmed, ws, ws_bytes, torch.cuda.current_stream(probs.device)))
     return boosted, trimmed
 
 
@@ -117,26 +100,21 @@ def segments_device(trimmed, boosted=None, sample_rate=16000, hop_ms=10, window_
     device) after optimal_split_voice_activity against convert_frames_to_samples(boosted, ...).  Synchronises the current
     stream (with a split: once more per range query, on the order of length / max_length per long segment).
     `cap`: room for that many segments on the first call (default: one per frame); a second call fetches a larger count."""
-    import torch
-
-    if trimmed.device.type != "cuda" or trimmed.dtype != torch.uint8 or trimmed.dim() != 1:
-        raise ValueError("trimmed must be a uint8 [N] tensor on the device")
+    _lib.check_tensor(trimmed, "trimmed", torch.uint8, 1, contiguous=False)
     trimmed = trimmed.contiguous()
     N = int(trimmed.shape[0])
     max_samples = int(max_length_seconds * sample_rate) if max_length_seconds else 0
     if max_samples:
-        if boosted is None or boosted.device != trimmed.device or boosted.dtype != torch.float32 or tuple(boosted.shape) != (N,):
-            raise ValueError("a split needs boosted: float32 [N] on the device of trimmed")
+        _lib.check_tensor(boosted, "boosted (a split needs it)", torch.float32, shape=(N,), device=trimmed.device, contiguous=False)
         boosted = boosted.contiguous()
     lib = _lib.load()
-    with torch.cuda.device(trimmed.device):
+    with _lib.on_device(trimmed.device):
         ws, ws_bytes = _post_workspace(N, 1, sample_rate, hop_ms, window_ms, trimmed.device)
         cap = N + 2 if cap is None else int(cap)
         while True:
             starts, ends = np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.int64)
-            cnt = lib.savad_post_segments(ctypes.c_void_p(trimmed.data_ptr()), ctypes.c_void_p(boosted.data_ptr()) if max_samples else None, N,
-                                          int(sample_rate), float(hop_ms), float(window_ms), max_samples, _ptr(starts), _ptr(ends), cap,
-                                          ctypes.c_void_p(ws.data_ptr()), ws_bytes, _stream(trimmed.device))
+            cnt = lib.savad_post_segments(trimmed, boosted if max_samples else None, N, int(sample_rate), float(hop_ms), float(window_ms),
+                                          max_samples, starts, ends, cap, ws, ws_bytes, torch.cuda.current_stream(trimmed.device))
             if cnt < 0:
                 _lib.check(cnt)
             if cnt <= cap:
@@ -146,17 +124,13 @@ def segments_device(trimmed, boosted=None, sample_rate=16000, hop_ms=10, window_
 
 def sample_probs_device(boosted, sample_rate=16000, hop_ms=10, window_ms=25):
     """boosted [N] float32 on the device -> convert_frames_to_samples(boosted, ...) as a float64 tensor on the device.  Asynchronous."""
-    import torch
-
-    if boosted.device.type != "cuda" or boosted.dtype != torch.float32 or boosted.dim() != 1:
-        raise ValueError("boosted must be a float32 [N] tensor on the device")
+    _lib.check_tensor(boosted, "boosted", torch.float32, 1, contiguous=False)
     boosted = boosted.contiguous()
-    lib = _lib.load()
     N = int(boosted.shape[0])
     # savad_frames_to_samples' count, int((n-1)*hop + window), in the same double arithmetic
     num = max(int((N - 1) * (int(sample_rate) * float(hop_ms) / 1000) + int(sample_rate) * float(window_ms) / 1000), 0)
-    with torch.cuda.device(boosted.device):
+    with _lib.on_device(boosted.device):
         out = torch.empty((int(num),), dtype=torch.float64, device=boosted.device)
-        _lib.check(lib.savad_post_sample_probs(ctypes.c_void_p(boosted.data_ptr()), N, int(sample_rate), float(hop_ms), float(window_ms),
-                                               ctypes.c_void_p(out.data_ptr()), _stream(boosted.device)))
+        _lib.check(_lib.load().savad_post_sample_probs(boosted, N, int(sample_rate), float(hop_ms), float(window_ms), out,
+                                                       torch.cuda.current_stream(boosted.device)))
     return out

@@ -475,7 +475,7 @@ class VADFromScratchPredictor:
             return self.predict_probabilities_device(self.features(audio))
         model = self.model
         dev = _indexed(self.device)
-        with torch.cuda.device(dev):
+        with _lib.on_device(dev):
             model._prepare_call(dev)   # weights pushed, knobs set: the walk over the parameters' versions costs ~8 us
             key = (n, dev.index, model._pushed_knobs, self.context_window_half_frames, self.context_window_jump_frames, self.chunk_size,
                    self.front_end)
@@ -561,7 +561,7 @@ class VADFromScratchPredictor:
         N = 1 + n // 160
         self.model.eval()
         dev = _indexed(self.device)
-        with torch.cuda.device(dev):
+        with _lib.on_device(dev):
             if rate != SAMPLE_RATE:
                 resample_prepare(rate, dev)        # (the table upload synchronises: before the first copy is in flight)
             feed = HostFeed(src, dev, unit=channels, stream_owner=self)
@@ -628,25 +628,21 @@ class VADFromScratchPredictor:
         half, jump, W = self.context_window_half_frames, self.context_window_jump_frames, self.context_window_frames
         data_length = N - 2 * half  # vad/predictor.py:169
         self.model.eval()
-        with torch.cuda.device(self.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with _lib.on_device(self.device):
+            stream = torch.cuda.current_stream(self.device)
             n_items = max(data_length, 0)
             logp = torch.empty((n_items, W, 2), dtype=torch.float32, device=self.device)
             pos = torch.empty((n_items, W), dtype=torch.int64, device=self.device)
             for first in range(0, n_items, self.chunk_size):
                 count = min(self.chunk_size, n_items - first)
                 win = torch.empty((count, W, F), dtype=torch.float32, device=self.device)
-                _lib.check(lib.savad_gather_windows(ctypes.c_void_p(feat.data_ptr()), N, F, half, jump, first, count,
-                                                    ctypes.c_void_p(win.data_ptr()),
-                                                    ctypes.c_void_p(pos[first:first + count].data_ptr()), stream))
+                _lib.check(lib.savad_gather_windows(feat, N, F, half, jump, first, count, win, pos[first:first + count], stream))
                 self.model(features=win, out=logp[first:first + count])  # straight into the boost's input
             probs = torch.empty((N, W), dtype=torch.float32, device=self.device)
             mean = torch.empty((N,), dtype=torch.float32, device=self.device)
             if N > 0:
                 boosted = torch.empty((N, W, 2), dtype=torch.float32, device=self.device)
-                _lib.check(lib.savad_boost(ctypes.c_void_p(logp.data_ptr()), ctypes.c_void_p(pos.data_ptr()), n_items, N,
-                                           W, ctypes.c_void_p(boosted.data_ptr()), ctypes.c_void_p(probs.data_ptr()),
-                                           ctypes.c_void_p(mean.data_ptr()), stream))
+                _lib.check(lib.savad_boost(logp, pos, n_items, N, W, boosted, probs, mean, stream))
         return probs, mean
 
 
@@ -683,12 +679,11 @@ class StreamingPredictor:
         N, F = feat.shape
         W = self._window_count(N, self.T, self.hop)
         self.model.eval()
-        with torch.cuda.device(self.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with _lib.on_device(self.device):
             self._ensure_pipe()
 
             def windows_logp(lo, hi):  # this rank's contiguous span of windows -> [hi - lo, T, 2] log-probs
-                return self._windows_logp(feat, 0, N, lo, hi, stream)
+                return self._windows_logp(feat, 0, N, lo, hi)
 
             logp = sharded_rows(W, windows_logp, (self.T, 2), torch.float32, self.device).contiguous()
             return self._merge(logp, W, N)
@@ -708,11 +703,10 @@ class StreamingPredictor:
     def _merge(self, logp, W: int, N: int):
         """the windows' log-probs [W, T, 2] -> per-frame probabilities [N] (savad_overlap_merge on the current stream)"""
         probs = torch.empty((N,), dtype=torch.float32, device=logp.device)
-        _lib.check(_lib.load().savad_overlap_merge(ctypes.c_void_p(logp.data_ptr()), W, N, self.T, self.hop, ctypes.c_void_p(probs.data_ptr()),
-                                                   ctypes.c_void_p(torch.cuda.current_stream(logp.device).cuda_stream)))
+        _lib.check(_lib.load().savad_overlap_merge(logp, W, N, self.T, self.hop, probs, torch.cuda.current_stream(logp.device)))
         return probs
 
-    def _windows_logp(self, feat, frame0, n_total, lo, hi, stream, out=None, join=True):
+    def _windows_logp(self, feat, frame0, n_total, lo, hi, out=None, join=True):
         """log-probs [hi - lo, T, 2] of windows [lo, hi) of an n_total-frame recording, from `feat` = its frames [frame0,
         frame0 + len(feat)): windows that lie inside the recording are read IN PLACE (model.forward_windows, sequences hop * F
         elements apart: no copies); the last window of a recording that does not end on a window boundary is zero-padded
@@ -732,8 +726,7 @@ class StreamingPredictor:
                 win[0, :max(min(T, n_local - f_lo), 0)] = feat[f_lo:f_lo + T]
             else:
                 win = torch.empty((1, T, F), dtype=torch.float32, device=self.device)
-                _lib.check(lib.savad_gather_strided(ctypes.c_void_p(feat.data_ptr()), n_local, F, T, hop, w - frame0 // hop, 1,
-                                                    ctypes.c_void_p(win.data_ptr()), stream))
+                _lib.check(lib.savad_gather_strided(feat, n_local, F, T, hop, w - frame0 // hop, 1, win, torch.cuda.current_stream(self.device)))
             self._pipe.submit(win, out=local[w - lo:w - lo + 1])
         if join:
             self._pipe.join()
@@ -772,8 +765,7 @@ class StreamingPredictor:
         if hi <= lo:
             return torch.zeros((0, self.T, 2), dtype=torch.float32, device=self.device)
         self.model.eval()
-        with torch.cuda.device(self.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with _lib.on_device(self.device):
             self._ensure_pipe()
             sl = audio[first:first + count]
             if not isinstance(sl, torch.Tensor):
@@ -784,7 +776,7 @@ class StreamingPredictor:
             else:
                 sl = sl.to(self.device, torch.float32).contiguous()
             feat = log_mel_span(sl, first, n, f0, f1 - f0)
-            return self._windows_logp(feat, f0, 1 + n // 160, lo, hi, stream)
+            return self._windows_logp(feat, f0, 1 + n // 160, lo, hi)
 
     @torch.no_grad()
     def predict_audio_device(self, audio):
@@ -802,7 +794,7 @@ class StreamingPredictor:
         world, rank = (dist.get_world_size(), dist.get_rank()) if dist.is_initialized() else (1, 0)
         local = self.audio_span_logp(audio, rank, world)
         W = self._window_count(N, self.T, self.hop)
-        with torch.cuda.device(self.device):
+        with _lib.on_device(self.device):
             return self._merge((all_gather_rows(local, W) if world > 1 else local).contiguous(), W, N)
 
     _host_source = staticmethod(host_source)   # (the name scripts and callers knew it by)
@@ -853,8 +845,7 @@ class StreamingPredictor:
         plan = self.host_span_plan(n, self.T, self.hop, int(windows_per_chunk or self.max_batch), ramp)
         self.model.eval()
         dev = _indexed(self.device)
-        with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with _lib.on_device(dev):
             self._ensure_pipe()
             feed = HostFeed(src, dev, stream_owner=self)
             logp = torch.empty((W, self.T, 2), dtype=torch.float32, device=dev)
@@ -864,7 +855,7 @@ class StreamingPredictor:
                 if sl.dtype == torch.int16:
                     sl = pcm16_to_f32(sl)
                 feat = log_mel_span(sl, first, n, f0, f1 - f0)
-                self._windows_logp(feat, f0, N, lo, hi, stream, out=logp[lo:hi], join=False)   # (spans overlap on the pipeline's streams)
+                self._windows_logp(feat, f0, N, lo, hi, out=logp[lo:hi], join=False)   # (spans overlap on the pipeline's streams)
             self._pipe.join()
             return self._merge(logp, W, N)
 
