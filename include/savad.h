@@ -286,6 +286,35 @@ int savad_logmel_set_algorithm(int algorithm);
 int savad_logmel_table_floats(int which);
 int savad_logmel_tables_host(float* t1, float* t3, float* tm);
 
+/* THE LOG-MEL FEATURES OF MANY CLIPS IN ONE CALL: three launches whatever the number of clips, in front of
+ * savad_predict_probabilities_batch.  An AUDIO CLIP TABLE names the clips inside one float32 buffer of audio_count samples (device):
+ *   clips [C] {first, count}: clip c is samples [first, first + count).  count = 0 is legal and gives a clip without frames,
+ *   count >= 1 gives savad_logmel_frames(count) = 1 + count / 160 frames.  first is a multiple of 4: the kernel reads 16-byte chunks
+ *   straight from the clip and the batch has no aligned-copy fall-back.  Clips may overlap or repeat (they are only read: the
+ *   chunks of one recording are used in place).  No sample outside [first, first + count) is read for clip c.
+ * The call takes the table twice: clips_host (HOST) is validated and planned from, clips (DEVICE, the same values) is what the
+ * kernels read -- the library uploads nothing, allocates nothing and never synchronises; kernels go to `stream`.
+ * Refused before anything is launched: C < 1, a negative first or count, a clip that leaves [0, audio_count), a first that is no
+ * multiple of 4 (SAVAD_E_INVALID); a clip of more than 2 000 000 000 samples, more than 2^31 - 1 rows or tiles in all
+ * (SAVAD_E_UNSUPPORTED).
+ *   savad_logmel_batch_shape            rows = the frames of all clips, tiles = sum ceil(frames_c / 32) (a tile of 32 frames never spans
+ *       two clips); either pointer may be NULL.  HOST arithmetic.
+ *   savad_logmel_batch_workspace_bytes  HOST arithmetic: tiles_first [C + 1] int32, then a mirrored-head slot of 208 floats and a
+ *       tail slot of 212 floats per clip, every piece 16-byte aligned.
+ *   savad_logmel_batch                  features [rows][80] fp32: clip c's rows are [clip_first[c], clip_first[c + 1]), with the bits of
+ *       savad_logmel on the clip alone (a frame depends on nothing but its own 400 samples).  clip_first [C + 1] int32 (DEVICE) is
+ *       written by the call: the row table savad_predict_probabilities_batch takes, so that its caller uploads no second table.
+ *       audio, workspace, features and clip_first 16-byte aligned.  Writes exactly rows * 80 floats and C + 1 ints and stays inside
+ *       the reported workspace.  Only the factored DFT has a batch form: after savad_logmel_set_algorithm(1) the call returns
+ *       SAVAD_E_UNSUPPORTED. */
+typedef struct {
+    int64_t first, count;
+} savad_audio_clip;
+int savad_logmel_batch_shape(const savad_audio_clip* clips_host, int n_clips, int64_t audio_count, int64_t* rows, int64_t* tiles);
+int savad_logmel_batch_workspace_bytes(const savad_audio_clip* clips_host, int n_clips, int64_t audio_count, size_t* bytes);
+int savad_logmel_batch(const float* audio, int64_t audio_count, const savad_audio_clip* clips_host, const savad_audio_clip* clips,
+                       int n_clips, void* workspace, float* features, int32_t* clip_first, void* stream);
+
 /* Feature front-end for every transform a reference config can name (vad/acoustics/transforms/transform_factory.py:13-59)
  * and the temporal differences of vad/acoustics/feature_extractor.py:135-145 (stack_differences false), at 16 kHz.
  * hop / win in samples (int(hop_ms / 1000 * 16000), int(window_ms / 1000 * 16000)); output [n_frames][n_features] fp32:

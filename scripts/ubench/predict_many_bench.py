@@ -18,7 +18,17 @@ before every stamp (wall clock: the host's share is what a loop of small calls p
 and, between HIP events on the stream, the batch library call alone and the clip-aware gather of all its chunks alone
 (savad_gather_windows_batch, which also re-runs the one-workgroup scan per chunk): gather_share = gather / batch call.
 One JSON object on stdout (and in --out): every round, the medians, time per clip of each leg, and -- stated, not judged -- whether
-the batch is slower than the graph loop."""
+the batch is slower than the graph loop.
+
+python scripts/ubench/predict_many_bench.py --front-end [--out profiles/logmel_batch_bench.json]
+measures the front-end of the batch alone, the same workloads, precisions, rounds and stamps: audio -> features -> probabilities with
+    * per_clip   a log_mel call per clip into its rows of one matrix + ONE predict_windows_batch      (the `batch` leg above)
+    * one        ONE log_mel_many on the clip table + ONE predict_windows_batch with its device row table
+from host PCM16 (int16 arrays: per_clip uploads and converts each clip, one stages all of them and uploads once) and from float32
+audio on the device (the rows of one tensor: read in place).  Twelve cells (3 workloads x 2 precisions x 2 sources); a cell counts
+as won when the slowest round of `one` is below the fastest round of `per_clip` (the medians differ by more than the rounds'
+spread).  `--trace-calls K --leg LEG --source SRC` makes exactly K calls of one leg on clips_64x10s and nothing else: run under a
+kernel trace of its own, the front-end kernels' call counts divided by K are the launches per call."""
 from __future__ import annotations
 
 import argparse
@@ -35,7 +45,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
 
 from voice_activity_detection_amd import SelfAttentiveVAD, VADFromScratchPredictor, _lib, seeded_state_dict  # noqa: E402
 from voice_activity_detection_amd.clips import clip_table, split_by_clip, window_items  # noqa: E402
-from voice_activity_detection_amd.features import log_mel  # noqa: E402
+from voice_activity_detection_amd.features import log_mel, log_mel_many  # noqa: E402
 
 ROUNDS = 5
 WORKLOADS = {"clips_64x10s": (64, 160000), "clips_512x1s": (512, 16000), "hour_split10": (360, 160000)}
@@ -128,18 +138,82 @@ def measure(model, dev, n_clips: int, n_samples: int, seed: int) -> dict:
             "batch_slower_than_graph_loop": bool(med["batch"] > med["loop_graph"])}
 
 
+def front_end_legs(model, dev, n_clips: int, n_samples: int, seed: int) -> dict:
+    """(source, leg) -> a call: audio -> features -> probabilities of every clip"""
+    pred = VADFromScratchPredictor(model, dev)
+    half, jump, chunk = pred.context_window_half_frames, pred.context_window_jump_frames, pred.chunk_size
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    audio = (torch.rand((n_clips, n_samples), generator=gen, device=dev) - 0.5) * 0.2
+    pcm = (audio * 32768.0).to(torch.int16).cpu().numpy()
+    sources = {"host_pcm16": [pcm[i] for i in range(n_clips)], "device_f32": [audio[i] for i in range(n_clips)]}
+    table = clip_table([1 + n_samples // 160] * n_clips)
+
+    def per_clip(clips):
+        m = torch.empty((int(table[-1]), 80), dtype=torch.float32, device=dev)
+        for c, rows in zip(clips, split_by_clip(m, table)):
+            log_mel(c, dev, out=rows)
+        return model.predict_windows_batch(m, table, half, jump, chunk)
+
+    def one(clips):
+        m, first, first_dev = log_mel_many(clips, dev)
+        return model.predict_windows_batch(m, first, half, jump, chunk, first_dev)
+
+    return {(src, leg): (lambda fn=fn, clips=clips: fn(clips)) for src, clips in sources.items() for leg, fn in (("per_clip", per_clip), ("one", one))}
+
+
+def measure_front_end(model, dev, n_clips: int, n_samples: int, seed: int) -> dict:
+    legs = front_end_legs(model, dev, n_clips, n_samples, seed)
+    for fn in legs.values():   # warm-up: table upload, workspace growth, staging buffer, allocator
+        for _ in range(2):
+            fn()
+    out = {"clips": n_clips, "frames_per_clip": 1 + n_samples // 160}
+    for src in ("host_pcm16", "device_f32"):
+        same = all(torch.equal(a, b) for a, b in zip(legs[src, "per_clip"](), legs[src, "one"]()))
+        rounds = []
+        for _ in range(ROUNDS):
+            r = {}
+            for leg in ("per_clip", "one"):
+                t0 = stamp()
+                legs[src, leg]()
+                r[leg + "_ms"] = round((stamp() - t0) * 1e3, 4)
+            rounds.append(r)
+        med = {leg: statistics.median(r[leg + "_ms"] for r in rounds) for leg in ("per_clip", "one")}
+        spread = {leg: [min(r[leg + "_ms"] for r in rounds), max(r[leg + "_ms"] for r in rounds)] for leg in ("per_clip", "one")}
+        out[src] = {"same_bits": bool(same), "rounds": rounds, "median_ms": {k: round(v, 4) for k, v in med.items()}, "min_max_ms": spread,
+                    "per_clip_us": {k: round(v * 1e3 / n_clips, 3) for k, v in med.items()},
+                    "one_over_per_clip": round(med["one"] / med["per_clip"], 4),
+                    "one_below_per_clip_beyond_spread": bool(spread["one"][1] < spread["per_clip"][0])}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", type=Path, default=None)
+    ap.add_argument("--front-end", action="store_true", help="the front-end legs (per-clip log_mel calls against one log_mel_many)")
+    ap.add_argument("--trace-calls", type=int, default=0, help="make exactly this many calls of --leg from --source and nothing else")
+    ap.add_argument("--leg", choices=("per_clip", "one"), default="one")
+    ap.add_argument("--source", choices=("host_pcm16", "device_f32"), default="device_f32")
     args = ap.parse_args()
     dev = torch.device("cuda", torch.cuda.current_device())
     model = SelfAttentiveVAD(80, 3, 128, 0.5)
     model.load_state_dict({k: torch.from_numpy(v) for k, v in seeded_state_dict(1234).items()})
     model = model.to(dev).eval()
+    if args.trace_calls:
+        model.precision = "bf16"
+        call = front_end_legs(model, dev, *WORKLOADS["clips_64x10s"], 11)[args.source, args.leg]
+        for _ in range(args.trace_calls):
+            call()
+        torch.cuda.synchronize()
+        print(json.dumps({"leg": args.leg, "source": args.source, "calls": args.trace_calls, "clips": WORKLOADS["clips_64x10s"][0]}))
+        return
     res = {"device": torch.cuda.get_device_name(0), "rounds_per_workload": ROUNDS, "chunk_size": 16384}
     for precision in ("bf16", "fp32s"):
         model.precision = precision
-        res[precision] = {name: measure(model, dev, n, samples, 11 + i) for i, (name, (n, samples)) in enumerate(WORKLOADS.items())}
+        run = measure_front_end if args.front_end else measure
+        res[precision] = {name: run(model, dev, n, samples, 11 + i) for i, (name, (n, samples)) in enumerate(WORKLOADS.items())}
+    if args.front_end:
+        cells = [res[p][w][s]["one_below_per_clip_beyond_spread"] for p in ("bf16", "fp32s") for w in WORKLOADS for s in ("host_pcm16", "device_f32")]
+        res["cells_won"], res["cells"] = sum(cells), len(cells)
     text = json.dumps(res, indent=1)
     if args.out is not None:
         args.out.parent.mkdir(parents=True, exist_ok=True)

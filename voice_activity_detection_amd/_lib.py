@@ -59,6 +59,10 @@ class savad_live_post_config(ctypes.Structure):
                 ("hang_over", c_int32)]
 
 
+class savad_audio_clip(ctypes.Structure):
+    _fields_ = [("first", c_int64), ("count", c_int64)]
+
+
 # ---- pointer argument types ---------------------------------------------------------------------------------------------------
 f32, f64, bf16, i16, i32, i64, u8 = (torch.float32, torch.float64, torch.bfloat16, torch.int16, torch.int32, torch.int64, torch.uint8)
 _NUMPY = {d: np.dtype(str(d)[6:]) for d in (f32, f64, i16, i32, i64, u8)}
@@ -117,6 +121,32 @@ _cfg, _fe, _live, _post = POINTER(savad_config), POINTER(savad_frontend_config),
 _slots, _size = POINTER(savad_live_slot), POINTER(c_size_t)
 _ws, _table_host, _table_dev = dev(u8, f32), host(u8), dev(u8)   # a workspace, as the callers allocate them; a live tick's tables
 
+
+class _AudioClips(POINTER(savad_audio_clip)):
+    """An `argtypes` entry for a savad_audio_clip [C] table in `side` memory: an int64 [C, 2] array or tensor of (first, count) is
+    checked as `_Memory` checks and becomes its address; None, an int, a c_void_p or a pointer pass through (the raw form of the C ABI).
+    (A struct pointer of the header is a ctypes pointer type in this table, so the class derives from one.)"""
+    _type_ = savad_audio_clip
+    side = None
+
+    @classmethod
+    def from_param(cls, value):
+        if isinstance(value, (torch.Tensor, np.ndarray)):
+            if value.ndim != 2 or value.shape[1] != 2:
+                raise ValueError(f"{cls.__name__}: an audio clip table is [C, 2] (first, count), not {tuple(value.shape)}")
+            _memory((cls.side,), i64).from_param(value)   # (the side, dtype and contiguity checks)
+            value = value.data_ptr() if isinstance(value, torch.Tensor) else value.ctypes.data
+        if isinstance(value, (int, c_void_p)):
+            value = ctypes.cast(value if isinstance(value, c_void_p) else c_void_p(value), POINTER(savad_audio_clip))
+        return POINTER(savad_audio_clip).from_param(value)   # (ctypes' own check: None, a pointer, byref, an array of the struct)
+
+
+def _audio_clips(side: str) -> type:
+    return type(f"{side} audio clips", (_AudioClips,), {"side": side, "_type_": savad_audio_clip})
+
+
+_clips_host, _clips_dev = _audio_clips("host"), _audio_clips("device")   # savad_audio_clip [C] on either side
+
 # every symbol include/savad.h declares: name -> (restype, argtypes); pointer kinds and element types as the header states them
 SYMBOLS = {
     "savad_create": (c_int, [_cfg, POINTER(handle)]),
@@ -162,6 +192,9 @@ SYMBOLS = {
     "savad_logmel_set_algorithm": (c_int, [c_int]),
     "savad_logmel_table_floats": (c_int, [c_int]),
     "savad_logmel_tables_host": (c_int, [host(f32), host(f32), host(f32)]),
+    "savad_logmel_batch_shape": (c_int, [_clips_host, c_int, c_int64, POINTER(c_int64), POINTER(c_int64)]),
+    "savad_logmel_batch_workspace_bytes": (c_int, [_clips_host, c_int, c_int64, _size]),
+    "savad_logmel_batch": (c_int, [dev(f32), c_int64, _clips_host, _clips_dev, c_int, _ws, dev(f32), dev(i32), stream]),
     "savad_frontend_shape": (c_int, [_fe, c_long, POINTER(c_int), POINTER(c_int)]),
     "savad_frontend_workspace_bytes": (c_int, [_fe, c_long, _size]),
     "savad_frontend_prepare": (c_int, [_fe]),

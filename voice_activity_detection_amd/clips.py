@@ -42,6 +42,25 @@ def window_items(clip_first, half: int) -> np.ndarray:
     return np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
 
 
+def audio_clip_table(lengths, align: int = 4):
+    """sample counts of the clips, in order -> (table [C, 2] int64 of (first, count), audio_count): the clips one after the other in
+    ONE buffer of audio_count samples, every `first` rounded up to a multiple of `align` samples (savad_logmel_batch reads 16-byte
+    chunks straight from a clip: 4 floats; 8 also suits a PCM16 staging buffer converted in 8-byte pieces).  An empty clip is legal."""
+    n = np.asarray(list(lengths), dtype=np.int64)
+    align = int(align)
+    if n.ndim != 1 or n.size < 1:
+        raise ValueError("an audio clip table needs at least one clip")
+    if (n < 0).any():
+        raise ValueError("a clip cannot have a negative number of samples")
+    if align < 4 or align % 4:
+        raise ValueError("align must be a positive multiple of 4 samples")
+    table = np.zeros((n.size, 2), dtype=np.int64)
+    table[:, 1] = n
+    padded = (n + align - 1) // align * align
+    table[1:, 0] = np.cumsum(padded[:-1])
+    return table, int(table[-1, 0] + n[-1])
+
+
 def split_by_clip(rows, clip_first) -> list:
     """rows [sum N, ...] (array or tensor) -> one view per clip, in order: rows[clip_first[c]:clip_first[c + 1]]"""
     t = [int(v) for v in clip_first]

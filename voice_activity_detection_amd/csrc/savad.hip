@@ -23,6 +23,7 @@
 #include "savad_weights.h"
 #include "savad_live.h"
 #include "savad_live_post.h"
+#include "savad_logmel_batch.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -1449,8 +1450,8 @@ SAVAD_EXPORT int savad_logmel_span(const float* audio, long audio_first, long au
     if ((rc = mel_tables(&tb, &n_cu))) return rc;
     const float* y0 = audio - audio_first;  // y0[i] = sample i (only indices inside the slice are ever read)
     // the frames read padded indices [j_first, j_last + 4), in 16-byte chunks (savad_logmel.h: sample stage)
-    const long j_first = (long)mel::HOP * frame_first + 48, j_last = (long)mel::HOP * (frame_first + frame_count - 1) + 460;
-    constexpr long NEVER = 1L << 40;
+    const mel::PadRule rule = mel::pad_rule(n_samples, frame_first, frame_count);
+    constexpr long NEVER = mel::PAD_NEVER;
     const mel::Workspace w = mel::workspace_span(frame_count);   // (the whole-signal workspace places its pieces the same)
     mel::FftSrc src{};
     mel::PadSeg A{at(workspace, w.pad_a), 0, 0}, B{at(workspace, w.pad_b), 0, 0};
@@ -1458,21 +1459,14 @@ SAVAD_EXPORT int savad_logmel_span(const float* audio, long audio_first, long au
     src.jA_end = -NEVER;
     src.jB0 = NEVER;
     const bool direct = (((uintptr_t)audio - (uintptr_t)audio_first * 4u) & 15) == 0;
-    if (direct) {
-        if (j_first < mel::N_FFT / 2) {  // the stretch that mirrors the head of the signal
-            A.j0 = j_first;
-            A.count = (int)((j_last + 4 < mel::N_FFT / 2 ? j_last + 4 : mel::N_FFT / 2) - j_first);
-            src.jA_end = mel::N_FFT / 2;
-        }
-        const long jb = (n_samples + 253 + 3) & ~3L;  // first chunk that runs past the last sample
-        if (j_last >= jb) {
-            B.j0 = jb;
-            B.count = (int)(j_last + 4 - jb);  // <= 212
-            src.jB0 = jb;
-        }
+    if (direct) {  // the mirrored head and the run past the last sample, where the frames touch them
+        if (rule.a_count) A.j0 = rule.a_j0, A.count = rule.a_count;
+        if (rule.b_count) B.j0 = rule.b_j0, B.count = rule.b_count;
+        src.jA_end = rule.a_end;
+        src.jB0 = rule.b_j0;
     } else {  // unaligned audio: the whole span from a padded (and thereby aligned) copy
-        A.j0 = j_first;
-        A.count = (int)(j_last + 4 - j_first);
+        A.j0 = rule.j_first;
+        A.count = (int)(rule.j_last + 4 - rule.j_first);
         src.jA_end = NEVER;
     }
     src.padA = A.dst;
@@ -1505,6 +1499,63 @@ SAVAD_EXPORT int savad_logmel(const float* audio, int n_samples, float* workspac
     hipLaunchKernelGGL(mel::reflect_pad_kernel, dim3(grid_for(total)), dim3(256), 0, st, audio, n_samples, workspace);
     const int tiles = (n_frames + 31) / 32;
     hipLaunchKernelGGL(mel::logmel_kernel<4>, dim3(tiles), dim3(256), 0, st, workspace, n_frames, std::get<0>(tb), std::get<1>(tb), features);
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+// ---- log-mel over a clip table (savad_logmel_batch_plan.h: the host plan; savad_logmel_batch.h: the kernels) ------------------
+namespace {
+static_assert(sizeof(savad_audio_clip) == sizeof(melbatch::Clip), "audio clip ABI struct");
+
+// the HOST table validated and planned; the refusal's message when it is not an audio clip table
+int logmel_batch_plan(const savad_audio_clip* clips_host, int n_clips, int64_t audio_count, melbatch::Plan* p) {
+    *p = melbatch::plan(reinterpret_cast<const melbatch::Clip*>(clips_host), n_clips, audio_count);
+    return p->err ? fail(p->err, "%s", p->msg) : SAVAD_OK;
+}
+}  // namespace
+
+SAVAD_EXPORT int savad_logmel_batch_shape(const savad_audio_clip* clips_host, int n_clips, int64_t audio_count, int64_t* rows, int64_t* tiles) {
+    melbatch::Plan p;
+    if (int rc = logmel_batch_plan(clips_host, n_clips, audio_count, &p)) return rc;
+    if (rows) *rows = p.rows;
+    if (tiles) *tiles = p.tiles;
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_logmel_batch_workspace_bytes(const savad_audio_clip* clips_host, int n_clips, int64_t audio_count, size_t* bytes) {
+    melbatch::Plan p;
+    if (int rc = logmel_batch_plan(clips_host, n_clips, audio_count, &p)) return rc;
+    if (!bytes) return fail(SAVAD_E_INVALID, "null argument");
+    *bytes = p.total;
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_logmel_batch(const float* audio, int64_t audio_count, const savad_audio_clip* clips_host, const savad_audio_clip* clips,
+                                    int n_clips, void* workspace, float* features, int32_t* clip_first, void* stream) {
+    melbatch::Plan p;
+    int rc = logmel_batch_plan(clips_host, n_clips, audio_count, &p);
+    if (rc) return rc;
+    if (g_logmel_algorithm != 0) return fail(SAVAD_E_UNSUPPORTED, "the one-GEMM DFT (savad_logmel_set_algorithm(1)) has no batch form");
+    if (!clips || !workspace || !clip_first || (p.rows > 0 && (!audio || !features))) return fail(SAVAD_E_INVALID, "null pointer");
+    if (!aligned16(audio, workspace) || !aligned16(features, clip_first))
+        return fail(SAVAD_E_INVALID, "audio, workspace, features and clip_first must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    int n_cu;
+    MelTables::Ptrs tb;
+    if ((rc = mel_tables(&tb, &n_cu))) return rc;
+    char* ws = (char*)workspace;
+    int32_t* tiles_first = (int32_t*)(ws + p.tiles_first);
+    float *head = (float*)(ws + p.head), *tail = (float*)(ws + p.tail);
+    const melbatch::Clip* table = reinterpret_cast<const melbatch::Clip*>(clips);
+    hipLaunchKernelGGL(melbatch::clip_frames_scan_kernel, dim3(1), dim3(BATCH_SCAN_THREADS), 0, st, table, n_clips, clip_first, tiles_first);
+    if (p.tiles > 0) {
+        hipLaunchKernelGGL(melbatch::reflect_pad_clips_kernel, dim3(grid_for((long)n_clips * (melbatch::HEAD_SLOT + melbatch::TAIL_SLOT))), dim3(256), 0,
+                           st, audio, table, n_clips, head, tail);
+        const auto [d_dft, d_mel, d_t1, d_t3, d_tm] = tb;
+        const int tiles = (int)p.tiles, grid = tiles < n_cu ? tiles : n_cu;
+        hipLaunchKernelGGL(melbatch::logmel_fft_kernel_clips, dim3(grid), dim3(256), mel::FFT_LDS_BYTES, st, audio, table, (const int32_t*)clip_first,
+                           (const int32_t*)tiles_first, n_clips, tiles, (const float*)head, (const float*)tail, d_t1, d_t3, d_tm, features);
+    }
     HIP_TRY(hipGetLastError());
     return SAVAD_OK;
 }
@@ -2232,6 +2283,7 @@ int audio_device(int dev, int* n_cu) {
         if ((rc = allow_lds(ingest::resample_kernel<true>, ingest::LDS_BYTES_MAX))) return rc;   // rs_host refuses a rate that needs more
         if ((rc = allow_lds(ingest::resample_kernel<false>, ingest::LDS_BYTES_MAX - ingest::NWIN * 16))) return rc;
         if ((rc = allow_lds(live::logmel_fft_kernel_table, mel::FFT_LDS_BYTES))) return rc;
+        if ((rc = allow_lds(melbatch::logmel_fft_kernel_clips, mel::FFT_LDS_BYTES))) return rc;
         g_audio_n_cu[dev] = n;
     }
     *n_cu = g_audio_n_cu[dev];

@@ -193,6 +193,55 @@ inline void span_samples(long n, int frame_first, int frame_count, long* first, 
     *count = b - a;
 }
 
+// Which padded indices j (ypad[j] = y[reflect(j - 256)]) frames [frame_first, frame_first + frame_count) of an n-sample signal read,
+// in 16-byte chunks: [j_first, j_last + 4).  On the direct path (aligned audio) the chunks below a_end = 256 come from stretch A =
+// padded indices [a_j0, a_j0 + a_count), the mirrored head; the chunks from b_j0 on from stretch B = [b_j0, b_j0 + b_count), the
+// run past the last sample; everything between straight from the audio.  A stretch the frames do not touch has count 0 and its
+// bound is PAD_NEVER away.  Written once, for the host (savad_logmel_span, the plans) and for the kernels that place the stretches
+// themselves (savad_logmel_batch.h): __host__ __device__ under hipcc, plain C++ anywhere else.
+#if defined(__HIPCC__)
+#define SAVAD_PAD_HD __host__ __device__
+#else
+#define SAVAD_PAD_HD
+#endif
+constexpr long PAD_NEVER = 1L << 40;
+constexpr int PAD_A_MAX = 208, PAD_B_MAX = 212;   // floats a stretch holds at most
+struct PadRule {
+    long j_first, j_last;
+    long a_j0, a_end, b_j0;
+    int a_count, b_count;
+};
+SAVAD_PAD_HD inline PadRule pad_rule(long n, long frame_first, long frame_count) {
+    PadRule r{};
+    r.j_first = (long)HOP * frame_first + 48;
+    r.j_last = (long)HOP * (frame_first + frame_count - 1) + 460;
+    r.a_end = -PAD_NEVER;
+    r.b_j0 = PAD_NEVER;
+    if (r.j_first < N_FFT / 2) {  // the stretch that mirrors the head of the signal
+        r.a_j0 = r.j_first;
+        r.a_count = (int)((r.j_last + 4 < N_FFT / 2 ? r.j_last + 4 : N_FFT / 2) - r.j_first);
+        r.a_end = N_FFT / 2;
+    }
+    const long jb = (n + 253 + 3) & ~3L;  // first chunk that runs past the last sample
+    if (r.j_last >= jb) {
+        r.b_j0 = jb;
+        r.b_count = (int)(r.j_last + 4 - jb);  // <= 212
+    }
+    return r;
+}
+// the sample padded index j stands for: one reflection at either end (numpy.pad(mode="reflect")), then the clamps for signals
+// shorter than the padding -- the index rule of reflect_pad_segments_kernel (savad_logmel.h).  That kernel keeps its own statement:
+// calling this inline there gave it another register allocation (54 VGPRs for 52, other instruction order), and its code is pinned
+SAVAD_PAD_HD inline long pad_source(long j, long n) {
+    long i = j - N_FFT / 2;
+    if (i < 0) i = -i;
+    if (i >= n) i = 2L * (n - 1) - i;
+    if (i < 0) i = 0;
+    if (i >= n) i = n - 1;
+    return i;
+}
+#undef SAVAD_PAD_HD
+
 // Workspace of savad_logmel (n samples) and savad_logmel_span (frame_count frames), in bytes.  Algorithm 1 and an unaligned
 // audio pointer fill it from offset 0 with the padded signal / the padded span; aligned audio materialises only the two
 // edge stretches (the mirrored head, at most 208 floats, and the run past the last sample, at most 212), one PAD_SEG each.

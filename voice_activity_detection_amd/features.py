@@ -5,6 +5,7 @@ configuration a checkpoint can name."""
 from __future__ import annotations
 
 import ctypes
+import threading
 from dataclasses import dataclass
 from pathlib import Path
 from typing import Optional
@@ -345,6 +346,121 @@ def log_mel(audio, device="cuda", out: Optional[torch.Tensor] = None) -> torch.T
         # (raw addresses, as in the model's forward: made or checked above, and a typed argument costs ~1 us each, a fifth of this call)
         _lib.check(lib.savad_logmel(y.data_ptr(), n, buf.data_ptr(), out.data_ptr(), torch.cuda.current_stream(y.device)))
     return out
+
+
+_staging = {}   # (dtype, device) -> [pinned host buffer, event of the last upload from it]; guarded by _staging_lock
+_staging_lock = threading.Lock()
+STAGING_KEEP_BYTES = 128 << 20   # a staging buffer above this is not kept between calls (one hour of PCM16 is 115 MB)
+
+
+def release_staging() -> None:
+    """give back the pinned staging buffers log_mel_many keeps between calls (after their last upload has finished)"""
+    with _staging_lock:
+        for _, busy in _staging.values():
+            if busy is not None:
+                busy.synchronize()
+        _staging.clear()
+
+
+def _upload_staged(arrays, table, audio_count: int, dtype, dev: torch.device) -> torch.Tensor:
+    """host arrays -> their table positions of ONE pinned staging buffer -> the device, in one copy.  The buffer is kept between calls
+    and grows, up to STAGING_KEEP_BYTES (a larger one lives for its call only); release_staging() gives the kept ones back.  One lock
+    covers the whole step -- waiting for the previous upload from the buffer, filling it, queueing the copy, recording its event --
+    so calls from several threads take turns."""
+    with _staging_lock:
+        slot = _staging.get((dtype, dev))
+        if slot is None or slot[0].numel() < audio_count:
+            slot = [torch.empty(max(audio_count, 1), dtype=dtype, pin_memory=True), None]
+            if slot[0].numel() * slot[0].element_size() <= STAGING_KEEP_BYTES:
+                _staging[dtype, dev] = slot
+            else:
+                _staging.pop((dtype, dev), None)
+        stage, busy = slot
+        if busy is not None:
+            busy.synchronize()
+        view = stage.numpy()
+        for a, (first, count) in zip(arrays, table):
+            view[first:first + count] = a
+        up = stage[:audio_count].to(dev, non_blocking=True)   # (torch's pinned allocator keeps an unkept buffer's memory until the copy is done)
+        slot[1] = torch.cuda.Event()
+        slot[1].record(torch.cuda.current_stream(dev))
+    return up
+
+
+def _in_place_clips(tensors):
+    """1-D float32 views of ONE storage whose byte offsets from a 16-byte-aligned base are multiples of 16 -> (base address, table,
+    audio_count): the clips are read where they are.  None for any other list."""
+    full = [t for t in tensors if t.numel()]   # (an empty view has no address: it is clip (0, 0))
+    if not full:
+        return None
+    store = full[0].untyped_storage().data_ptr()
+    base = min(t.data_ptr() for t in full)
+    if base % 16 or any(t.untyped_storage().data_ptr() != store or (t.data_ptr() - base) % 16 for t in full):
+        return None
+    table = np.array([((t.data_ptr() - base) // 4, t.numel()) if t.numel() else (0, 0) for t in tensors], dtype=np.int64)
+    return base, table, int((table[:, 0] + table[:, 1]).max())
+
+
+def log_mel_many(audios, device="cuda"):
+    """The log-mel features of MANY clips through one library call (savad_logmel_batch: three launches whatever the number of
+    clips) -> (feature [rows, 80] float32 on the device, clip_first [C + 1] int32 on the host, the same table on the device): clip
+    c's rows are feature[clip_first[c]:clip_first[c + 1]], with the bits of log_mel(clip).  An empty clip is legal and has no rows.
+    audios: 1-D clips @16 kHz; int16 is PCM16 (sample / 32768), anything else is taken as float32.  Host arrays are copied to their
+    places in one pinned staging buffer and go up in ONE copy (a list of int16 arrays only as PCM16, converted on the device by one
+    savad_pcm16_to_f32; int16 clips among others are converted while staging).  float32 device tensors that are views of one
+    storage at 16-byte steps (the rows of a matrix, the chunks of a recording cut at multiples of 4 samples) are read in place;
+    any other list is gathered into one device buffer first."""
+    from .clips import audio_clip_table
+
+    lib = _lib.load()
+    dev = device if isinstance(device, torch.device) else torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.SavadError("the log-mel front-end runs only on a HIP device (no CPU fallback)")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    audios = list(audios)
+    if not audios:
+        raise ValueError("log_mel_many needs at least one clip")
+    for a in audios:
+        if getattr(a, "ndim", None) != 1:
+            raise ValueError("every clip must be a 1-D array")
+    with _lib.on_device(dev):
+        keep = None   # what owns the device audio until the launches are queued
+        if all(isinstance(a, torch.Tensor) and a.device == dev and a.dtype == torch.float32 and a.is_contiguous() for a in audios):
+            placed = _in_place_clips(audios)
+            if placed is not None:
+                audio, table, audio_count = placed
+                keep = audios
+        elif not any(isinstance(a, torch.Tensor) and a.is_cuda for a in audios):
+            host = [a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a) for a in audios]
+            pcm = all(a.dtype == np.int16 for a in host)
+            if not pcm:   # float32 staging: an int16 clip among the others is scaled as the device conversion scales it (exact)
+                host = [a.astype(np.float32) * np.float32(1.0 / 32768.0) if a.dtype == np.int16 else np.asarray(a, dtype=np.float32) for a in host]
+            table, audio_count = audio_clip_table([a.size for a in host])
+            keep = _upload_staged(host, table, audio_count, torch.int16 if pcm else torch.float32, dev)
+            if pcm and audio_count:
+                keep = pcm16_to_f32(keep)
+            audio = keep.data_ptr()
+        if keep is None:   # anything else: every clip as float32 on the device, gathered at the table's positions by one cat
+            clips = [_device_audio(a, dev, "log-mel") if len(a) else torch.empty(0, dtype=torch.float32, device=dev) for a in audios]
+            table, audio_count = audio_clip_table([c.numel() for c in clips])
+            gap = torch.zeros(3, dtype=torch.float32, device=dev)
+            parts = []
+            for c, (first, count), nxt in zip(clips, table, list(table[1:, 0]) + [audio_count]):
+                parts += [c, gap[:int(nxt - first - count)]]
+            keep = torch.cat(parts)
+            audio = keep.data_ptr()
+        counts = table[:, 1]
+        nbytes = ctypes.c_size_t()
+        _lib.check(lib.savad_logmel_batch_workspace_bytes(table, len(table), audio_count, ctypes.byref(nbytes)))   # (validates the table)
+        clip_first = np.concatenate([[0], np.cumsum(np.where(counts > 0, 1 + counts // _HOP, 0))]).astype(np.int32)
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        table_dev = torch.from_numpy(table).to(dev)
+        feature = torch.empty((int(clip_first[-1]), 80), dtype=torch.float32, device=dev)
+        clip_first_dev = torch.empty(len(table) + 1, dtype=torch.int32, device=dev)
+        _lib.check(lib.savad_logmel_batch(audio, audio_count, table, table_dev, len(table), ws, feature, clip_first_dev,
+                                          torch.cuda.current_stream(dev)))
+    return feature, clip_first, clip_first_dev
 
 
 def log_mel_span(audio, audio_first: int, n_samples: int, frame_first: int, frame_count: int) -> torch.Tensor:

@@ -382,14 +382,15 @@ class SelfAttentiveVAD(nn.Module):
         return self._predict_windows(feature, half, jump, chunk)
 
     @torch.no_grad()
-    def predict_windows_batch(self, feature: Tensor, clip_first, half: int, jump: int, chunk: int):
+    def predict_windows_batch(self, feature: Tensor, clip_first, half: int, jump: int, chunk: int, clip_first_dev: Optional[Tensor] = None):
         """predict_windows for MANY clips in one library call (savad_predict_probabilities_batch): feature [sum N, F] fp32 on the
         device holds the clips one after the other, clip_first [C + 1] (clips.clip_table: list, array or tensor) says where each
         starts -> (probs [sum N, W], mean [sum N]), clip c's result in its rows.  No window crosses a clip boundary and every clip
-        keeps its own 0.5 placeholders; the windows of all clips share `chunk`-sized forwards."""
-        return self._predict_windows(feature, half, jump, chunk, clip_first)
+        keeps its own 0.5 placeholders; the windows of all clips share `chunk`-sized forwards.  `clip_first_dev`: the same table,
+        int32 [C + 1] on the feature's device already (features.log_mel_many writes it there) -- it is then not uploaded again."""
+        return self._predict_windows(feature, half, jump, chunk, clip_first, clip_first_dev)
 
-    def _predict_windows(self, feature: Tensor, half: int, jump: int, chunk: int, clip_first=None):
+    def _predict_windows(self, feature: Tensor, half: int, jump: int, chunk: int, clip_first=None, clip_first_dev=None):
         """predict_windows (no clip table) and predict_windows_batch: the feature check and alignment clone, the outputs, the
         workspace query and the call."""
         device = feature.device
@@ -406,6 +407,8 @@ class SelfAttentiveVAD(nn.Module):
             table = check_clip_table(clip_first.cpu().numpy() if isinstance(clip_first, Tensor) else clip_first)
             if int(table[-1]) != N:
                 raise ValueError(f"the clip table ends at row {int(table[-1])}, the feature matrix has {N}")
+            if clip_first_dev is not None:
+                _lib.check_tensor(clip_first_dev, "clip_first_dev", torch.int32, shape=(table.size,), device=device)
         if feat.data_ptr() % 16:   # (the library wants the matrix 16-byte aligned; the module takes any tensor)
             feat = feat.clone()
         lib = _lib.load()
@@ -420,7 +423,8 @@ class SelfAttentiveVAD(nn.Module):
             if table is None:
                 size, run, clips_host, clips = lib.savad_predict_workspace_bytes, lib.savad_predict_probabilities, (N,), (N,)
             else:
-                table_dev = torch.from_numpy(table).to(device)   # (the library uploads nothing: the device copy is the caller's)
+                # (the library uploads nothing: the device copy is the caller's)
+                table_dev = torch.from_numpy(table).to(device) if clip_first_dev is None else clip_first_dev
                 size, run = lib.savad_predict_batch_workspace_bytes, lib.savad_predict_probabilities_batch
                 clips_host, clips = (table, table.size - 1), (table, table_dev, table.size - 1)
             nbytes = ctypes.c_size_t()

@@ -78,6 +78,11 @@ def _require_shipped_front_end(self, what: str):
         raise NotImplementedError(self._not_shipped.format(what=what, front_end=self.front_end))
 
 
+# VADFromScratchPredictor(batch_front_end=...): on, because the one-call front-end was below the per-clip one by more than the rounds'
+# spread in all twelve cells of the measured table (profiles/logmel_batch_bench.json)
+BATCH_FRONT_END_DEFAULT = True
+
+
 @dataclass
 class ContextResolution:
     """config.context_resolution of the reference (vad/configs/dataset_config.py:7-10)."""
@@ -109,7 +114,8 @@ class VADFromScratchPredictor:
 
     def __init__(self, model: SelfAttentiveVAD, device: torch.device, context: ContextResolution = ContextResolution(),
                  chunk_size: int = 16384, graph: bool = False, graph_max_seconds: float = 120.0, graph_cache: int = 8,
-                 front_end=None, device_ingest: bool = False, device_post: bool = False, batch_chunks: bool = False):
+                 front_end=None, device_ingest: bool = False, device_post: bool = False, batch_chunks: bool = False,
+                 batch_front_end: bool = BATCH_FRONT_END_DEFAULT):
         """`graph=True` (not in the reference's signature): clip-sized inputs -- up to `graph_max_seconds` of audio -- run as a
         replayed HIP graph of the whole chain log-mel -> window gather -> forward -> boost, captured on first use per (length, model
         knobs) and re-captured when the weights change; at most `graph_cache` graphs are kept (least recently used goes).  For a 10 s
@@ -129,13 +135,18 @@ class VADFromScratchPredictor:
         `batch_chunks=True`: predict() sends the `split_max_seconds` chunks of a recording through ONE batched prediction
         (predict_many: every chunk's features into one matrix, one library call for the windows of all chunks) instead of one
         call per chunk; the probabilities agree with the looped path to fp32 rounding (the forwards see other batches).  Off by
-        default."""
+        default.
+        `batch_front_end`: predict_many (and with it the `batch_chunks` path of predict) computes the features of all chunks in ONE
+        front-end call on the clip table (features.log_mel_many: three launches and one upload whatever the number of chunks) and
+        hands its device row table on to the batched prediction, instead of one log_mel call per chunk; the same bits either way.
+        A custom features_fn and the extended front-ends keep the per-chunk calls.  On by default (measured: DESIGN.md section 4o)."""
         from .features import SHIPPED_FRONT_END
 
         self.front_end = SHIPPED_FRONT_END if front_end is None else front_end
         self.device_ingest = bool(device_ingest)
         self.device_post = bool(device_post)
         self.batch_chunks = bool(batch_chunks)
+        self.batch_front_end = bool(batch_front_end)
         self.post_stats = {"device": 0, "host": 0}   # chunks post-processed on the GPU / on the host
         self.graph, self.graph_max_seconds, self.graph_cache = bool(graph), float(graph_max_seconds), int(graph_cache)
         self._graphs: "OrderedDict[tuple, dict]" = OrderedDict()
@@ -199,7 +210,8 @@ class VADFromScratchPredictor:
 
     @classmethod
     def from_checkpoint(cls, checkpoint_path, device, trust_checkpoint: bool = False, extended_front_end: bool = False,
-                        device_ingest: bool = False, device_post: bool = False, batch_chunks: bool = False):
+                        device_ingest: bool = False, device_post: bool = False, batch_chunks: bool = False,
+                        batch_front_end: bool = BATCH_FRONT_END_DEFAULT):
         """vad/predictor.py:264-280: a training checkpoint holds {"config": ..., "state_dict": ...} plus what
         ModelCheckpointer adds (epoch, global_step, monitor_metric, a `metrics` dict of numpy scalars, optimizer /
         scheduler / grad-scaler state: vad/training/checkpointers/model_checkpointer.py:97-110); the model size, the
@@ -208,7 +220,7 @@ class VADFromScratchPredictor:
         `extended_front_end=True` builds every feature_extractor config features.FrontEnd takes (the four transforms at any
         geometry within its limits, temporal differences); the default refuses all but the shipped one.  The shipped
         features are pinned by goldens and trained-weights AUC, the others by a restatement of librosa 0.8.0: opting in
-        acknowledges that.  `device_ingest`, `device_post`, `batch_chunks`: as in the constructor."""
+        acknowledges that.  `device_ingest`, `device_post`, `batch_chunks`, `batch_front_end`: as in the constructor."""
         ckpt = cls._load_checkpoint(checkpoint_path, trust_checkpoint)
         cfg = ckpt["config"]
 
@@ -255,7 +267,7 @@ class VADFromScratchPredictor:
         ctx = ContextResolution(get(cfg, "context_resolution", "context_window_half_frames"),
                                 get(cfg, "context_resolution", "context_window_jump_frames"))
         predictor = cls(model.to(device).eval(), device, ctx, front_end=front, device_ingest=device_ingest, device_post=device_post,
-                        batch_chunks=batch_chunks)
+                        batch_chunks=batch_chunks, batch_front_end=batch_front_end)
         predictor.hop_ms, predictor.window_ms = hop_ms, window_ms  # vad/predictor.py:103-104
         return predictor
 
@@ -312,10 +324,11 @@ class VADFromScratchPredictor:
     def predict_many(self, audios, parameters: VADPredictParameters, features_fn=None) -> "list[VoiceActivity]":
         """predict() for a LIST of recordings (each as predict takes it) -> their VoiceActivity, in order, through one batched
         prediction: every recording is cut into its `split_max_seconds` chunks (clips.chunk_bounds: predict's own), every chunk's
-        front-end writes its rows of ONE feature matrix (per-chunk launches), the windows of all chunks of all recordings run in one
-        library call (predict_probabilities_many), and each chunk's slice is post-processed as predict does it."""
+        front-end writes its rows of ONE feature matrix (one call for all chunks with `batch_front_end`, else per-chunk launches), the
+        windows of all chunks of all recordings run in one library call (predict_probabilities_many), and each chunk's slice is
+        post-processed as predict does it."""
         from .clips import chunk_bounds, clip_table, split_by_clip
-        from .features import SAMPLE_RATE, log_mel
+        from .features import SAMPLE_RATE, log_mel, log_mel_many
 
         _require_hip(self.device)
         dev = _indexed(self.device)
@@ -332,22 +345,25 @@ class VADFromScratchPredictor:
             for piece in pieces:
                 if len(piece) < 1:
                     raise ValueError("audio must be a non-empty 1-D array")
-            table = clip_table(1 + len(piece) // 160 for piece in pieces)
-            feature = torch.empty((int(table[-1]), self.front_end.feature_size), dtype=torch.float32, device=dev)
-            for piece, rows in zip(pieces, split_by_clip(feature, table)):
-                log_mel(piece, dev, out=rows)
-            results = split_by_clip_pairs(self._predict_matrix(feature, table), table)
+            if self.batch_front_end:
+                feature, table, table_dev = log_mel_many(pieces, dev)
+            else:
+                table, table_dev = clip_table(1 + len(piece) // 160 for piece in pieces), None
+                feature = torch.empty((int(table[-1]), self.front_end.feature_size), dtype=torch.float32, device=dev)
+                for piece, rows in zip(pieces, split_by_clip(feature, table)):
+                    log_mel(piece, dev, out=rows)
+            results = split_by_clip_pairs(self._predict_matrix(feature, table, table_dev), table)
         else:
             results = self.predict_probabilities_many([features_fn(piece) if features_fn is not None else self.features(piece)
                                                        for piece in pieces])
         return [self._voice_activity(adjusted, (results[i][0] for i in indices), parameters) for adjusted, indices in plan]
 
     @torch.no_grad()
-    def _predict_matrix(self, feature, table):
-        """(probs [sum N, W], mean [sum N]) of a concatenated device matrix and its clip table"""
+    def _predict_matrix(self, feature, table, table_dev=None):
+        """(probs [sum N, W], mean [sum N]) of a concatenated device matrix and its clip table (and the table's device copy, if there is one)"""
         self.model.eval()
         return self.model.predict_windows_batch(feature, table, self.context_window_half_frames, self.context_window_jump_frames,
-                                                self.chunk_size)
+                                                self.chunk_size, table_dev)
 
     @torch.no_grad()
     def predict_probabilities_many(self, features) -> "list[tuple]":
