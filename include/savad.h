@@ -456,6 +456,44 @@ int savad_post_sample_class_host(const uint8_t* frames, int n, int sample_rate, 
                                  long count, uint8_t* cls);
 int savad_post_set_block(int elems);
 
+/* The device post-processing for EVERY CLIP OF A BATCH (csrc/savad_post_batch.h): probs [rows, W] of a clip table (clip_first
+ * [C + 1] as above, passed as clip_first_host and clip_first) -> every clip's segments, each clip with the results of
+ * savad_post_frames + savad_post_segments on its rows alone, integer for integer and bit for bit.  The number of launches and of
+ * stream synchronisations does not depend on the number of clips.  Clip boundaries: an edge never exists at a clip's first row,
+ * and the whole-matrix edge scans are clamped to the row's clip (a last edge before it, a first edge at or behind its end: none);
+ * the clips' sample domains lie one after the other as SLOTS -- a clip of n > 0 frames owns its int((n - 1) * hop + window)
+ * samples and one closing slot, a clip without rows owns nothing -- and "voice before this sample" restarts behind every
+ * closing slot.  Sample indices are local to the clip.
+ *   savad_post_batch_supported        HOST arithmetic, 1 or 0: a clip table whose every clip savad_post_supported takes.
+ *   savad_post_batch_slot_table       HOST arithmetic: slot_first [C + 1] (host), the exclusive prefix sum of the clips' slots.
+ *   savad_post_batch_workspace_bytes  HOST arithmetic from the table: one size for _frames and _segments.
+ *   savad_post_batch_frames           DEVICE pointers; boosted [rows], trimmed [rows].  Asynchronous: launches only.
+ *   savad_post_batch_segments         trimmed, boosted, clip_first, ws: DEVICE; everything else HOST.  Returns the segment count of
+ *       the batch; seg_first_host [C + 1]: clip c's segments are [seg_first_host[c], seg_first_host[c + 1]) of starts / ends, of
+ *       which the first `cap` pairs are written.  max_samples > 0: long_host [C] = 1 for the clips that hold a segment longer than
+ *       max_samples (flagged on the device); those clips' pairs come from savad_post_segments (the optimal split) on the clip's
+ *       rows and are spliced in.  max_samples == 0: no split, boosted may be NULL, long_host all 0.  SYNCHRONISES `stream`: at
+ *       most twice when no clip is flagged (counts, then pairs); a flagged clip adds savad_post_segments' own.
+ *   savad_post_batch_frames_host / savad_post_batch_slot_class_host   HOST twins for the CPU tests, running the clip rules the
+ *       kernels run (shared inline functions) in plain loops; the second writes the classes of all slots (0, 1, 2 as
+ *       savad_post_sample_class_host; 3 = a closing slot).
+ * Refused before anything is launched or written: what is not a clip table, negative parameters, a NULL pointer, a workspace
+ * that is short or not 8-byte aligned.  savad_post_set_block governs these scans too.  rows == 0 is a no-op (0 segments). */
+int savad_post_batch_supported(const int32_t* clip_first_host, int C, int W, int sample_rate, double hop_ms, double window_ms);
+int savad_post_batch_slot_table(const int32_t* clip_first_host, int C, int sample_rate, double hop_ms, double window_ms, long* slot_first);
+int savad_post_batch_workspace_bytes(const int32_t* clip_first_host, int C, int W, int sample_rate, double hop_ms, double window_ms,
+                                     size_t* bytes);
+int savad_post_batch_frames(const float* probs, const int32_t* clip_first_host, const int32_t* clip_first, int C, int W, float threshold,
+                            int min_vally, int min_hill, int hang_before, int hang_over, float* boosted, uint8_t* trimmed, void* ws,
+                            size_t ws_bytes, void* stream);
+int savad_post_batch_segments(const uint8_t* trimmed, const float* boosted, const int32_t* clip_first_host, const int32_t* clip_first, int C,
+                              int sample_rate, double hop_ms, double window_ms, long max_samples, long* seg_first_host, uint8_t* long_host,
+                              long* starts, long* ends, int cap, void* ws, size_t ws_bytes, void* stream);
+int savad_post_batch_frames_host(const float* probs, const int32_t* clip_first_host, int C, int W, float threshold, int min_vally,
+                                 int min_hill, int hang_before, int hang_over, float* boosted, uint8_t* trimmed);
+int savad_post_batch_slot_class_host(const uint8_t* frames, const int32_t* clip_first_host, int C, int sample_rate, double hop_ms,
+                                     double window_ms, uint8_t* cls);
+
 /* The metrics of the evaluate command ON THE DEVICE (csrc/savad_eval_device.h).  Every one of the 18 values of a file
  * (vad/evaluate.py:56-80) is a float64 expression of integers -- confusion counts, edge counts, a rank sum and per-boundary hit
  * counts -- so only those integers are computed here and return to the host; metrics.metrics_from_counts turns them into the

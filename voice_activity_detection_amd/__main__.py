@@ -51,6 +51,9 @@ def main(argv=None) -> int:
     p.add_argument("--batch-chunks", action="store_true",
                    help="run the --split-max-seconds chunks of the recording through one batched prediction (one feature matrix, one "
                         "library call for the windows of all chunks) instead of one call per chunk: same results to fp32 rounding")
+    p.add_argument("--batch-post", action="store_true",
+                   help="with --device-post and --batch-chunks: post-process all chunks in one batched pass on the GPU (a fixed number "
+                        "of launches and two synchronisations whatever the number of chunks) instead of one round per chunk: same results")
     e = sub.add_parser("evaluate", help="frame metrics over a labelled data list (vad/evaluate.py:20-29)")
     e.add_argument("eval_path", type=Path)
     e.add_argument("checkpoint_path", type=Path)
@@ -101,7 +104,7 @@ def main(argv=None) -> int:
 
     predictor = VADFromScratchPredictor.from_checkpoint(args.checkpoint_path, args.device, extended_front_end=args.extended_front_end,
                                                         device_ingest=args.device_ingest, device_post=args.device_post,
-                                                        batch_chunks=args.batch_chunks)
+                                                        batch_chunks=args.batch_chunks, batch_post=args.batch_post)
     predictor.model.precision, predictor.model.batch_invariant, predictor.graph = args.precision, args.batch_invariant, args.graph
     voice_activity = predictor.predict_from_path(
         args.audio_path,

@@ -223,6 +223,15 @@ SYMBOLS = {
     "savad_post_frames_host": (c_int, [host(f32), c_int, c_int, c_float, c_int, c_int, c_int, c_int, host(f32), host(u8)]),
     "savad_post_sample_class_host": (c_int, [host(u8), c_int, c_int, c_double, c_double, c_long, c_long, host(u8)]),
     "savad_post_set_block": (c_int, [c_int]),
+    "savad_post_batch_supported": (c_int, [host(i32), c_int, c_int, c_int, c_double, c_double]),
+    "savad_post_batch_slot_table": (c_int, [host(i32), c_int, c_int, c_double, c_double, host(i64)]),
+    "savad_post_batch_workspace_bytes": (c_int, [host(i32), c_int, c_int, c_int, c_double, c_double, _size]),
+    "savad_post_batch_frames": (c_int, [dev(f32), host(i32), dev(i32), c_int, c_int, c_float, c_int, c_int, c_int, c_int, dev(f32), dev(u8), _ws,
+                                        c_size_t, stream]),
+    "savad_post_batch_segments": (c_int, [dev(u8), dev(f32), host(i32), dev(i32), c_int, c_int, c_double, c_double, c_long, host(i64), host(u8),
+                                          host(i64), host(i64), c_int, _ws, c_size_t, stream]),
+    "savad_post_batch_frames_host": (c_int, [host(f32), host(i32), c_int, c_int, c_float, c_int, c_int, c_int, c_int, host(f32), host(u8)]),
+    "savad_post_batch_slot_class_host": (c_int, [host(u8), host(i32), c_int, c_int, c_double, c_double, host(u8)]),
     "savad_eval_supported": (c_int, [c_int, c_long, c_long]),
     "savad_eval_workspace_bytes": (c_int, [c_int, c_int, _size]),
     "savad_eval_counts": (c_long, [dev(f32), c_int, c_int, dev(u8), c_long, c_float, c_int, host(i64), host(u8), c_long, _ws, c_size_t, stream]),

@@ -18,6 +18,7 @@
 #include "savad_ingest.h"
 #include "savad_post.h"
 #include "savad_post_device.h"
+#include "savad_post_batch.h"
 #include "savad_eval_device.h"
 #include "savad_schedule.h"
 #include "savad_weights.h"
@@ -2565,6 +2566,284 @@ SAVAD_EXPORT int savad_post_sample_class_host(const uint8_t* frames, int n, int 
     if (count == 0) return SAVAD_OK;
     if ((n > 0 && !frames) || !cls) return fail(SAVAD_E_INVALID, "null pointer");
     for (long i = 0; i < count; ++i) cls[i] = pd::sample_class(frames, g, first + i);
+    return SAVAD_OK;
+}
+
+// ---- post-processing of every clip of a batch (savad_post_batch.h) ----------------------------------------------------------
+namespace {
+
+struct PostBatchLayout {   // byte offsets into the caller's workspace: host arithmetic from the table
+    size_t row_lo, row_hi, last, next, sums_f, frames_end;                                       // savad_post_batch_frames
+    size_t slot_first, sums_c, cls, state, sums_s, seg_starts, seg_ends, seg_clip, result, single, total;   // savad_post_batch_segments
+    size_t result_bytes, single_bytes;   // result: totals [2] long | clip_total [C] long | flags [C] bytes, fetched in one copy
+    long slots, seg_cap;                 // slots of all clips; room of the segment buffers (without a split a segment needs a frame of its own)
+    int rows, n_max;                     // rows of the table; frames of its longest clip
+};
+
+// the HOST table validated (as the batched prediction does) and measured
+int post_batch_table(const int32_t* clip_first_host, int C, int* rows, int* n_max) {
+    if (!clip_first_host || C < 1) return fail(SAVAD_E_INVALID, "clip table: at least one clip");
+    if (clip_first_host[0] != 0) return fail(SAVAD_E_INVALID, "clip table: clip_first[0] must be 0");
+    int longest = 0;
+    for (int c = 0; c < C; ++c) {
+        const long n = (long)clip_first_host[c + 1] - clip_first_host[c];
+        if (n < 0) return fail(SAVAD_E_INVALID, "clip table: clip_first must not decrease");
+        if (n > longest) longest = (int)n;
+    }
+    *rows = clip_first_host[C];
+    *n_max = longest;
+    return SAVAD_OK;
+}
+
+// geometry: only the frame stage's share is laid out when sample_rate == 0
+PostBatchLayout post_batch_layout(const int32_t* clip_first_host, int C, int rows, int n_max, int sample_rate, double hop_ms, double window_ms) {
+    PostBatchLayout L{};
+    Arena a;
+    const size_t N = (size_t)rows;
+    L.rows = rows, L.n_max = n_max;
+    L.row_lo = a.take(sizeof(int) * N);
+    L.row_hi = a.take(sizeof(int) * N);
+    L.last = a.take(sizeof(int) * N);
+    L.next = a.take(sizeof(int) * N);
+    L.sums_f = a.take(sizeof(int) * (size_t)pd::scan_sums_elems(rows));
+    L.frames_end = a.off;
+    if (sample_rate == 0) return L;
+    for (int c = 0; c < C; ++c) L.slots += pd::clip_slots(clip_first_host[c + 1] - clip_first_host[c], sample_rate, hop_ms, window_ms);
+    L.seg_cap = (long)rows + 2 * (long)C;
+    L.slot_first = a.take(sizeof(long) * ((size_t)C + 1));
+    L.sums_c = a.take(sizeof(long) * (size_t)pd::scan_sums_elems(C));
+    L.cls = a.take((size_t)L.slots);
+    L.state = a.take((size_t)L.slots);
+    L.sums_s = a.take(sizeof(pd::Long2) * (size_t)pd::scan_sums_elems(L.slots));
+    L.seg_starts = a.take(sizeof(long) * (size_t)L.seg_cap);
+    L.seg_ends = a.take(sizeof(long) * (size_t)L.seg_cap);
+    L.seg_clip = a.take(sizeof(int) * (size_t)L.seg_cap);
+    L.result_bytes = sizeof(long) * (2 + (size_t)C) + (size_t)C;
+    L.result = a.take(L.result_bytes);
+    L.single_bytes = post_layout(n_max, pd::make_geometry(n_max, sample_rate, hop_ms, window_ms)).total;   // a flagged clip's savad_post_segments
+    L.single = a.take(L.single_bytes);
+    L.total = a.off;
+    return L;
+}
+
+int post_batch_check_w(int W) {
+    if (W < 1) return fail(SAVAD_E_INVALID, "W = %d", W);
+    if (W > pd::W_MAX) return fail(SAVAD_E_UNSUPPORTED, "W = %d: the device row mean has numpy's order up to %d", W, pd::W_MAX);
+    return SAVAD_OK;
+}
+
+}  // namespace
+
+SAVAD_EXPORT int savad_post_batch_supported(const int32_t* clip_first_host, int C, int W, int sample_rate, double hop_ms, double window_ms) {
+    if (!clip_first_host || C < 1 || clip_first_host[0] != 0) return 0;
+    for (int c = 0; c < C; ++c) {
+        const long n = (long)clip_first_host[c + 1] - clip_first_host[c];
+        if (n < 0 || !savad_post_supported(W, sample_rate, hop_ms, window_ms, (int)n)) return 0;
+    }
+    return 1;
+}
+
+SAVAD_EXPORT int savad_post_batch_slot_table(const int32_t* clip_first_host, int C, int sample_rate, double hop_ms, double window_ms, long* slot_first) {
+    int rc, rows, n_max;
+    if ((rc = post_batch_table(clip_first_host, C, &rows, &n_max))) return rc;
+    if ((rc = post_check_geometry(sample_rate, hop_ms, window_ms, n_max))) return rc;   // (the longest clip's span bounds every other)
+    if (!slot_first) return fail(SAVAD_E_INVALID, "null pointer");
+    pd::slot_table_host(clip_first_host, C, sample_rate, hop_ms, window_ms, slot_first);
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_post_batch_workspace_bytes(const int32_t* clip_first_host, int C, int W, int sample_rate, double hop_ms, double window_ms,
+                                                  size_t* bytes) {
+    int rc, rows, n_max;
+    if (!bytes) return fail(SAVAD_E_INVALID, "null pointer");
+    if ((rc = post_batch_table(clip_first_host, C, &rows, &n_max))) return rc;
+    if ((rc = post_batch_check_w(W))) return rc;
+    if ((rc = post_check_geometry(sample_rate, hop_ms, window_ms, n_max))) return rc;
+    *bytes = post_batch_layout(clip_first_host, C, rows, n_max, sample_rate, hop_ms, window_ms).total;
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_post_batch_frames(const float* probs, const int32_t* clip_first_host, const int32_t* clip_first, int C, int W, float threshold,
+                                         int min_vally, int min_hill, int hang_before, int hang_over, float* boosted, uint8_t* trimmed, void* ws,
+                                         size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc, N, n_max;
+    if ((rc = post_batch_table(clip_first_host, C, &N, &n_max))) return rc;
+    if ((rc = post_batch_check_w(W))) return rc;
+    if ((rc = post_check_trim(min_vally, min_hill, hang_before, hang_over))) return rc;
+    if (N == 0) return SAVAD_OK;
+    if (!probs || !clip_first || !boosted || !trimmed || !ws) return fail(SAVAD_E_INVALID, "null pointer");
+    if ((uintptr_t)ws & 7) return fail(SAVAD_E_INVALID, "workspace must be 8-byte aligned");
+    const PostBatchLayout L = post_batch_layout(clip_first_host, C, N, n_max, 0, 0.0, 0.0);
+    if (ws_bytes < L.frames_end) return fail(SAVAD_E_INVALID, "workspace of %zu bytes, %zu needed", ws_bytes, L.frames_end);
+    char* base = (char*)ws;
+    int* row_lo = (int*)(base + L.row_lo);
+    int* row_hi = (int*)(base + L.row_hi);
+    int* last = (int*)(base + L.last);
+    int* next = (int*)(base + L.next);
+    int* sums = (int*)(base + L.sums_f);
+    const int block = post_block();
+    hipLaunchKernelGGL(pd::frames_batch_kernel, dim3(grid_for(N)), dim3(256), 0, st, probs, clip_first, C, N, W, threshold, boosted, trimmed, row_lo,
+                       row_hi);
+    for (int pass = 0; pass < 3; ++pass) {
+        if ((pass == 0 && min_vally <= 0) || (pass == 1 && min_hill <= 0) || (pass == 2 && hang_before <= 0)) continue;
+        const int k_last = pass == 1 ? 0 : 1, k_next = pass == 1 ? 1 : 0;
+        pd::scan_run<pd::OpMax>(st, N, block, pd::EdgeLoadBatch{trimmed, row_lo, N, k_last, 0}, pd::EdgeStore{last, N, 0}, sums);
+        pd::scan_run<pd::OpMin>(st, N, block, pd::EdgeLoadBatch{trimmed, row_lo, N, k_next, 1}, pd::EdgeStore{next, N, 1}, sums);
+        hipLaunchKernelGGL(pd::trim_apply_batch_kernel, dim3(grid_for(N)), dim3(256), 0, st, trimmed, N, pass, (const int*)last, (const int*)next,
+                           (const int*)row_lo, (const int*)row_hi, min_vally, min_hill, hang_before, hang_over);
+    }
+    HIP_TRY(hipGetLastError());
+    return SAVAD_OK;
+}
+
+// Launches and synchronisations of a batch in which no clip is flagged: one scan of C elements, one launch over the slots, two
+// scans of them, (with max_samples) one memset and one launch over the segments, two synchronisations -- the scans' levels grow
+// with log(slots), nothing with the number of clips.  A flagged clip adds its own savad_post_segments.
+SAVAD_EXPORT int savad_post_batch_segments(const uint8_t* trimmed, const float* boosted, const int32_t* clip_first_host, const int32_t* clip_first,
+                                           int C, int sample_rate, double hop_ms, double window_ms, long max_samples, long* seg_first_host,
+                                           uint8_t* long_host, long* starts, long* ends, int cap, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc, N, n_max;
+    if ((rc = post_batch_table(clip_first_host, C, &N, &n_max))) return rc;
+    if (cap < 0 || max_samples < 0 || max_samples == 1) return fail(SAVAD_E_INVALID, "cap = %d, max_samples = %ld", cap, max_samples);
+    if (!seg_first_host || !long_host || (cap > 0 && (!starts || !ends))) return fail(SAVAD_E_INVALID, "null output");
+    if ((rc = post_check_geometry(sample_rate, hop_ms, window_ms, n_max))) return rc;
+    if (N > 0 && (!trimmed || !clip_first || (max_samples > 0 && !boosted) || !ws)) return fail(SAVAD_E_INVALID, "null pointer");
+    if ((uintptr_t)ws & 7) return fail(SAVAD_E_INVALID, "workspace must be 8-byte aligned");
+    const PostBatchLayout L = post_batch_layout(clip_first_host, C, N, n_max, sample_rate, hop_ms, window_ms);
+    if (N > 0 && ws_bytes < L.total) return fail(SAVAD_E_INVALID, "workspace of %zu bytes, %zu needed", ws_bytes, L.total);
+    for (int c = 0; c <= C; ++c) seg_first_host[c] = 0;
+    for (int c = 0; c < C; ++c) long_host[c] = 0;
+    if (N == 0) return 0;
+    char* base = (char*)ws;
+    long* slot_first = (long*)(base + L.slot_first);
+    uint8_t* cls = (uint8_t*)(base + L.cls);
+    uint8_t* state = (uint8_t*)(base + L.state);
+    pd::Long2* sums = (pd::Long2*)(base + L.sums_s);
+    long* d_starts = (long*)(base + L.seg_starts);
+    long* d_ends = (long*)(base + L.seg_ends);
+    int* d_seg_clip = (int*)(base + L.seg_clip);
+    long* d_totals = (long*)(base + L.result);
+    long* d_clip_total = d_totals + 2;
+    uint8_t* d_flags = (uint8_t*)(d_clip_total + C);
+    const int block = post_block();
+
+    pd::scan_run<pd::OpSumL>(st, C, block, pd::SlotCountLoad{clip_first, sample_rate, hop_ms, window_ms}, pd::SlotFirstStore{slot_first},
+                             (long*)(base + L.sums_c));
+    hipLaunchKernelGGL(pd::slot_class_kernel, dim3(grid_for(L.slots)), dim3(256), 0, st, trimmed, clip_first, (const long*)slot_first, C, L.slots,
+                       sample_rate, hop_ms, window_ms, cls);
+    pd::scan_run<pd::OpLast>(st, L.slots, block, pd::ClassLoadBatch{cls}, pd::ClassStore{state}, (int*)sums);
+    const pd::FlagLoadBatch flags{cls, state};
+    pd::scan_run<pd::OpSum2>(st, L.slots, block, flags,
+                             pd::SegmentStoreBatch{flags, slot_first, C, L.slots, d_starts, d_ends, d_seg_clip, L.seg_cap, d_clip_total, d_totals}, sums);
+    if (max_samples > 0) {
+        HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)C, st));
+        hipLaunchKernelGGL(pd::long_flag_kernel, dim3(grid_for(L.seg_cap)), dim3(256), 0, st, (const long*)d_starts, (const long*)d_ends,
+                           (const int*)d_seg_clip, (const long*)d_totals, L.seg_cap, max_samples, d_flags);
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<char> result(L.result_bytes);
+    HIP_TRY(hipMemcpyAsync(result.data(), d_totals, max_samples > 0 ? L.result_bytes : L.result_bytes - (size_t)C, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the first of two
+    long tot[2];
+    memcpy(tot, result.data(), sizeof(tot));
+    if (tot[0] != tot[1]) return fail(SAVAD_E_STATE, "%ld starts and %ld ends", tot[0], tot[1]);
+    if (tot[0] > L.seg_cap) return fail(SAVAD_E_STATE, "%ld segments in %d frames of %d clips", tot[0], N, C);
+    if (tot[0] > INT_MAX) return fail(SAVAD_E_UNSUPPORTED, "%ld segments", tot[0]);
+    bool any_long = false;
+    for (int c = 0; c < C; ++c) {   // a clip without rows has no closing slot: it ends where the clip before it ends
+        long upto = seg_first_host[c];
+        if (clip_first_host[c + 1] > clip_first_host[c]) memcpy(&upto, result.data() + sizeof(long) * (2 + (size_t)c), sizeof(long));
+        seg_first_host[c + 1] = upto;
+        if (max_samples > 0) long_host[c] = (uint8_t)result[sizeof(long) * (2 + (size_t)C) + (size_t)c];
+        any_long = any_long || long_host[c];
+    }
+    const long count = tot[0];
+    if (!any_long) {
+        const size_t want = (size_t)(count < cap ? count : cap);
+        if (want) {
+            HIP_TRY(hipMemcpyAsync(starts, d_starts, sizeof(long) * want, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(ends, d_ends, sizeof(long) * want, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));   // the second
+        }
+        return (int)count;
+    }
+    // some clip holds an over-long segment: the optimal split stays the single-clip routine, run on that clip's slice; every
+    // other clip keeps the pairs of the batch
+    std::vector<long> bs((size_t)count), be((size_t)count), os, oe, one_s, one_e;
+    if (count) {
+        HIP_TRY(hipMemcpyAsync(bs.data(), d_starts, sizeof(long) * (size_t)count, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(be.data(), d_ends, sizeof(long) * (size_t)count, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    long before = 0;   // seg_first_host[c] of the batch pass, before the entry is rewritten
+    for (int c = 0; c < C; ++c) {
+        const long upto = seg_first_host[c + 1];
+        if (!long_host[c]) {
+            os.insert(os.end(), bs.begin() + before, bs.begin() + upto);
+            oe.insert(oe.end(), be.begin() + before, be.begin() + upto);
+        } else {
+            const int lo = clip_first_host[c], n = clip_first_host[c + 1] - lo;
+            int one_cap = n + 2;
+            for (;;) {
+                one_s.resize((size_t)one_cap), one_e.resize((size_t)one_cap);
+                const int got = savad_post_segments(trimmed + lo, boosted + lo, n, sample_rate, hop_ms, window_ms, max_samples, one_s.data(),
+                                                    one_e.data(), one_cap, base + L.single, L.single_bytes, stream);
+                if (got < 0) return got;
+                if (got <= one_cap) {
+                    one_cap = got;
+                    break;
+                }
+                one_cap = got;   // (a split into more pieces than frames)
+            }
+            os.insert(os.end(), one_s.begin(), one_s.begin() + one_cap);
+            oe.insert(oe.end(), one_e.begin(), one_e.begin() + one_cap);
+        }
+        before = upto;
+        if (os.size() > (size_t)INT_MAX) return fail(SAVAD_E_UNSUPPORTED, "%zu segments", os.size());
+        seg_first_host[c + 1] = (long)os.size();
+    }
+    const size_t want = os.size() < (size_t)cap ? os.size() : (size_t)cap;
+    if (want) {
+        memcpy(starts, os.data(), sizeof(long) * want);
+        memcpy(ends, oe.data(), sizeof(long) * want);
+    }
+    return (int)os.size();
+}
+
+SAVAD_EXPORT int savad_post_batch_frames_host(const float* probs, const int32_t* clip_first_host, int C, int W, float threshold, int min_vally,
+                                              int min_hill, int hang_before, int hang_over, float* boosted, uint8_t* trimmed) {
+    int rc, N, n_max;
+    if ((rc = post_batch_table(clip_first_host, C, &N, &n_max))) return rc;
+    if ((rc = post_batch_check_w(W))) return rc;
+    if ((rc = post_check_trim(min_vally, min_hill, hang_before, hang_over))) return rc;
+    if (N == 0) return SAVAD_OK;
+    if (!probs || !boosted || !trimmed) return fail(SAVAD_E_INVALID, "null pointer");
+    for (int i = 0; i < N; ++i) {
+        boosted[i] = pd::row_mean(probs + (size_t)i * W, W);
+        trimmed[i] = pd::above(boosted[i], threshold);
+    }
+    std::vector<int> row_lo((size_t)N), row_hi((size_t)N), last((size_t)N), next((size_t)N);
+    pd::clip_bounds_host(clip_first_host, C, N, row_lo.data(), row_hi.data());
+    pd::trim_batch_host(trimmed, N, row_lo.data(), row_hi.data(), min_vally, min_hill, hang_before, hang_over, last.data(), next.data());
+    return SAVAD_OK;
+}
+
+SAVAD_EXPORT int savad_post_batch_slot_class_host(const uint8_t* frames, const int32_t* clip_first_host, int C, int sample_rate, double hop_ms,
+                                                  double window_ms, uint8_t* cls) {
+    int rc, N, n_max;
+    if ((rc = post_batch_table(clip_first_host, C, &N, &n_max))) return rc;
+    if ((rc = post_check_geometry(sample_rate, hop_ms, window_ms, n_max))) return rc;
+    if (N == 0) return SAVAD_OK;
+    if (!frames || !cls) return fail(SAVAD_E_INVALID, "null pointer");
+    std::vector<long> slot_first((size_t)C + 1);
+    pd::slot_table_host(clip_first_host, C, sample_rate, hop_ms, window_ms, slot_first.data());
+    for (long j = 0; j < slot_first[(size_t)C]; ++j) {
+        const int c = pd::clip_of(slot_first.data(), C, j);
+        const int lo = clip_first_host[c];
+        cls[j] = pd::slot_class(frames + lo, clip_first_host[c + 1] - lo, j - slot_first[(size_t)c], sample_rate, hop_ms, window_ms);
+    }
     return SAVAD_OK;
 }
 

@@ -115,7 +115,7 @@ class VADFromScratchPredictor:
     def __init__(self, model: SelfAttentiveVAD, device: torch.device, context: ContextResolution = ContextResolution(),
                  chunk_size: int = 16384, graph: bool = False, graph_max_seconds: float = 120.0, graph_cache: int = 8,
                  front_end=None, device_ingest: bool = False, device_post: bool = False, batch_chunks: bool = False,
-                 batch_front_end: bool = BATCH_FRONT_END_DEFAULT):
+                 batch_front_end: bool = BATCH_FRONT_END_DEFAULT, batch_post: bool = False):
         """`graph=True` (not in the reference's signature): clip-sized inputs -- up to `graph_max_seconds` of audio -- run as a
         replayed HIP graph of the whole chain log-mel -> window gather -> forward -> boost, captured on first use per (length, model
         knobs) and re-captured when the weights change; at most `graph_cache` graphs are kept (least recently used goes).  For a 10 s
@@ -139,7 +139,13 @@ class VADFromScratchPredictor:
         `batch_front_end`: predict_many (and with it the `batch_chunks` path of predict) computes the features of all chunks in ONE
         front-end call on the clip table (features.log_mel_many: three launches and one upload whatever the number of chunks) and
         hands its device row table on to the batched prediction, instead of one log_mel call per chunk; the same bits either way.
-        A custom features_fn and the extended front-ends keep the per-chunk calls.  On by default (measured: DESIGN.md section 4o)."""
+        A custom features_fn and the extended front-ends keep the per-chunk calls.  On by default (measured: DESIGN.md section 4o).
+        `batch_post=True` (with `device_post`): predict_many (and the `batch_chunks` path of predict) post-processes ALL chunks through
+        one batched call (postprocessing.post_frames_device_many / segments_device_many: a fixed number of launches and two stream
+        synchronisations whatever the number of chunks) instead of one `device_post` round per chunk; the same activities, integer
+        for integer.  Chunks with a segment above `activity_max_seconds` go through the per-chunk split; `return_probs` stays per
+        chunk.  Where the device post-processing would refuse any chunk, the per-chunk loop runs as without the flag.
+        `post_batch_stats` counts the batched calls, their chunks and the chunks that were split.  Off by default."""
         from .features import SHIPPED_FRONT_END
 
         self.front_end = SHIPPED_FRONT_END if front_end is None else front_end
@@ -147,6 +153,9 @@ class VADFromScratchPredictor:
         self.device_post = bool(device_post)
         self.batch_chunks = bool(batch_chunks)
         self.batch_front_end = bool(batch_front_end)
+        self.batch_post = bool(batch_post)
+        # batched post-processing: calls, the chunks they took, the chunks that went through the split (and which of the last call)
+        self.post_batch_stats = {"calls": 0, "clips": 0, "split": 0, "last_split": []}
         self.post_stats = {"device": 0, "host": 0}   # chunks post-processed on the GPU / on the host
         self.graph, self.graph_max_seconds, self.graph_cache = bool(graph), float(graph_max_seconds), int(graph_cache)
         self._graphs: "OrderedDict[tuple, dict]" = OrderedDict()
@@ -211,7 +220,7 @@ class VADFromScratchPredictor:
     @classmethod
     def from_checkpoint(cls, checkpoint_path, device, trust_checkpoint: bool = False, extended_front_end: bool = False,
                         device_ingest: bool = False, device_post: bool = False, batch_chunks: bool = False,
-                        batch_front_end: bool = BATCH_FRONT_END_DEFAULT):
+                        batch_front_end: bool = BATCH_FRONT_END_DEFAULT, batch_post: bool = False):
         """vad/predictor.py:264-280: a training checkpoint holds {"config": ..., "state_dict": ...} plus what
         ModelCheckpointer adds (epoch, global_step, monitor_metric, a `metrics` dict of numpy scalars, optimizer /
         scheduler / grad-scaler state: vad/training/checkpointers/model_checkpointer.py:97-110); the model size, the
@@ -220,7 +229,7 @@ class VADFromScratchPredictor:
         `extended_front_end=True` builds every feature_extractor config features.FrontEnd takes (the four transforms at any
         geometry within its limits, temporal differences); the default refuses all but the shipped one.  The shipped
         features are pinned by goldens and trained-weights AUC, the others by a restatement of librosa 0.8.0: opting in
-        acknowledges that.  `device_ingest`, `device_post`, `batch_chunks`, `batch_front_end`: as in the constructor."""
+        acknowledges that.  `device_ingest`, `device_post`, `batch_chunks`, `batch_front_end`, `batch_post`: as in the constructor."""
         ckpt = cls._load_checkpoint(checkpoint_path, trust_checkpoint)
         cfg = ckpt["config"]
 
@@ -267,7 +276,7 @@ class VADFromScratchPredictor:
         ctx = ContextResolution(get(cfg, "context_resolution", "context_window_half_frames"),
                                 get(cfg, "context_resolution", "context_window_jump_frames"))
         predictor = cls(model.to(device).eval(), device, ctx, front_end=front, device_ingest=device_ingest, device_post=device_post,
-                        batch_chunks=batch_chunks, batch_front_end=batch_front_end)
+                        batch_chunks=batch_chunks, batch_front_end=batch_front_end, batch_post=batch_post)
         predictor.hop_ms, predictor.window_ms = hop_ms, window_ms  # vad/predictor.py:103-104
         return predictor
 
@@ -301,13 +310,12 @@ class VADFromScratchPredictor:
                 else:
                     yield self.predict_audio_device(chunk)[0]   # (a replayed HIP graph for clip-sized chunks when graph=True)
 
-        return self._voice_activity(adjusted, chunk_probs(), parameters)
+        return self._voice_activity(adjusted, (self._post(probs_dev, parameters) for probs_dev in chunk_probs()), parameters)
 
-    def _voice_activity(self, adjusted, chunk_probs, parameters: VADPredictParameters) -> VoiceActivity:
-        """a recording's VoiceActivity from the probabilities of its chunks, each post-processed as it arrives (vad/predictor.py:120-157)"""
+    def _voice_activity(self, adjusted, posted, parameters: VADPredictParameters) -> VoiceActivity:
+        """a recording's VoiceActivity from the post-processed (activities, probs) of its chunks, taken as they arrive (vad/predictor.py:120-157)"""
         chunks = []
-        for probs_dev in chunk_probs:
-            activities, probs = self._post(probs_dev, parameters)
+        for activities, probs in posted:
             chunks.append(VoiceActivity(duration=timedelta(seconds=adjusted), activities=activities,
                                         probs_sample_rate=parameters.probs_sample_rate if parameters.return_probs else None,
                                         probs=probs))
@@ -326,7 +334,7 @@ class VADFromScratchPredictor:
         prediction: every recording is cut into its `split_max_seconds` chunks (clips.chunk_bounds: predict's own), every chunk's
         front-end writes its rows of ONE feature matrix (one call for all chunks with `batch_front_end`, else per-chunk launches), the
         windows of all chunks of all recordings run in one library call (predict_probabilities_many), and each chunk's slice is
-        post-processed as predict does it."""
+        post-processed as predict does it -- chunk by chunk, or with `batch_post` (and `device_post`) all chunks in one batched call."""
         from .clips import chunk_bounds, clip_table, split_by_clip
         from .features import SAMPLE_RATE, log_mel, log_mel_many
 
@@ -352,11 +360,24 @@ class VADFromScratchPredictor:
                 feature = torch.empty((int(table[-1]), self.front_end.feature_size), dtype=torch.float32, device=dev)
                 for piece, rows in zip(pieces, split_by_clip(feature, table)):
                     log_mel(piece, dev, out=rows)
-            results = split_by_clip_pairs(self._predict_matrix(feature, table, table_dev), table)
+            probs_all = self._predict_matrix(feature, table, table_dev)[0]
         else:
-            results = self.predict_probabilities_many([features_fn(piece) if features_fn is not None else self.features(piece)
-                                                       for piece in pieces])
-        return [self._voice_activity(adjusted, (results[i][0] for i in indices), parameters) for adjusted, indices in plan]
+            (probs_all, _), table = self._probabilities_matrix([features_fn(piece) if features_fn is not None else self.features(piece)
+                                                                for piece in pieces])
+            table_dev = None
+        return self._voice_activities(probs_all, table, table_dev, plan, parameters)
+
+    def _voice_activities(self, probs_all, table, table_dev, plan, parameters: VADPredictParameters) -> "list[VoiceActivity]":
+        """the probabilities [sum N, W] of all chunks -> one VoiceActivity per recording of `plan` [(seconds per chunk, its chunks'
+        indices)]: every chunk post-processed on its own, or (`batch_post` with `device_post`, where the device takes every chunk)
+        all of them in one batched call"""
+        from .clips import split_by_clip
+
+        chunk_probs = split_by_clip(probs_all, table)
+        if self.batch_post and self.device_post and all(self._device_post_applies(p, parameters) for p in chunk_probs):
+            posted = self._post_device_many(probs_all, table, table_dev, parameters)
+            return [self._voice_activity(adjusted, (posted[i] for i in indices), parameters) for adjusted, indices in plan]
+        return [self._voice_activity(adjusted, (self._post(chunk_probs[i], parameters) for i in indices), parameters) for adjusted, indices in plan]
 
     @torch.no_grad()
     def _predict_matrix(self, feature, table, table_dev=None):
@@ -369,19 +390,26 @@ class VADFromScratchPredictor:
     def predict_probabilities_many(self, features) -> "list[tuple]":
         """predict_probabilities_device for a LIST of [N_c, F] feature matrices (numpy or tensor; an empty one is legal) in one
         library call -> [(probs [N_c, W], mean [N_c])] on the device: views of one result, clip by clip."""
+        feats = list(features)
+        if not feats:
+            return []
+        result, table = self._probabilities_matrix(feats)
+        return split_by_clip_pairs(result, table)
+
+    @torch.no_grad()
+    def _probabilities_matrix(self, features):
+        """((probs [sum N, W], mean [sum N]), clip table) of a non-empty list of [N_c, F] feature matrices: one library call"""
         from .clips import clip_table
 
         _require_hip(self.device)
         dev = _indexed(self.device)
         feats = [torch.as_tensor(f, dtype=torch.float32).to(dev) for f in features]
-        if not feats:
-            return []
         for f in feats:
             if f.dim() != 2 or f.shape[1] != self.model.feature_size:
                 raise ValueError(f"every feature matrix must be [N, {self.model.feature_size}], got {tuple(f.shape)}")
         table = clip_table(f.shape[0] for f in feats)
         feature = feats[0].contiguous() if len(feats) == 1 else torch.cat(feats, dim=0)
-        return split_by_clip_pairs(self._predict_matrix(feature, table), table)
+        return self._predict_matrix(feature, table), table
 
     def _post_host(self, probs_dev, parameters: VADPredictParameters):
         """probs [N, W] on the device -> (activities, probs list or None) on the host: vad/predictor.py:95-141"""
@@ -424,16 +452,46 @@ class VADFromScratchPredictor:
 
     def _post_device(self, probs_dev, parameters: VADPredictParameters):
         """_post_host's results from the GPU: only the segment indices (and the probability samples, when asked for) come back"""
-        from .postprocessing import post_frames_device, sample_probs_device, segments_device
+        from .postprocessing import post_frames_device, segments_device
 
         hop_ms, window_ms = self.hop_ms, self.window_ms
-        boosted, trimmed = post_frames_device(probs_dev, parameters.threshold, min_vally=round(parameters.min_vally_ms / hop_ms),
-                                              min_hill=round(parameters.min_hill_ms / hop_ms),
-                                              hang_before=round(parameters.hang_before_ms / hop_ms),
-                                              hang_over=round(parameters.hang_over_ms / hop_ms))
+        boosted, trimmed = post_frames_device(probs_dev, parameters.threshold, **self._trim_frames(parameters))
         amax = parameters.activity_max_seconds
         starts, ends = segments_device(trimmed, boosted, sample_rate=16000, hop_ms=hop_ms, window_ms=window_ms,
                                        max_length_seconds=amax if amax is not None and amax > 0 else None)
+        return self._device_result(starts, ends, boosted, parameters)
+
+    def _trim_frames(self, parameters: VADPredictParameters) -> dict:
+        """the trim parameters in frames (vad/predictor.py:99-104)"""
+        hop_ms = self.hop_ms
+        return dict(min_vally=round(parameters.min_vally_ms / hop_ms), min_hill=round(parameters.min_hill_ms / hop_ms),
+                    hang_before=round(parameters.hang_before_ms / hop_ms), hang_over=round(parameters.hang_over_ms / hop_ms))
+
+    def _post_device_many(self, probs_all, table, table_dev, parameters: VADPredictParameters) -> list:
+        """_post_device for every chunk of a batch through ONE batched call: [(activities, probs)] in chunk order"""
+        from .clips import split_by_clip
+        from .postprocessing import post_frames_device_many, segments_device_many
+
+        hop_ms, window_ms = self.hop_ms, self.window_ms
+        boosted, trimmed = post_frames_device_many(probs_all, table, table_dev, parameters.threshold, **self._trim_frames(parameters))
+        amax = parameters.activity_max_seconds
+        seg_first, starts, ends, split = segments_device_many(trimmed, table, table_dev, boosted, sample_rate=16000, hop_ms=hop_ms, window_ms=window_ms,
+                                                              max_length_seconds=amax if amax is not None and amax > 0 else None, return_long=True)
+        chunks = len(table) - 1
+        self.post_stats["device"] += chunks
+        stats = self.post_batch_stats
+        stats["calls"] += 1
+        stats["clips"] += chunks
+        stats["last_split"] = [int(c) for c in np.flatnonzero(split)]
+        stats["split"] += len(stats["last_split"])
+        return [self._device_result(starts[a:b], ends[a:b], rows, parameters)
+                for a, b, rows in zip(seg_first[:-1], seg_first[1:], split_by_clip(boosted, table))]
+
+    def _device_result(self, starts, ends, boosted, parameters: VADPredictParameters):
+        """(activities, probs) of a chunk from its segments' sample indices and its boosted probabilities on the device"""
+        from .postprocessing import sample_probs_device
+
+        hop_ms, window_ms = self.hop_ms, self.window_ms
         # (times as convert_samples_to_segments builds them)
         activities = [Activity(start=timedelta(seconds=int(a) / 16000), end=timedelta(seconds=int(b) / 16000)) for a, b in zip(starts, ends)]
         probs = None
