@@ -539,6 +539,36 @@ long savad_eval_counts_host(const float* probs, int N, int W, const uint8_t* lab
                             long* counters, uint8_t* seg, long seg_cap);
 int savad_eval_set_block(int elems);
 
+/* The same metrics for EVERY CLIP OF A BATCH in one call (csrc/savad_eval_batch.h).  probs [rows, W] with the row clip table
+ * clip_first [C + 1] of the batched prediction; ONE concatenated labels array with a table of its own, label_first [C + 1] (a
+ * file's label count is not its row count); both tables as HOST and DEVICE copies holding the same values.  Clip c works on
+ * n_c = min(rows_c, labels_c) frames and gets what savad_eval_counts returns for that clip alone -- nothing looks across a clip
+ * boundary: edges, boundary windows, tie groups, "negatives before", _NAN and _BAD_LABEL are the clip's own.
+ *   counters [C][SAVAD_EVAL_COUNTERS] (int64, HOST): clip c's block, SAVAD_EVAL_N = n_c included.
+ *   seg [count x 8] (uint8, HOST): the boundary records in clip order, then segment order; clip c's are records
+ *       seg_first_host[c] .. seg_first_host[c + 1] (seg_first_host [C + 1], HOST, written by the call).
+ *   A clip with n_c = 0 is legal: zero counters, no records.  C = 1 gives the results of savad_eval_counts.
+ *   savad_eval_batch_supported        HOST arithmetic, 1 or 0: C >= 1, both tables start at 0 and do not decrease, 1 <= W <= 128,
+ *                                     fewer than 2^31 frames in all.
+ *   savad_eval_batch_workspace_bytes  HOST arithmetic from the two host tables; the same at every savad_eval_set_block.
+ *   savad_eval_batch_counts           probs, labels, the device tables, workspace (8-byte aligned): DEVICE.  Returns the batch's
+ *                                     true-segment count, or a negative code.  Refused before anything is launched or written:
+ *                                     C < 1, a table that does not start at 0 or decreases, W outside 1 .. 128, L outside
+ *                                     1 .. 254, 2^31 frames or more, a NULL pointer, a short or misaligned workspace.  seg_cap
+ *                                     below the count is SAVAD_E_INVALID once the counters are known (they are returned).  The
+ *                                     number of launches does not depend on C; SYNCHRONISES `stream` at most twice (counters,
+ *                                     then records).  No allocation.
+ *   savad_eval_batch_counts_host      HOST twin for the CPU tests: evaldev::counts_host on every clip's slice, in a plain loop.
+ * savad_eval_set_block governs the scans and sort blocks of the batch too (a sort block never spans two clips). */
+int savad_eval_batch_supported(const int32_t* clip_first_host, const int32_t* label_first_host, int C, int W);
+int savad_eval_batch_workspace_bytes(const int32_t* clip_first_host, const int32_t* label_first_host, int C, int W, size_t* bytes);
+long savad_eval_batch_counts(const float* probs, const int32_t* clip_first_host, const int32_t* clip_first, const uint8_t* labels,
+                             const int32_t* label_first_host, const int32_t* label_first, int C, int W, float threshold, int L,
+                             long* counters, uint8_t* seg, long seg_cap, long* seg_first_host, void* ws, size_t ws_bytes, void* stream);
+long savad_eval_batch_counts_host(const float* probs, const int32_t* clip_first_host, const uint8_t* labels,
+                                  const int32_t* label_first_host, int C, int W, float threshold, int L, long* counters, uint8_t* seg,
+                                  long seg_cap, long* seg_first_host);
+
 /* LIVE SESSIONS: audio fed as it arrives, many streams per tick (csrc/savad_live_plan.h, csrc/savad_live.h).  The rows a stream's
  * ticks and its finish emit, concatenated, are savad_logmel + savad_predict_probabilities of the finished recording, row for row,
  * however the recording was cut into pushes.  Shipped front-end only (16 kHz mono).  After n samples of an open stream

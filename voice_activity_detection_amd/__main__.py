@@ -73,6 +73,9 @@ def main(argv=None) -> int:
     e.add_argument("--device-metrics", action="store_true",
                    help="compute a file's metrics on the GPU (same values; the labels go up and a few hundred bytes come back instead "
                         "of the probability matrix going down): pays for long recordings, a short clip is launch-bound")
+    e.add_argument("--batch-files", type=int, default=0, metavar="K",
+                   help="with --device-metrics: groups of K files of the list go through one front-end call, one batched prediction and "
+                        "one metrics call (same values; the launches of a group do not grow with K)")
     e.add_argument("--precision", choices=("fp32", "fp32s", "bf16"), default="fp32", help="as for predict")
     lv = sub.add_parser("live", help="one 16 kHz WAV file fed through a live session: an event line as soon as it is final, then "
                                      "predict's JSON")
@@ -94,7 +97,8 @@ def main(argv=None) -> int:
 
         evaluate_vad_from_scratch(args.eval_path, args.checkpoint_path, args.output_path, args.data_dir, args.threshold,
                                   args.shuffle, args.limit, args.random_seed, args.device, extended_front_end=args.extended_front_end,
-                                  device_ingest=args.device_ingest, device_metrics=args.device_metrics, precision=args.precision)
+                                  device_ingest=args.device_ingest, device_metrics=args.device_metrics, precision=args.precision,
+                                  batch_files=args.batch_files)
         return 0
 
     if args.command == "live":

@@ -238,6 +238,12 @@ SYMBOLS = {
     "savad_eval_sort": (c_int, [dev(f32), dev(u8), c_long, dev(f32), dev(u8), _ws, c_size_t, stream]),
     "savad_eval_counts_host": (c_long, [host(f32), c_int, c_int, host(u8), c_long, c_float, c_int, host(i64), host(u8), c_long]),
     "savad_eval_set_block": (c_int, [c_int]),
+    "savad_eval_batch_supported": (c_int, [host(i32), host(i32), c_int, c_int]),
+    "savad_eval_batch_workspace_bytes": (c_int, [host(i32), host(i32), c_int, c_int, _size]),
+    "savad_eval_batch_counts": (c_long, [dev(f32), host(i32), dev(i32), dev(u8), host(i32), dev(i32), c_int, c_int, c_float, c_int, host(i64), host(u8),
+                                         c_long, host(i64), _ws, c_size_t, stream]),
+    "savad_eval_batch_counts_host": (c_long, [host(f32), host(i32), host(u8), host(i32), c_int, c_int, c_float, c_int, host(i64), host(u8), c_long,
+                                              host(i64)]),
     "savad_live_ready_frames": (c_long, [c_long]),
     "savad_live_final_rows": (c_long, [c_long, c_int]),
     "savad_live_state_bytes": (c_int, [_live, _size]),

@@ -20,6 +20,7 @@
 #include "savad_post_device.h"
 #include "savad_post_batch.h"
 #include "savad_eval_device.h"
+#include "savad_eval_batch.h"
 #include "savad_schedule.h"
 #include "savad_weights.h"
 #include "savad_live.h"
@@ -2989,6 +2990,170 @@ SAVAD_EXPORT long savad_eval_counts_host(const float* probs, int N, int W, const
     if (!probs || !labels || !counters || seg_cap < 0 || (seg_cap > 0 && !seg)) return fail(SAVAD_E_INVALID, "null pointer");
     const int n = (int)eval_frames(N, n_labels);
     const long n_true = ed::counts_host(probs, W, labels, n, threshold, L, counters, seg, seg_cap);
+    if (n_true > seg_cap) return fail(SAVAD_E_INVALID, "%ld true segments, room for %ld", n_true, seg_cap);
+    return n_true;
+}
+
+// ---- evaluate's metrics for every clip of a batch (savad_eval_batch.h) ---------------------------------------------------------
+namespace {
+
+namespace eb = savad::evalbatch;
+
+struct EvalBatchLayout {   // byte offsets into the caller's workspace: host arithmetic from the two tables
+    size_t elem_first, block_first, sums_c, elem_clip, keys_a, keys_b, y, labels_a, labels_b, spred, bpred, table, sums, scan, seg, counters, total;
+    long E, seg_cap;       // frames of all clips; records of the boundary buffer (a true segment needs a frame of its own and a gap, per clip)
+};
+
+// both HOST tables validated: the refusal's message, or null.  *E = the frames of all clips
+const char* eval_batch_tables(const int32_t* clip_first_host, const int32_t* label_first_host, int C, long* E) {
+    if (!clip_first_host || !label_first_host) return "null table";
+    if (C < 1) return "at least one clip";
+    if (clip_first_host[0] != 0 || label_first_host[0] != 0) return "clip_first[0] and label_first[0] must be 0";
+    long total = 0;
+    for (int c = 0; c < C; ++c) {
+        if (clip_first_host[c + 1] < clip_first_host[c] || label_first_host[c + 1] < label_first_host[c]) return "a table must not decrease";
+        total += eb::clip_frames(clip_first_host, label_first_host, c);
+    }
+    if (total >= 2147483648L) return "2^31 frames or more";
+    *E = total;
+    return nullptr;
+}
+
+EvalBatchLayout eval_batch_layout(const int32_t* clip_first_host, const int32_t* label_first_host, int C, long E) {
+    EvalBatchLayout L;
+    Arena a;
+    const size_t n = (size_t)E;
+    L.E = E;
+    L.elem_first = a.take(sizeof(long) * ((size_t)C + 1));
+    L.block_first = a.take(sizeof(long) * ((size_t)C + 1));
+    L.sums_c = a.take(sizeof(pd::Long2) * (size_t)pd::scan_sums_elems(C));
+    L.elem_clip = a.take(sizeof(int) * n);
+    L.keys_a = a.take(sizeof(uint32_t) * n);
+    L.keys_b = a.take(sizeof(uint32_t) * n);
+    L.y = a.take(n);
+    L.labels_a = a.take(n);
+    L.labels_b = a.take(n);
+    L.spred = a.take(n);
+    L.bpred = a.take(n);
+    const long table = eb::sort_table_elems(clip_first_host, label_first_host, C);
+    L.table = a.take(sizeof(unsigned) * (size_t)table);
+    const size_t sums_sort = sizeof(unsigned) * (size_t)pd::scan_sums_elems(table);
+    const size_t sums_frames = sizeof(pd::Long2) * (size_t)pd::scan_sums_elems(E);   // (Long2 is the larger of the two frame scans' types)
+    L.sums = a.take(sums_sort > sums_frames ? sums_sort : sums_frames);
+    L.scan = a.take(sizeof(ed::HeadNeg) * n);
+    L.seg_cap = 0;
+    for (int c = 0; c < C; ++c) L.seg_cap += (eb::clip_frames(clip_first_host, label_first_host, c) + 1) / 2;
+    L.seg = a.take((size_t)ed::SEG_BYTES * (size_t)L.seg_cap);
+    L.counters = a.take(sizeof(long) * ed::COUNTERS * (size_t)C);
+    L.total = a.off;
+    return L;
+}
+
+// the arguments both forms of the call share
+int eval_batch_check(const int32_t* clip_first_host, const int32_t* label_first_host, int C, int W, int L, long* E) {
+    if (const char* why = eval_batch_tables(clip_first_host, label_first_host, C, E)) return fail(SAVAD_E_INVALID, "clip tables: %s", why);
+    if (W < 1) return fail(SAVAD_E_INVALID, "W = %d", W);
+    if (W > pd::W_MAX) return fail(SAVAD_E_UNSUPPORTED, "W = %d: the device row mean has numpy's order up to %d", W, pd::W_MAX);
+    if (L < 1 || L > ed::L_MAX) return fail(SAVAD_E_INVALID, "L = %d (1 .. %d)", L, ed::L_MAX);
+    return SAVAD_OK;
+}
+
+}  // namespace
+
+SAVAD_EXPORT int savad_eval_batch_supported(const int32_t* clip_first_host, const int32_t* label_first_host, int C, int W) {
+    long E;
+    return !eval_batch_tables(clip_first_host, label_first_host, C, &E) && W >= 1 && W <= pd::W_MAX ? 1 : 0;
+}
+
+SAVAD_EXPORT int savad_eval_batch_workspace_bytes(const int32_t* clip_first_host, const int32_t* label_first_host, int C, int W, size_t* bytes) {
+    int rc;
+    long E;
+    if (!bytes) return fail(SAVAD_E_INVALID, "null pointer");
+    if ((rc = eval_batch_check(clip_first_host, label_first_host, C, W, 1, &E))) return rc;
+    *bytes = eval_batch_layout(clip_first_host, label_first_host, C, E).total;
+    return SAVAD_OK;
+}
+
+// Launches and synchronisations: one memset, one scan of C elements, two launches over the frames, two scans of them, four sort
+// passes (histogram, scan of the digit table, scatter), one launch for the rank sum, two synchronisations -- the scans' levels
+// grow with the logarithm of their lengths, nothing with the number of clips.
+SAVAD_EXPORT long savad_eval_batch_counts(const float* probs, const int32_t* clip_first_host, const int32_t* clip_first, const uint8_t* labels,
+                                          const int32_t* label_first_host, const int32_t* label_first, int C, int W, float threshold, int L,
+                                          long* counters, uint8_t* seg, long seg_cap, long* seg_first_host, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    long E;
+    if ((rc = eval_batch_check(clip_first_host, label_first_host, C, W, L, &E))) return rc;
+    if (!probs || !clip_first || !labels || !label_first || !counters || !seg_first_host || !ws || seg_cap < 0 || (seg_cap > 0 && !seg))
+        return fail(SAVAD_E_INVALID, "null pointer");
+    if ((uintptr_t)ws & 7) return fail(SAVAD_E_INVALID, "workspace must be 8-byte aligned");
+    const EvalBatchLayout Y = eval_batch_layout(clip_first_host, label_first_host, C, E);
+    if (ws_bytes < Y.total) return fail(SAVAD_E_INVALID, "workspace of %zu bytes, %zu needed", ws_bytes, Y.total);
+    char* base = (char*)ws;
+    long* elem_first = (long*)(base + Y.elem_first);
+    long* block_first = (long*)(base + Y.block_first);
+    int* elem_clip = (int*)(base + Y.elem_clip);
+    uint32_t* keys_a = (uint32_t*)(base + Y.keys_a);
+    uint32_t* keys_b = (uint32_t*)(base + Y.keys_b);
+    uint8_t* y = (uint8_t*)(base + Y.y);
+    uint8_t* labels_a = (uint8_t*)(base + Y.labels_a);
+    uint8_t* labels_b = (uint8_t*)(base + Y.labels_b);
+    uint8_t* spred = (uint8_t*)(base + Y.spred);
+    uint8_t* bpred = (uint8_t*)(base + Y.bpred);
+    unsigned* table = (unsigned*)(base + Y.table);
+    void* sums = base + Y.sums;
+    ed::HeadNeg* scan = (ed::HeadNeg*)(base + Y.scan);
+    uint8_t* d_seg = (uint8_t*)(base + Y.seg);
+    long* d_counters = (long*)(base + Y.counters);
+    const int block = eval_block();
+    long blocks = 0;
+    for (int c = 0; c < C; ++c) blocks += eb::blocks_of(eb::clip_frames(clip_first_host, label_first_host, c), block);
+
+    if (E > 0) {
+        HIP_TRY(hipMemsetAsync(d_counters, 0, sizeof(long) * ed::COUNTERS * (size_t)C, st));
+        pd::scan_run<pd::OpSum2>(st, C, block, eb::ClipCountLoad{clip_first, label_first, block}, eb::ClipFirstStore{elem_first, block_first},
+                                 (pd::Long2*)(base + Y.sums_c));
+        hipLaunchKernelGGL(eb::frames_kernel, dim3(grid_for(E)), dim3(256), 0, st, probs, clip_first, labels, label_first, (const long*)elem_first, C, E, W,
+                           threshold, elem_clip, keys_a, y, spred, bpred, d_counters);
+        hipLaunchKernelGGL(eb::counts_kernel, dim3(grid_for(E)), dim3(256), 0, st, (const uint8_t*)y, (const uint8_t*)spred, (const uint8_t*)bpred,
+                           (const int*)elem_clip, (const long*)elem_first, E, d_counters);
+        const eb::BoundaryLoad flags{y, elem_clip, elem_first};
+        pd::scan_run<pd::OpSum2>(st, E, block, flags, eb::BoundaryStore{flags, spred, bpred, L, d_seg, Y.seg_cap}, (pd::Long2*)sums);
+        eb::sort_run(st, blocks, block, elem_first, block_first, C, keys_a, keys_b, y, labels_a, labels_b, table, (unsigned*)sums);
+        pd::scan_run<ed::OpHeadNeg>(st, E, block, eb::HeadNegLoad{keys_a, labels_a, elem_clip}, pd::PtrStore<ed::HeadNeg>{scan}, (ed::HeadNeg*)sums);
+        hipLaunchKernelGGL(eb::u2_kernel, dim3(grid_for(E)), dim3(256), 0, st, (const uint32_t*)keys_a, (const uint8_t*)labels_a, (const ed::HeadNeg*)scan,
+                           (const int*)elem_clip, (const long*)elem_first, E, d_counters);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(counters, d_counters, sizeof(long) * ed::COUNTERS * (size_t)C, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));   // the first of two
+    } else {
+        for (long k = 0; k < (long)ed::COUNTERS * C; ++k) counters[k] = 0;
+    }
+    long n_true = 0;
+    seg_first_host[0] = 0;
+    for (int c = 0; c < C; ++c) {
+        long* mine = counters + (size_t)c * ed::COUNTERS;
+        const long n = eb::clip_frames(clip_first_host, label_first_host, c);
+        mine[ed::C_N] = n;
+        if (mine[ed::C_TRUE] < 0 || mine[ed::C_TRUE] > (n + 1) / 2) return fail(SAVAD_E_STATE, "%ld true segments in the %ld frames of clip %d", mine[ed::C_TRUE], n, c);
+        n_true += mine[ed::C_TRUE];
+        seg_first_host[c + 1] = n_true;
+    }
+    if (n_true > seg_cap) return fail(SAVAD_E_INVALID, "%ld true segments, room for %ld", n_true, seg_cap);
+    if (n_true > 0) {
+        HIP_TRY(hipMemcpyAsync(seg, d_seg, (size_t)ed::SEG_BYTES * (size_t)n_true, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));   // the second
+    }
+    return n_true;
+}
+
+SAVAD_EXPORT long savad_eval_batch_counts_host(const float* probs, const int32_t* clip_first_host, const uint8_t* labels, const int32_t* label_first_host,
+                                               int C, int W, float threshold, int L, long* counters, uint8_t* seg, long seg_cap, long* seg_first_host) {
+    int rc;
+    long E;
+    if ((rc = eval_batch_check(clip_first_host, label_first_host, C, W, L, &E))) return rc;
+    if (!probs || !labels || !counters || !seg_first_host || seg_cap < 0 || (seg_cap > 0 && !seg)) return fail(SAVAD_E_INVALID, "null pointer");
+    const long n_true = eb::counts_host_batch(probs, clip_first_host, labels, label_first_host, C, W, threshold, L, counters, seg, seg_cap, seg_first_host);
     if (n_true > seg_cap) return fail(SAVAD_E_INVALID, "%ld true segments, room for %ld", n_true, seg_cap);
     return n_true;
 }
